@@ -7,7 +7,11 @@ points are exchanged with one RCCL all_gather and summed (weak scaling, per-GPU 
 
 `python bench.py --gpus N` launched bare starts its own N ranks (a torch.distributed.run child, before any GPU call).
 
-Also reported in the same JSON line: the NTT rates (configs[2]), the MSM+NTT kernel sum for
+A plain run (`--gpus N --steps K --warmup W`) does only what the headline needs: set-up, warm-up, the K timed steps, the
+outputs of the last step when `--dump-outputs DIR` is given, and the JSON line with `metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` and the workload's `config`.  Everything below runs only with `--full`.
+
+With --full, also reported in the same JSON line: the NTT rates (configs[2]), the MSM+NTT kernel sum for
 the k=17 proof op list, a real and VERIFIED k=17 proof through the reference's API
 (configs[3]) with the restated-reference CPU op list beside it, the proof-level batch (configs[4] in small:
 `batch_k17`, `proofs_per_s`), `roofline` for the dominant kernel (msm_accumulate) and `cpu_baseline` (the oracle's
@@ -79,6 +83,14 @@ def snapshot_tree(levels=20, nc=2):
     bal[:, 5:] = 0                                           # sums stay below 2^64 (N_BYTES = 8)
     d_bals = A.fr_to_montgomery(torch.from_numpy(bal.reshape(-1)).cuda())
     return DeviceMerkleSumTree(d_users, d_bals, levels, nc)
+
+
+def dump_outputs(out_dir, point):
+    """--dump-outputs: what a caller of the timed path receives from its last step, the MSM's 64-byte affine point (identity =
+    zeros), as DIR/msm_point.npy: rows x, y of 8 little-endian u32 words each (Montgomery form), as float64 (exact)"""
+    os.makedirs(out_dir, exist_ok=True)
+    words = np.frombuffer(np.ascontiguousarray(point, dtype=np.uint8).tobytes(), dtype="<u4")
+    np.save(os.path.join(out_dir, "msm_point.npy"), words.astype(np.float64).reshape(2, 8))
 
 
 def oracle_vk(params, vk):
@@ -626,8 +638,14 @@ def _main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=9)
     ap.add_argument("--log-n", type=int, default=LOG_N)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-extras", action="store_true", help="skip NTT / op-list extras")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the benchmark measures or checks: the sequential and per-kernel "
+                         "(roofline, phases) re-runs of the MSM, the extras (strong scaling, proof batch, NTT, proofs) and the CPU "
+                         "baselines; without it the run stops after the headline's timed steps")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed (the MSM's result point) to DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip NTT / op-list extras")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend for --gpus > 1: nccl (= RCCL, one GPU per rank); gloo rehearses the multi-rank logic on a "
                          "box with fewer GPUs than ranks (host-side collectives, ranks share GPUs round-robin)")
@@ -647,6 +665,8 @@ def _main():
     ap.add_argument("--acc-log", default="", help="profiling: write the library's msm_accumulate launch log (sg_msm_launch_log) to this file at the end "
                                                   "of the headline steps / of the batch, so that a kernel trace of this run attributes every launch to its job exactly")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.cpu_share > 0:
         allowed = sorted(os.sched_getaffinity(0))
@@ -799,7 +819,40 @@ def _main():
     dt, results = timed(args.steps, in_flight)
     result = results[-1]
     assert all((r == result).all() for r in results), "steps of one input must agree"
-    fs.partial.update({"value": world * n * args.steps / dt, "ms_per_step": dt / args.steps * 1e3, "n_gpus": world})
+    ms_per_step = dt / args.steps * 1e3
+    value = world * n * args.steps / dt
+    fs.partial.update({"value": value, "ms_per_step": ms_per_step, "n_gpus": world})
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, result)
+
+    # ---- the line's headline part
+    line = None
+    if rank == 0:
+        line = {
+            "metric": "msm_points_per_sec", "value": value, "unit": "points/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "u32", "dtype_note": "254-bit Montgomery integers: 8 x u32 words in memory, 9 x 29-bit limbs with 64-bit accumulators in registers",
+            "data": "synthetic",
+            "config": {"workload": f"standalone BN254 G1 MSM, 2^{args.log_n} uniform Fr scalars x synthetic-SRS "
+                                   f"affine points per GPU (BASELINE configs[1])",
+                       "points_per_gpu": n, "sharding": "point-sharded; exchange = ONE all_gather of steps x 64-B partials per timed region + host sums" if world > 1 else "none",
+                       "backend": ("nccl (RCCL)" if args.backend == "nccl" else "gloo (rehearsal: ranks share GPUs)") if world > 1 else None,
+                       "steps_in_flight": in_flight,
+                       "step": "one whole MSM per GPU (digits, sort, accumulate, reduce, host tail; result = the 64-byte point); "
+                               "consecutive steps are issued from steps_in_flight host threads, each call on its own lane of the library"},
+        }
+    if not args.full:
+        # a plain run: the headline is all it measures
+        pool.shutdown()
+        dump_acc_log("process start .. the headline's timed steps")
+        if world > 1:
+            _beat("final barrier")
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            fs.emit(line)
+        return line
+
     # the SAME regime once more, untimed, with every step's own HIP events (sg_msm_timings: the chained accumulation launch from
     # behind its wait for the previous one): the per-kernel figure of the regime `value` is quoted on, for `roofline`
     # (every rank runs it -- the region ends in the ranks' collective -- rank 0 reports its own launches)
@@ -844,27 +897,11 @@ def _main():
         phase_reps = [sg.best_multiexp(scal, bases, timings=True)[1] for _ in range(5)]
     dump_acc_log("process start .. the five lone timed MSMs after the headline steps")
 
-    # ---- the line's headline part, complete BEFORE any extra runs: if an extra hangs or the wall-clock limit comes, the
-    # watchdog still has a whole, valid line to print (FailSafe.base_line)
-    line = None
+    # ---- the line's headline part with its re-runs, complete BEFORE any extra runs: if an extra hangs or the wall-clock limit
+    # comes, the watchdog still has a whole, valid line to print (FailSafe.base_line)
     if rank == 0:
-        ms_per_step = dt / args.steps * 1e3
-        value = world * n * args.steps / dt
-        line = {
-            "metric": "msm_points_per_sec", "value": value, "unit": "points/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "u32", "dtype_note": "254-bit Montgomery integers: 8 x u32 words in memory, 9 x 29-bit limbs with 64-bit accumulators in registers",
-            "data": "synthetic",
-            "config": {"workload": f"standalone BN254 G1 MSM, 2^{args.log_n} uniform Fr scalars x synthetic-SRS "
-                                   f"affine points per GPU (BASELINE configs[1])",
-                       "points_per_gpu": n, "sharding": "point-sharded; exchange = ONE all_gather of steps x 64-B partials per timed region + host sums" if world > 1 else "none",
-                       "backend": ("nccl (RCCL)" if args.backend == "nccl" else "gloo (rehearsal: ranks share GPUs)") if world > 1 else None,
-                       "steps_in_flight": in_flight,
-                       "step": "one whole MSM per GPU (digits, sort, accumulate, reduce, host tail; result = the 64-byte point); "
-                               "consecutive steps are issued from steps_in_flight host threads, each call on its own lane of the library"},
-            "sequential": {"ms_per_step": dt_seq / args.steps * 1e3, "value": world * n * args.steps / dt_seq,
-                           "note": "the same steps strictly one after the other (--in-flight 1): the latency of one MSM"},
-        }
+        line["sequential"] = {"ms_per_step": dt_seq / args.steps * 1e3, "value": world * n * args.steps / dt_seq,
+                              "note": "the same steps strictly one after the other (--in-flight 1): the latency of one MSM"}
         if world > 1:
             # what the collectives library itself saw (the driver's "did RCCL see N ranks" check): the process group's size and backend
             line["config"]["ranks_seen_by_process_group"] = dist.get_world_size()

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-import os, random, subprocess, sys
+import os, random, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 from oracle import pyref as P
-exe = "/tmp/limb_curve29_check"
+_build_dir = tempfile.TemporaryDirectory(prefix="limb_curve29_check_")   # private to this run, removed at exit
+exe = os.path.join(_build_dir.name, "limb_curve29_check")
 # SG_CHECK_CXXFLAGS: other compiler flags for the driver (tests/test_sanitizers_cpu.py: -fsanitize=address,undefined)
 flags = os.environ.get("SG_CHECK_CXXFLAGS", "-O2").split()
 if flags != ["-O2"]:

@@ -210,6 +210,28 @@ def _check_two_rank_line(line, backend_word):
     return st["result_x"]
 
 
+def test_plain_bench_run_is_the_headline_and_dumps_the_last_steps_point(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the headline line alone (no re-runs, no extras), and
+    --dump-outputs writes the point the last timed step computed -- the oracle's MSM of the same seeded inputs"""
+    _gpu()
+    import torch
+    from circuits_halo2_amd.arithmetic import fr_to_montgomery, g1_fixed_base_mul
+    from circuits_halo2_amd.utils import DEFAULT_SEED, random_fr_canonical
+    from oracle import oracle as O
+    n = 1 << 12
+    line = _run_bench(["--gpus", "1", "--steps", "4", "--warmup", "1", "--log-n", "12", "--dump-outputs", str(tmp_path)])
+    assert line["metric"] == "msm_points_per_sec" and line["unit"] == "points/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "u32" and line["steps"] == 4 and line["ms_per_step"] > 0
+    assert abs(line["value"] - n / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+    assert not {"sequential", "roofline", "msm_phases_ms", "batched", "cpu_baseline", "batch_k17"} & set(line)
+    got = np.load(tmp_path / "msm_point.npy")
+    assert got.dtype == np.float64 and got.shape == (2, 8)
+    scal = fr_to_montgomery(torch.from_numpy(random_fr_canonical(DEFAULT_SEED, n)).cuda())
+    bases = g1_fixed_base_mul(fr_to_montgomery(torch.from_numpy(random_fr_canonical(0x7A55, n)).cuda()))
+    want = O.best_multiexp(scal.cpu().numpy(), bases.cpu().numpy(), 4)
+    assert (got.reshape(-1).astype(np.uint32).view(np.uint8) == want).all()
+
+
 def test_bench_starts_its_own_ranks_two_rank_rehearsal():
     """`python bench.py --gpus 2` launched bare: the parent starts the two ranks itself (torch.distributed.run child, before
     it touches the GPU), rank 0 prints the one JSON line with n_gpus = 2.  On this one-GPU box the ranks rehearse with the
@@ -217,10 +239,10 @@ def test_bench_starts_its_own_ranks_two_rank_rehearsal():
     (weak: 2^20 per rank; strong: one 2^23-point MSM cut in two), setup broadcast, the batch's users dealt to the ranks and
     kept in flight, max-over-ranks timing -- is the N > 1 code path.  The strong-scaling MSM's result must be the point the
     same extra finds on ONE rank (same 2^23 inputs at every N)."""
-    two = _run_bench(["--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1", "--batch-proofs", "6", "--batch-repeats", "1",
+    two = _run_bench(["--gpus", "2", "--backend", "gloo", "--full", "--steps", "3", "--warmup", "1", "--batch-proofs", "6", "--batch-repeats", "1",
                       "--no-cpu", "--log-n", "20"])
     x2 = _check_two_rank_line(two, "gloo")
-    one = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch-proofs", "0", "--no-cpu", "--log-n", "20", "--strong-only"])
+    one = _run_bench(["--gpus", "1", "--full", "--steps", "3", "--warmup", "1", "--batch-proofs", "0", "--no-cpu", "--log-n", "20", "--strong-only"])
     assert one["msm_strong_scaling_2^23"]["result_x"] == x2 and one["msm_strong_scaling_2^23"]["points_per_gpu"] == 1 << 23
 
 
@@ -230,7 +252,7 @@ def test_four_rank_rehearsal_on_one_gpu():
     batch dealt over four ranks, the setup broadcast to three receivers, max-over-ranks timing, the watchdog's per-step
     allowance under four-fold contention for the device, and still ONE JSON line; the strong-scaling MSM cut in four gives the
     point it gives cut in two or not at all"""
-    line = _run_bench(["--gpus", "4", "--backend", "gloo", "--steps", "3", "--warmup", "1", "--batch-proofs", "8", "--batch-repeats", "1",
+    line = _run_bench(["--gpus", "4", "--backend", "gloo", "--full", "--steps", "3", "--warmup", "1", "--batch-proofs", "8", "--batch-repeats", "1",
                        "--batch-in-flight", "2", "--no-cpu", "--log-n", "20"])
     assert line["n_gpus"] == 4 and line["value"] > 0 and line["scaling"] == "weak"
     assert line["config"]["ranks_seen_by_process_group"] == 4 and line["config"]["rccl_ranks_seen"] is None
@@ -240,7 +262,7 @@ def test_four_rank_rehearsal_on_one_gpu():
     assert all(r["proofs"] == 8 and r["errors"] == 0 for r in b["repeats"])          # dealt 2 + 2 + 2 + 2, every rank counted
     st = line["msm_strong_scaling_2^23"]
     assert st["n_gpus"] == 4 and st["points_per_gpu"] == 1 << 21 and st["every_rank_partial_equals_inner_product_times_G"] is True
-    one = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch-proofs", "0", "--no-cpu", "--log-n", "20", "--strong-only"])
+    one = _run_bench(["--gpus", "1", "--full", "--steps", "3", "--warmup", "1", "--batch-proofs", "0", "--no-cpu", "--log-n", "20", "--strong-only"])
     assert one["msm_strong_scaling_2^23"]["result_x"] == st["result_x"]
 
 
@@ -258,7 +280,7 @@ def test_a_rank_killed_mid_batch_costs_an_error_line_not_the_run():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env["SUMMA_BENCH_FAULT"] = "1:batch:1.0"
     t0 = time.time()
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--full", "--steps", "3", "--warmup", "1",
                         "--batch-proofs", "512", "--batch-repeats", "1", "--batch-in-flight", "8", "--no-cpu", "--log-n", "20"],
                        capture_output=True, text=True, timeout=400, env=env, cwd=root)
     took = time.time() - t0
@@ -279,7 +301,7 @@ def test_two_rank_nccl():
     import torch
     if torch.cuda.device_count() < 2:
         pytest.skip("needs two GPUs (RCCL between ranks)")
-    line = _run_bench(["--gpus", "2", "--backend", "nccl", "--steps", "3", "--warmup", "1", "--batch-proofs", "6", "--batch-repeats", "1",
+    line = _run_bench(["--gpus", "2", "--backend", "nccl", "--full", "--steps", "3", "--warmup", "1", "--batch-proofs", "6", "--batch-repeats", "1",
                        "--no-cpu", "--log-n", "20"])
     _check_two_rank_line(line, "nccl")
 

@@ -10,7 +10,7 @@ out="gpurun_out/${tag}_ab_frontend.txt"
 : > "$out"
 for rep in 1 2; do
   for fe in 0 1; do
-    line=$(SG_PARAMS="msm.fused_frontend=$fe" python bench.py --steps 20 --warmup 5 --no-cpu --no-extras 2>/dev/null | tail -1)
+    line=$(SG_PARAMS="msm.fused_frontend=$fe" python bench.py --full --steps 20 --warmup 5 --no-cpu --no-extras 2>/dev/null | tail -1)
     python - "$fe" "$line" >> "$out" <<'PY'
 import json, sys
 fe, line = sys.argv[1:3]

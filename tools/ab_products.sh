@@ -21,13 +21,13 @@ PY
 for r in 1 2 3; do for v in v0 v1; do
   cp circuits_halo2_amd/libsumma_gpu_$v.so circuits_halo2_amd/libsumma_gpu.so
   echo -n "$v round $r | msm "
-  python bench.py --steps 30 --warmup 5 --no-cpu --no-extras 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['ms_per_step'],3), 'sequential', round(d['sequential']['ms_per_step'],3), {k:round(v,3) for k,v in d['msm_phases_ms'].items() if k.endswith('_ms')}, end=' | proof ')"
+  python bench.py --full --steps 30 --warmup 5 --no-cpu --no-extras 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['ms_per_step'],3), 'sequential', round(d['sequential']['ms_per_step'],3), {k:round(v,3) for k,v in d['msm_phases_ms'].items() if k.endswith('_ms')}, end=' | proof ')"
   ./tools/create_proof_cpp $out/bundle17.bin $out/proof_$v.bin 30 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['create_proof_ms'])"
 done; done
 for v in v0 v1; do
   cp circuits_halo2_amd/libsumma_gpu_$v.so circuits_halo2_amd/libsumma_gpu.so
   echo -n "$v full bench | "
-  python bench.py --no-cpu 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('msm', round(d['ms_per_step'],3), 'ntt22', round(d['ntt']['2^22']['ms'],4), 'ntt17', round(d['ntt']['2^17']['ms'],4), 'proof py', round(d['create_proof_k17']['ms'],3), 'cpp', d['create_proof_k17']['ms_cpp_driver'], 'batch', {k:round(v['proofs_per_s'],1) for k,v in d['batch_k17']['by_in_flight'].items()}, 'mst', round(d['witness_mst_2^20']['ms'],2))"
+  python bench.py --full --no-cpu 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('msm', round(d['ms_per_step'],3), 'ntt22', round(d['ntt']['2^22']['ms'],4), 'ntt17', round(d['ntt']['2^17']['ms'],4), 'proof py', round(d['create_proof_k17']['ms'],3), 'cpp', d['create_proof_k17']['ms_cpp_driver'], 'batch', {k:round(v['proofs_per_s'],1) for k,v in d['batch_k17']['by_in_flight'].items()}, 'mst', round(d['witness_mst_2^20']['ms'],2))"
 done
 cp /tmp/lib_orig.so circuits_halo2_amd/libsumma_gpu.so
 rm -f $out/bundle17.bin
