@@ -83,7 +83,8 @@ bool numerator_fused_available(const GateProgram& gates, const GateProgram& look
   return for_known_pair(gates, lookup_input, [](auto, int) {});
 }
 hipError_t numerator_fused(const GateProgram& gates, const GateProgram& lookup_input, NumeratorArgs& a, hipStream_t stream) {
-  if (!numerator_fused_available(gates, lookup_input) || a.perm.cosets == 0 || a.perm.ext_k != a.perm.k || a.look.ext_k != a.look.k)
+  // one program object in both roles would be one constant table serving two programs
+  if (&gates == &lookup_input || !numerator_fused_available(gates, lookup_input) || a.perm.cosets == 0 || a.perm.ext_k != a.perm.k || a.look.ext_k != a.look.k)
     return hipErrorInvalidValue;
   a.n_consts = (uint32_t)(gates.const_words.size() / 8);
   a.n_input_consts = (uint32_t)(lookup_input.const_words.size() / 8);

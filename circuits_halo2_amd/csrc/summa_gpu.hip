@@ -2834,8 +2834,21 @@ int sg_quotient_numerator_cosets_dev(void* d_values, const sg_graph* gates, cons
       (n_advice && !d_advice) || (n_instance && !d_instance) || (n_challenges && !challenges))
     return fail(SG_ERR_INVALID, "sg_quotient_numerator_cosets: null argument");
   if (!coset_shape_ok(k, ext_k, n_cosets) || n_cosets > QUOT_MAX_COSETS) return fail(SG_ERR_INVALID, "sg_quotient_numerator_cosets: bad shape");
-  if (nsets == 0 || nsets > QUOT_MAX_SETS || ncols == 0 || ncols > QUOT_MAX_COLS || chunk_len == 0 || (ncols + chunk_len - 1) / chunk_len != nsets)
+  // every precondition of either path is checked here, before one is chosen: a call both paths would refuse is refused
+  // the same way, and nothing is launched for it
+  if (nsets == 0 || nsets > QUOT_MAX_SETS || ncols == 0 || ncols > QUOT_MAX_COLS || chunk_len == 0 || chunk_len > 11 ||
+      (ncols + chunk_len - 1) / chunk_len != nsets || last_rotation_abs >= (1u << k))
     return fail(SG_ERR_INVALID, "sg_quotient_numerator_cosets: bad permutation shape");
+  for (uint32_t i = 0; i < n_fixed; i++)
+    if (!d_fixed[i]) return fail(SG_ERR_INVALID, "sg_quotient_numerator_cosets: null column");
+  for (uint32_t i = 0; i < n_advice; i++)
+    if (!d_advice[i]) return fail(SG_ERR_INVALID, "sg_quotient_numerator_cosets: null column");
+  for (uint32_t i = 0; i < n_instance; i++)
+    if (!d_instance[i]) return fail(SG_ERR_INVALID, "sg_quotient_numerator_cosets: null column");
+  for (uint32_t i = 0; i < nsets; i++)
+    if (!d_z[i]) return fail(SG_ERR_INVALID, "sg_quotient_numerator_cosets: null z");
+  for (uint32_t i = 0; i < ncols; i++)
+    if (!d_perm_cols[i] || !d_sigma[i]) return fail(SG_ERR_INVALID, "sg_quotient_numerator_cosets: null permutation column");
   bool fused = false;
   if (g_numerator_fused.load() && n_fixed + n_advice + n_instance <= NUM_MAX_COLS) {
     LOCKED_CTX();
@@ -2844,7 +2857,8 @@ int sg_quotient_numerator_cosets_dev(void* d_values, const sg_graph* gates, cons
     const uint8_t none[32] = {0};
     TRY(gate_program_for(gates, n_fixed, n_advice, n_instance, challenges, n_challenges, beta, gamma, theta, y, &pg));
     TRY(gate_program_for(lookup_input, n_fixed, n_advice, n_instance, none, 0, beta, gamma, theta, y, &pi));
-    if (numerator_fused_available(*pg, *pi)) {
+    // (two structurally identical programs are one cache entry: its constant table holds the second call's constants only)
+    if (pg != pi && numerator_fused_available(*pg, *pi)) {
       NumeratorArgs a;
       std::memset(&a, 0, sizeof a);
       a.values = static_cast<fp_words*>(d_values);
@@ -2852,15 +2866,9 @@ int sg_quotient_numerator_cosets_dev(void* d_values, const sg_graph* gates, cons
       for (uint32_t i = 0; i < n_fixed; i++) a.cols[c++] = static_cast<const fp_words*>(d_fixed[i]);
       for (uint32_t i = 0; i < n_advice; i++) a.cols[c++] = static_cast<const fp_words*>(d_advice[i]);
       for (uint32_t i = 0; i < n_instance; i++) a.cols[c++] = static_cast<const fp_words*>(d_instance[i]);
-      for (uint32_t i = 0; i < c; i++)
-        if (!a.cols[i]) return fail(SG_ERR_INVALID, "sg_quotient_numerator_cosets: null column");
       QuotPermArgs& pa = a.perm;
-      for (uint32_t i = 0; i < nsets; i++) {
-        if (!d_z[i]) return fail(SG_ERR_INVALID, "sg_quotient_numerator_cosets: null z");
-        pa.z[i] = static_cast<const fp_words*>(d_z[i]);
-      }
+      for (uint32_t i = 0; i < nsets; i++) pa.z[i] = static_cast<const fp_words*>(d_z[i]);
       for (uint32_t i = 0; i < ncols; i++) {
-        if (!d_perm_cols[i] || !d_sigma[i]) return fail(SG_ERR_INVALID, "sg_quotient_numerator_cosets: null permutation column");
         pa.cols[i] = static_cast<const fp_words*>(d_perm_cols[i]);
         pa.sigma[i] = static_cast<const fp_words*>(d_sigma[i]);
       }
