@@ -321,65 +321,65 @@ def prove_batch(tree, user_indices, params, pk, levels: int, flavour: str = "evm
         elif ffi.get_param("host.wait_sleep_us") == 0:
             scope["host.wait_sleep_us"] = 50
     params_scope = _ParamScope(scope)
-    params_scope.enter()
-    mine = deal(list(user_indices))
-    res = BatchResult()
-    if prove is None:
-        res.wait_sleep_us = ffi.get_param("host.wait_sleep_us")
     ahead = None
-    if make_circuit is None:
-        if hasattr(tree, "d_h"):      # a device-resident snapshot: the witness never visits the host
-            if len(mine) >= 8 and len(set(mine)) == len(mine) and hasattr(pk, "circuit_shape"):
-                ahead = _WitnessAhead(tree, pk, mine)       # chunks of users per witness launch, ahead of the provers
-                make_circuit = ahead.circuit
-            else:
-                make_circuit = lambda i: api.MstInclusionCircuit.init_from_tree(tree, i)
-        else:
-            make_circuit = lambda i: api.MstInclusionCircuit.init(tree.generate_proof(i), levels)
-    if prove is None:
-        if flavour == "evm":
-            prove = lambda c: api.gen_proof_solidity_calldata(params, pk, c)
-        else:
-            def prove(c):
-                inst = c.instances()
-                return api.full_prover(params, pk, c, inst), inst[0]
-    lock = threading.Lock()
-    local = threading.local()
-
-    def work(i):
-        try:
-            import torch
-            on_gpu = torch.cuda.is_available()
-        except Exception:  # pragma: no cover
-            on_gpu = False
-        try:
-            api.set_commit_combining(combine)
-            if on_gpu:
-                if not hasattr(local, "stream"):
-                    local.stream = torch.cuda.Stream()
-                with torch.cuda.stream(local.stream):
-                    out = prove(make_circuit(i))
-                    local.stream.synchronize()
-            else:
-                out = prove(make_circuit(i))
-            with lock:
-                res.proofs[i] = out
-        except Exception as ex:   # one bad witness must not lose the batch
-            with lock:
-                res.errors[i] = repr(ex)
-
-    t0 = time.perf_counter()
     try:
+        params_scope.enter()
+        mine = deal(list(user_indices))
+        res = BatchResult()
+        if prove is None:
+            res.wait_sleep_us = ffi.get_param("host.wait_sleep_us")
+        if make_circuit is None:
+            if hasattr(tree, "d_h"):      # a device-resident snapshot: the witness never visits the host
+                if len(mine) >= 8 and len(set(mine)) == len(mine) and hasattr(pk, "circuit_shape"):
+                    ahead = _WitnessAhead(tree, pk, mine)       # chunks of users per witness launch, ahead of the provers
+                    make_circuit = ahead.circuit
+                else:
+                    make_circuit = lambda i: api.MstInclusionCircuit.init_from_tree(tree, i)
+            else:
+                make_circuit = lambda i: api.MstInclusionCircuit.init(tree.generate_proof(i), levels)
+        if prove is None:
+            if flavour == "evm":
+                prove = lambda c: api.gen_proof_solidity_calldata(params, pk, c)
+            else:
+                def prove(c):
+                    inst = c.instances()
+                    return api.full_prover(params, pk, c, inst), inst[0]
+        lock = threading.Lock()
+        local = threading.local()
+
+        def work(i):
+            try:
+                import torch
+                on_gpu = torch.cuda.is_available()
+            except Exception:  # pragma: no cover
+                on_gpu = False
+            try:
+                api.set_commit_combining(combine)
+                if on_gpu:
+                    if not hasattr(local, "stream"):
+                        local.stream = torch.cuda.Stream()
+                    with torch.cuda.stream(local.stream):
+                        out = prove(make_circuit(i))
+                        local.stream.synchronize()
+                else:
+                    out = prove(make_circuit(i))
+                with lock:
+                    res.proofs[i] = out
+            except Exception as ex:   # one bad witness must not lose the batch
+                with lock:
+                    res.errors[i] = repr(ex)
+
+        t0 = time.perf_counter()
         if in_flight <= 1:
             for i in mine:
                 work(i)
         else:
             list(_workers(in_flight).map(work, mine))
+        res.seconds = time.perf_counter() - t0
     finally:
         if ahead is not None:
             ahead.close()
         params_scope.leave()     # a later caller's lone proofs do not wait 5 ms for company, nor sleep between polls
-    res.seconds = time.perf_counter() - t0
     return res
 
 
@@ -392,19 +392,33 @@ class _ParamScope:
 
     def __init__(self, values):
         self.values = dict(values)
+        self.entered = False
 
     def enter(self):
+        """all or nothing: if a value is refused, the ones set before it are put back and the scope does not count"""
         cls = _ParamScope
         with cls._lock:
-            for name, value in self.values.items():
-                if name not in cls._saved:
-                    cls._saved[name] = ffi.get_param(name)
-                ffi.set_param(name, value)
+            found = {}
+            try:
+                for name, value in self.values.items():
+                    found[name] = ffi.get_param(name)
+                    ffi.set_param(name, value)
+            except BaseException:
+                for name, value in found.items():
+                    ffi.set_param(name, value)
+                raise
+            for name, value in found.items():
+                cls._saved.setdefault(name, value)
             cls._active += 1
+            self.entered = True
 
     def leave(self):
+        """(a no-op for a scope that did not enter)"""
         cls = _ParamScope
         with cls._lock:
+            if not self.entered:
+                return
+            self.entered = False
             cls._active -= 1
             if cls._active == 0:
                 for name, value in cls._saved.items():

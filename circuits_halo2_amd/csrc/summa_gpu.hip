@@ -200,6 +200,135 @@ struct Context {
   std::map<hipStream_t, LookupWork> lookup_work;
 };
 
+static constexpr int kLanes = 8;          // upper bound; "lanes" of them are handed out (the concurrency model, below)
+
+// ---- runtime parameters (sg_set_param / sg_get_param, one line each in include/summa_gpu.h).  kParams is the only list of
+// them: a row holds a name, its scope, its default, what an incoming value becomes and how it takes effect.  The values in
+// effect live in Shared::param; the library reads its configs and those atomics as before -- nothing here is looked up by
+// name on a launch path.
+enum class Scope {
+  process,   // Shared::param is what the library reads (to_process: a copy elsewhere that needs the value too)
+  lane,      // to_lane writes one context's configs: every existing lane when the value is set, every new one when it is made
+  device,    // side_prio: to_process writes the device's copy -- when set while a device is bound, and when a context is made
+};
+struct ParamRow {
+  const char* name;
+  Scope scope;
+  int def;                          // what sg_get_param reports until the parameter is set
+  int (*clamp)(int);                // the value in effect for a requested one (>= 0), or -1: rejected
+  void (*to_lane)(Context&, int);
+  int (*to_process)(int);
+};
+template <int lo, int hi>
+constexpr int in_range(int v) { return std::min(hi, std::max(lo, v)); }
+constexpr int kNoLimit = 0x7fffffff;
+// both MSM engines of a context hold one config
+void msm_set(Context& c, uint32_t MsmConfig::*field, int v) { c.msm.config().*field = c.msm_b.config().*field = (uint32_t)v; }
+// side_prio is device-wide, not per lane: wave priority 3 for every kernel but msm_accumulate (side_prio.cuh)
+int set_side_prio(int on) {
+  hipError_t e = msm_set_side_prio(on);
+  if (e == hipSuccess) e = ntt_set_side_prio(on);
+  if (e == hipSuccess) e = poly_set_side_prio(on);
+  if (e == hipSuccess) e = quotient_set_side_prio(on);
+  if (e == hipSuccess) e = gates_set_side_prio(on);
+  if (e == hipSuccess) e = numerator_set_side_prio(on);
+  if (e == hipSuccess) e = witness_set_side_prio(on);
+  if (e == hipSuccess) e = abi_set_side_prio(on);
+  if (e != hipSuccess) return hip_fail("side_prio", e);
+  return SG_OK;
+}
+// a lane row named after its config field, whose default is what the config struct holds
+#define MSM_ROW(field, clamp) \
+  { "msm." #field, Scope::lane, (int)MsmConfig{}.field, clamp, [](Context& c, int v) { msm_set(c, &MsmConfig::field, v); }, nullptr }
+#define NTT_ROW(field, clamp) \
+  { "ntt." #field, Scope::lane, (int)NttConfig{}.field, clamp, [](Context& c, int v) { c.ntt.config().field = (uint32_t)v; }, nullptr }
+constexpr ParamRow kParams[] = {
+    {"lanes", Scope::process, 4, [](int v) { return v >= 1 && v <= kLanes ? v : -1; }, nullptr, nullptr},
+    {"commit.combine_wait_us", Scope::process, 300, in_range<0, 100000>, nullptr, nullptr},
+    {"commit.combine_target", Scope::process, 4, in_range<1, 32>, nullptr, nullptr},
+    {"commit.combine_runners", Scope::process, 1, in_range<1, 4>, nullptr, nullptr},
+    {"host.wait_sleep_us", Scope::process, 0, in_range<0, 1000>, nullptr, [](int v) -> int { host_wait_sleep_us().store(v); return SG_OK; }},
+    {"msm.host_chunks", Scope::process, 0, in_range<0, 8>, nullptr, nullptr},
+    {"msm.tiny_max", Scope::process, (int)MSM_TINY_MAX, in_range<0, (int)MSM_TINY_MAX>, nullptr, nullptr},
+    // setting 1 clears the launch log, so that set(get) is not a no-op here while the log is on
+    {"msm.acc_log", Scope::process, 0, in_range<0, 1>, nullptr, [](int v) -> int { msm_acc_log_enable(v != 0); return SG_OK; }},
+    {"ntt.coset_scale_pass", Scope::process, 0, in_range<0, 1>, nullptr, nullptr},
+    {"quotient.fused_numerator", Scope::process, 1, in_range<0, 1>, nullptr, nullptr},
+    {"debug.fail_next_fused_job", Scope::process, 0, in_range<0, 1>, nullptr, nullptr},   // the combiner takes it back to 0
+    {"side_prio", Scope::device, 1, in_range<0, 1>, nullptr, set_side_prio},
+    MSM_ROW(window_bits, (in_range<0, kNoLimit>)),
+    MSM_ROW(log_seg, (in_range<0, 12>)),
+    // 0: the built-in sizes of each kind (2^25 generic, 2^27 fixed-base); anything else applies to both
+    {"msm.log_fuse_entries", Scope::lane, 0, [](int v) { return v ? in_range<16, 30>(v) : 0; },
+     [](Context& c, int v) {
+       msm_set(c, &MsmConfig::log_fuse_entries, v ? v : (int)MSM_LOG_FUSE_ENTRIES_GENERIC);
+       msm_set(c, &MsmConfig::log_fuse_entries_fixed, v ? v : (int)MSM_LOG_FUSE_ENTRIES_FIXED);
+     }, nullptr},
+    {"msm.red_threads", Scope::lane, 256, [](int v) { return v <= 64 ? 64 : v <= 128 ? 128 : 256; },
+     [](Context& c, int v) { msm_set(c, &MsmConfig::red_threads, v); }, nullptr},
+    {"msm.acc_threads", Scope::lane, 0, [](int v) { return v == 64 || v == 128 || v == 256 ? v : 0; },
+     [](Context& c, int v) { msm_set(c, &MsmConfig::acc_threads, v); }, nullptr},
+    MSM_ROW(log_scatter_rounds, (in_range<0, 6>)),
+    MSM_ROW(two_pass, (in_range<0, 2>)),
+    MSM_ROW(fused_frontend, (in_range<0, 2>)),
+    MSM_ROW(acc_trace, (in_range<0, 1>)),
+    MSM_ROW(acc_chain, (in_range<0, 1>)),
+    MSM_ROW(red_lean, (in_range<0, 2>)),
+    MSM_ROW(acc_waves_fixed, (in_range<0, 8>)),
+    MSM_ROW(acc_waves, (in_range<0, 8>)),
+    MSM_ROW(merge_quad_tasks, (in_range<0, kNoLimit>)),
+    MSM_ROW(red2d_max_sets, (in_range<0, 32>)),
+    MSM_ROW(red2d_fold, (in_range<1, 256>)),
+    MSM_ROW(red2d_prefold, (in_range<0, 1>)),
+    MSM_ROW(prefold_quad_buckets, (in_range<0, kNoLimit>)),
+    MSM_ROW(red2d, (in_range<0, 2>)),
+    MSM_ROW(quad, (in_range<0, 2>)),
+    MSM_ROW(log_red_chunk, (in_range<0, 8>)),
+    NTT_ROW(tile_log, (in_range<6, 12>)),
+    NTT_ROW(threads, (in_range<64, 1024>)),
+    NTT_ROW(big_tile_log, ([](int v) { return v ? in_range<6, 12>(v) : 0; })),   // 0: one shape for all
+    NTT_ROW(big_threads, (in_range<64, 1024>)),
+    NTT_ROW(batch_min, (in_range<1, kNoLimit>)),
+    NTT_ROW(big_log, (in_range<1, kNoLimit>)),
+    // 0: by size, 1: always, 2: never (NttConfig::radix4 counts the other way round: 1, 2, 0)
+    {"ntt.radix4", Scope::lane, 0, [](int v) { return v == 1 || v == 2 ? v : 0; },
+     [](Context& c, int v) { c.ntt.config().radix4 = v == 1 ? 2u : v == 2 ? 0u : 1u; }, nullptr},
+    // the plans are cut by these two: the cached ones go
+    {"ntt.max_single_log", Scope::lane, (int)NttConfig{}.max_single_log, in_range<1, 12>,
+     [](Context& c, int v) { c.ntt.config().max_single_log = (uint32_t)v; c.ntt.clear(); }, nullptr},
+    {"ntt.max_multi_log", Scope::lane, (int)NttConfig{}.max_multi_log, in_range<4, 12>,
+     [](Context& c, int v) { c.ntt.config().max_multi_log = (uint32_t)v; c.ntt.clear(); }, nullptr},
+};
+#undef MSM_ROW
+#undef NTT_ROW
+constexpr size_t kNumParams = sizeof kParams / sizeof kParams[0];
+constexpr bool same_name(const char* a, const char* b) {
+  while (*a && *a == *b) a++, b++;
+  return *a == *b;
+}
+constexpr size_t param_index(const char* name) {   // kNumParams: no such parameter
+  size_t i = 0;
+  while (i < kNumParams && !same_name(kParams[i].name, name)) i++;
+  return i;
+}
+constexpr bool params_sound() {   // every default is a value its own row keeps; every name is unique; every row takes effect
+  for (size_t i = 0; i < kNumParams; i++) {
+    const ParamRow& r = kParams[i];
+    if (r.def < 0 || r.clamp(r.def) != r.def || param_index(r.name) != i) return false;
+    if ((r.scope == Scope::lane) != (r.to_lane != nullptr) || (r.scope == Scope::device && !r.to_process)) return false;
+  }
+  return true;
+}
+static_assert(params_sound(), "kParams");
+// the process rows the library reads in Shared::param
+constexpr size_t kRowLanes = param_index("lanes"), kRowCombineWaitUs = param_index("commit.combine_wait_us"),
+                 kRowCombineTarget = param_index("commit.combine_target"), kRowCombineRunners = param_index("commit.combine_runners"),
+                 kRowHostChunks = param_index("msm.host_chunks"), kRowTinyMax = param_index("msm.tiny_max"),
+                 kRowCosetScalePass = param_index("ntt.coset_scale_pass"), kRowFusedNumerator = param_index("quotient.fused_numerator"),
+                 kRowFailNextFusedJob = param_index("debug.fail_next_fused_job");
+static_assert(std::max({kRowLanes, kRowCombineWaitUs, kRowCombineTarget, kRowCombineRunners, kRowHostChunks, kRowTinyMax,
+                        kRowCosetScalePass, kRowFusedNumerator, kRowFailNextFusedJob}) < kNumParams, "kParams");
+
 // What every lane shares: the device index, the SRS cache (read-only after upload / precompute) and the runtime
 // parameters.  Guarded by its own short mutex (never held across device work).
 struct Shared {
@@ -207,10 +336,13 @@ struct Shared {
   int device = -1;
   std::map<uint64_t, Srs> srs;
   uint64_t next_handle = 1;
-  std::vector<std::pair<std::string, int>> params;  // sg_set_param history, replayed on every new lane
+  std::atomic<int> param[kNumParams];   // the value in effect of each row of kParams: written under mu, read anywhere
+  Shared() {
+    for (size_t i = 0; i < kNumParams; i++) param[i].store(kParams[i].def);
+  }
 };
 
-// Concurrency model.  The library keeps g_lane_count (default 4, at most kLanes) independent contexts ("lanes"), each with its own streams, MSM
+// Concurrency model.  The library keeps "lanes" (default 4, at most kLanes) independent contexts ("lanes"), each with its own streams, MSM
 // engines, NTT plans, staging and scratch buffers.  A call takes ONE lane for its whole duration (lane 0 when it is
 // free, so a single-threaded caller always works in the same warm work space) and touches nothing of the others:
 // calls from different host threads -- halo2 reaches best_multiexp / best_fft from rayon iterators; the batch driver
@@ -219,8 +351,6 @@ struct Shared {
 // as the call returns.  The lock is per lane and re-entrant for the owning thread (entry points that stage host
 // buffers and then call their `_dev` form keep the lane in between).
 Shared g_sh;
-static constexpr int kLanes = 8;          // upper bound; g_lane_count of them are handed out (sg_set_param "lanes")
-std::atomic<int> g_lane_count{4};
 struct Lane {
   std::mutex mu;
   Context* ctx = nullptr;
@@ -231,7 +361,13 @@ thread_local Context* g_ctx = nullptr;   // the lane this thread holds (valid in
 thread_local Lane* g_held = nullptr;
 thread_local int g_depth = 0;
 
-int apply_param(Context& c, const std::string& s, int value);
+// a new context takes every lane and device value in effect
+void apply_params(Context& c) {
+  for (size_t i = 0; i < kNumParams; i++) {
+    if (kParams[i].scope == Scope::lane) kParams[i].to_lane(c, g_sh.param[i].load());
+    else if (kParams[i].scope == Scope::device) (void)kParams[i].to_process(g_sh.param[i].load());
+  }
+}
 
 // The main streams of the lanes in use are created together, before any of the library's other streams, so that they land
 // on different hardware queues: two streams on ONE queue run their kernels one after the other whatever the priorities,
@@ -253,7 +389,7 @@ int make_context(int device, int lane_index, Context** out) {
   hipError_t e = hipSetDevice(device);
   if (e == hipSuccess) {
     std::lock_guard<std::mutex> lk(g_sh.mu);
-    e = make_lane_streams(std::max(g_lane_count.load(), lane_index + 1));
+    e = make_lane_streams(std::max(g_sh.param[kRowLanes].load(), lane_index + 1));
     if (e == hipSuccess) c->stream = g_lane_main[lane_index];
   }
   if (e == hipSuccess) e = c->ntt.init();
@@ -313,7 +449,6 @@ void destroy_context(Context* c) {
 // take a lane for the calling thread (g_ctx / g_held): lane 0 if free, else the first free one, else wait
 int acquire_lane() {
   int device;
-  std::vector<std::pair<std::string, int>> params;
   {
     std::lock_guard<std::mutex> lk(g_sh.mu);
     if (g_sh.device < 0) {
@@ -323,10 +458,9 @@ int acquire_lane() {
       g_sh.device = 0;
     }
     device = g_sh.device;
-    params = g_sh.params;
   }
   Lane* lane = nullptr;
-  const int lanes = g_lane_count.load();
+  const int lanes = g_sh.param[kRowLanes].load();
   for (int i = 0; i < lanes && !lane; i++)
     if (g_lanes[i].mu.try_lock()) lane = &g_lanes[i];
   if (!lane) {   // more concurrent callers than lanes: wait for one (round-robin), for the whole of its current call
@@ -339,7 +473,7 @@ int acquire_lane() {
       lane->mu.unlock();
       return rc;
     }
-    for (auto& kv : params) (void)apply_param(*lane->ctx, kv.first, kv.second);
+    apply_params(*lane->ctx);
   }
   hipError_t e = hipSetDevice(device);
   if (e != hipSuccess) {
@@ -466,57 +600,6 @@ int download(uint8_t* host, const void* dev, size_t bytes, hipStream_t s) {
     if (_rc != SG_OK) return _rc; \
   } while (0)
 
-int apply_param(Context& c, const std::string& s, int value) {
-  if (s == "msm.window_bits") c.msm.config().window_bits = c.msm_b.config().window_bits = (uint32_t)value;
-  else if (s == "msm.log_seg") c.msm.config().log_seg = c.msm_b.config().log_seg = (uint32_t)std::min(12, value);
-  else if (s == "msm.log_fuse_entries") {   // one value for generic and fixed-base jobs; 0: the built-in defaults (what sg_get_param reports for a parameter never set)
-    const uint32_t v = (uint32_t)std::max(16, std::min(30, value));
-    c.msm.config().log_fuse_entries = c.msm_b.config().log_fuse_entries = value == 0 ? MSM_LOG_FUSE_ENTRIES_GENERIC : v;
-    c.msm.config().log_fuse_entries_fixed = c.msm_b.config().log_fuse_entries_fixed = value == 0 ? MSM_LOG_FUSE_ENTRIES_FIXED : v;
-  }
-  else if (s == "msm.red_threads") { uint32_t v = value <= 64 ? 64 : value <= 128 ? 128 : 256; c.msm.config().red_threads = c.msm_b.config().red_threads = v; }
-  else if (s == "msm.log_scatter_rounds") c.msm.config().log_scatter_rounds = c.msm_b.config().log_scatter_rounds = (uint32_t)std::min(6, std::max(0, value));
-  else if (s == "msm.two_pass") c.msm.config().two_pass = c.msm_b.config().two_pass = (uint32_t)std::min(2, std::max(0, value));
-  else if (s == "side_prio") {   // device-wide, not per lane: wave priority 3 for every kernel but msm_accumulate (side_prio.cuh)
-    const uint32_t on = value ? 1u : 0u;
-    hipError_t e = msm_set_side_prio(on);
-    if (e == hipSuccess) e = ntt_set_side_prio(on);
-    if (e == hipSuccess) e = poly_set_side_prio(on);
-    if (e == hipSuccess) e = quotient_set_side_prio(on);
-    if (e == hipSuccess) e = gates_set_side_prio(on);
-    if (e == hipSuccess) e = numerator_set_side_prio(on);
-    if (e == hipSuccess) e = witness_set_side_prio(on);
-    if (e == hipSuccess) e = abi_set_side_prio(on);
-    if (e != hipSuccess) return hip_fail("side_prio", e);
-  }
-  else if (s == "msm.fused_frontend") c.msm.config().fused_frontend = c.msm_b.config().fused_frontend = (uint32_t)std::min(2, std::max(0, value));
-  else if (s == "msm.acc_trace") c.msm.config().acc_trace = c.msm_b.config().acc_trace = value ? 1u : 0u;
-  else if (s == "msm.acc_chain") c.msm.config().acc_chain = c.msm_b.config().acc_chain = value ? 1u : 0u;
-  else if (s == "msm.red_lean") c.msm.config().red_lean = c.msm_b.config().red_lean = (uint32_t)std::max(0, std::min(2, value));
-  else if (s == "msm.acc_waves_fixed") c.msm.config().acc_waves_fixed = c.msm_b.config().acc_waves_fixed = (uint32_t)std::max(0, std::min(8, value));
-  else if (s == "msm.acc_waves") c.msm.config().acc_waves = c.msm_b.config().acc_waves = (uint32_t)std::max(0, std::min(8, value));
-  else if (s == "msm.acc_threads") c.msm.config().acc_threads = c.msm_b.config().acc_threads = (value == 64 || value == 128 || value == 256) ? (uint32_t)value : 0u;
-  else if (s == "msm.merge_quad_tasks") c.msm.config().merge_quad_tasks = c.msm_b.config().merge_quad_tasks = (uint32_t)std::max(0, value);
-  else if (s == "msm.red2d_max_sets") c.msm.config().red2d_max_sets = c.msm_b.config().red2d_max_sets = (uint32_t)std::min(32, std::max(0, value));
-  else if (s == "msm.red2d_fold") c.msm.config().red2d_fold = c.msm_b.config().red2d_fold = (uint32_t)std::min(256, std::max(1, value));
-  else if (s == "msm.red2d_prefold") c.msm.config().red2d_prefold = c.msm_b.config().red2d_prefold = value ? 1u : 0u;
-  else if (s == "msm.prefold_quad_buckets") c.msm.config().prefold_quad_buckets = c.msm_b.config().prefold_quad_buckets = (uint32_t)std::max(0, value);
-  else if (s == "msm.red2d") c.msm.config().red2d = c.msm_b.config().red2d = (uint32_t)std::min(2, std::max(0, value));
-  else if (s == "msm.quad") c.msm.config().quad = c.msm_b.config().quad = (uint32_t)std::min(2, std::max(0, value));
-  else if (s == "msm.log_red_chunk") c.msm.config().log_red_chunk = c.msm_b.config().log_red_chunk = (uint32_t)std::min(8, value);
-  else if (s == "ntt.tile_log") c.ntt.config().tile_log = (uint32_t)std::max(6, std::min(12, value));
-  else if (s == "ntt.threads") c.ntt.config().threads = (uint32_t)std::max(64, std::min(1024, value));
-  else if (s == "ntt.big_tile_log") c.ntt.config().big_tile_log = value ? (uint32_t)std::max(6, std::min(12, value)) : 0u;   // 0: one shape for all
-  else if (s == "ntt.big_threads") c.ntt.config().big_threads = (uint32_t)std::max(64, std::min(1024, value));
-  else if (s == "ntt.batch_min") c.ntt.config().batch_min = (uint32_t)std::max(1, value);
-  else if (s == "ntt.big_log") c.ntt.config().big_log = (uint32_t)std::max(1, value);
-  else if (s == "ntt.radix4") c.ntt.config().radix4 = value == 1 ? 2u : value == 2 ? 0u : 1u;   // 0: by size (default), 1: always, 2: never
-  else if (s == "ntt.max_single_log") { c.ntt.config().max_single_log = (uint32_t)std::max(1, std::min(12, value)); c.ntt.clear(); }
-  else if (s == "ntt.max_multi_log") { c.ntt.config().max_multi_log = (uint32_t)std::max(4, std::min(12, value)); c.ntt.clear(); }
-  else return fail(SG_ERR_INVALID, "sg_set_param: unknown parameter");
-  return SG_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -597,7 +680,6 @@ void sg_shutdown(void) {
         if (t.table) (void)hipFree(t.table);
     }
     g_sh.srs.clear();
-    g_sh.params.clear();
     g_sh.device = -1;
     retired_device_memory_collect();
     summa::prover::release_orphans();   // what the prover sessions of ended threads left behind
@@ -722,8 +804,6 @@ int sg_msm_g1_dev(const void* d_scalars, const void* d_bases, size_t n, void* st
 // -- chunk i + 1 crosses the link while chunk i's accumulation runs.  K: "msm.host_chunks" (0 = by size: 2 from 2^18 pairs; more
 // chunks lose: every job brings its own latency chains, and small kernels beside an accumulation run slowly).
 static constexpr size_t MSM_HOST_SPLIT_MIN = (size_t)1 << 18;
-static std::atomic<int> g_host_chunks{0};
-static std::atomic<int> g_msm_tiny_max{(int)MSM_TINY_MAX};   // "msm.tiny_max": host-pointer MSMs of at most this many points run as one launch
 static int msm_host_chunked(const uint8_t* scalars, const uint8_t* bases_host, const g1_affine_mem* d_bases_resident, size_t n,
                             uint8_t out_affine[64]) {
   Context& c = *g_ctx;
@@ -732,7 +812,7 @@ static int msm_host_chunked(const uint8_t* scalars, const uint8_t* bases_host, c
   if (e != hipSuccess) return hip_fail("staging buffer", e);
   const fp_words* d_s = reinterpret_cast<const fp_words*>(c.stage_a.p);
   const g1_affine_mem* d_b = bases_host ? reinterpret_cast<const g1_affine_mem*>(c.stage_b.p) : d_bases_resident;
-  uint32_t K = (uint32_t)g_host_chunks.load();
+  uint32_t K = (uint32_t)g_sh.param[kRowHostChunks].load();
   if (K == 0) K = n < MSM_HOST_SPLIT_MIN ? 1u : 2u;   // measured at 2^20 (profiles/r04_sweeps/host_chunks.txt): 2 is the best for both entry points
   K = std::min<uint32_t>(K, 8u);
   if (n < 2 * (size_t)K) K = 1;
@@ -827,7 +907,7 @@ static int msm_host_chunked(const uint8_t* scalars, const uint8_t* bases_host, c
 int sg_msm_g1(const uint8_t* scalars, const uint8_t* bases, size_t n, uint8_t out_affine[64]) {
   if (!out_affine || (n && (!scalars || !bases))) return fail(SG_ERR_INVALID, "sg_msm_g1: null argument");
   LOCKED_CTX();
-  if (n && n <= (size_t)g_msm_tiny_max.load()) {   // a handful of points (the verifier's 37): one launch, no staging (MsmEngine::run_tiny)
+  if (n && n <= (size_t)g_sh.param[kRowTinyMax].load()) {   // a handful of points (the verifier's 37): one launch, no staging (MsmEngine::run_tiny)
     const hipError_t e = g_ctx->msm.run_tiny(scalars, bases, n, g_ctx->stream, out_affine);
     if (e != hipSuccess) return hip_fail("msm (one launch)", e);
     return SG_OK;
@@ -1196,12 +1276,8 @@ struct Combiner {
   int runners = 0;                       // fused jobs running now
   int busy = 0;                          // requests inside those jobs
   int members = 0;                       // threads between sg_commit_combine_begin and _end
-  std::atomic<int> wait_us{300};         // how long a runner waits for requests to arrive (sg_set_param "commit.combine_wait_us")
-  std::atomic<int> target{4};            // ... or until this many are pending ("commit.combine_target")
-  std::atomic<int> max_runners{1};       // fused jobs that may run side by side, each on a lane of its own ("commit.combine_runners")
   std::atomic<uint64_t> jobs{0}, requests{0};   // statistics: fused jobs run, requests served
   std::atomic<uint64_t> isolated{0};     // members re-run alone after their fused job failed as a whole
-  std::atomic<int> fail_next{0};         // test hook ("debug.fail_next_fused_job"): the next fused job reports SG_ERR_NOMEM unrun
 };
 Combiner g_comb;
 thread_local bool t_combine = false;
@@ -1245,7 +1321,7 @@ static void combiner_run_unguarded(const std::vector<CommitReq*>& batch) {
         if (e != hipSuccess) { rc = hip_fail("commit combiner: stream wait", e); break; }
       }
     }
-    if (rc == SG_OK && batch.size() > 1 && g_comb.fail_next.exchange(0)) rc = fail(SG_ERR_NOMEM, "commit combiner: injected failure of a fused job");
+    if (rc == SG_OK && batch.size() > 1 && g_sh.param[kRowFailNextFusedJob].exchange(0)) rc = fail(SG_ERR_NOMEM, "commit combiner: injected failure of a fused job");
     else if (rc == SG_OK) rc = commit_batch_mixed_core(batch[0]->srs, basis.data(), scalars.data(), total, batch[0]->n, g_ctx->stream, out.data());
   }
   size_t at = 0;
@@ -1287,7 +1363,7 @@ static int commit_combined(uint64_t srs_handle, const int* basis, const void* co
   g_comb.cv.notify_all();                         // a runner waiting for stragglers counts again
   while (!req.done) {
     const bool mine_pending = std::find(g_comb.pending.begin(), g_comb.pending.end(), &req) != g_comb.pending.end();
-    if (!mine_pending || g_comb.runners >= g_comb.max_runners.load()) {   // my request is inside a running job, or no runner slot is free
+    if (!mine_pending || g_comb.runners >= g_sh.param[kRowCombineRunners].load()) {   // my request is inside a running job, or no runner slot is free
       g_comb.cv.wait(lk);
       continue;
     }
@@ -1296,11 +1372,11 @@ static int commit_combined(uint64_t srs_handle, const int* basis, const void* co
     // only around its commitments, so at the tail of a batch the few proofs left would otherwise sit out the full wait
     // (5 ms in batch.prove_batch) at every one of their five jobs for members that are busy elsewhere
     const int may_come = std::max(1, g_comb.members - g_comb.busy - (int)g_comb.pending.size());
-    const int wait_us = std::min(g_comb.wait_us.load(), 400 * may_come);
+    const int wait_us = std::min(g_sh.param[kRowCombineWaitUs].load(), 400 * may_come);
     const auto deadline = std::chrono::steady_clock::now() + std::chrono::microseconds(wait_us);
     // wait for company: until `target` requests are pending, or every declared thread that is not inside a running job
     // has arrived, or the deadline
-    while ((int)g_comb.pending.size() < std::min(g_comb.target.load(), g_comb.members - g_comb.busy))
+    while ((int)g_comb.pending.size() < std::min(g_sh.param[kRowCombineTarget].load(), g_comb.members - g_comb.busy))
       if (g_comb.cv.wait_until(lk, deadline) == std::cv_status::timeout) break;
     // everything pending with the first request's SRS and length, up to MAX_FUSED polynomials
     if (g_comb.pending.empty()) {   // another runner took everything meanwhile (this thread's request included)
@@ -1399,13 +1475,13 @@ static int commit_batch_mixed_core(uint64_t srs_handle, const int* basis, const 
   // 1.07 -> 1.00 ms) where dense jobs lose by them (profiles/r04_sweeps/task_length_by_phase.txt).  A hint, never semantics.
   struct SegRestore {
     Context& c;
-    uint32_t a, b;
-    ~SegRestore() { c.msm.config().log_seg = a; c.msm_b.config().log_seg = b; }
-  } seg_restore{*g_ctx, g_ctx->msm.config().log_seg, g_ctx->msm_b.config().log_seg};
+    uint32_t seg;
+    ~SegRestore() { msm_set(c, &MsmConfig::log_seg, (int)seg); }
+  } seg_restore{*g_ctx, g_ctx->msm.config().log_seg};
   // (only for jobs small enough for the 2-D reduction, which adds up to eight partial sums per bucket itself: a fused job of many
   // proofs' columns goes through merge rounds, and shorter tasks would add one)
   if (all_sparse && fixed && count <= 5 && g_ctx->msm.config().log_seg == 0 && n >= ((size_t)1 << 14))
-    g_ctx->msm.config().log_seg = g_ctx->msm_b.config().log_seg = 3;
+    msm_set(*g_ctx, &MsmConfig::log_seg, 3);
   return msm_batch_locked(d_scalars, bases.data(), fixed ? &s.tab[0] : nullptr, ns.data(), count, stream, out_affine, flags.data());
 }
 int sg_commit(uint64_t srs_handle, int basis, const uint8_t* scalars, size_t n, uint8_t out_affine[64]) {
@@ -1736,8 +1812,6 @@ static int coset_tables_for(uint32_t k, uint32_t ext_k, uint32_t nc, const Conte
   *out = &it->second;
   return SG_OK;
 }
-// debug / A-B: 1 = the coset shift as a pass of its own before the transforms (rounds 3-4), 0 = folded into the first NTT pass
-static std::atomic<int> g_coset_scale_pass{0};
 static bool coset_shape_ok(uint32_t k, uint32_t ext_k, uint32_t nc) {
   return k >= 1 && ext_k > k && ext_k <= 28 && nc >= 1 && nc <= MAX_COSETS && nc <= (1u << (ext_k - k));
 }
@@ -1777,7 +1851,7 @@ int sg_coeff_to_cosets_batch_dev(const void* const* d_coeffs, void* const* d_out
   hipStream_t s = pick_stream(stream);
   TRY(sync_own_stream_into(s));
   const size_t n = (size_t)1 << k;
-  if (k <= 18 && !g_coset_scale_pass.load()) {
+  if (k <= 18 && !g_sh.param[kRowCosetScalePass].load()) {
     // the coset shift c_b^i rides on the load of the first NTT pass (a table of 2^261-domain words per coset, indexed like the
     // input): no pass over HBM of its own, and every block of every column is a vector of ONE batched launch per pass
     const DomainConsts* dk;
@@ -2819,7 +2893,6 @@ int sg_quotient_gates_cosets_dev(void* d_values, const sg_graph* graph, const vo
 // halo2's evaluate_h in one call: values <- gates, then the permutation argument, then the lookup argument (input expression
 // evaluated on the way).  One fused kernel when the two programs are known ahead of time (csrc/numerator.hip), otherwise the
 // separate kernels one after the other -- the same words either way.
-static std::atomic<int> g_numerator_fused{1};   // "quotient.fused_numerator": 0 forces the separate kernels (A-B, tests)
 int sg_quotient_numerator_cosets_dev(void* d_values, const sg_graph* gates, const sg_graph* lookup_input, const void* const* d_fixed,
                                      uint32_t n_fixed, const void* const* d_advice, uint32_t n_advice, const void* const* d_instance,
                                      uint32_t n_instance, const uint8_t* challenges, uint32_t n_challenges, const void* const* d_z,
@@ -2850,7 +2923,7 @@ int sg_quotient_numerator_cosets_dev(void* d_values, const sg_graph* gates, cons
   for (uint32_t i = 0; i < ncols; i++)
     if (!d_perm_cols[i] || !d_sigma[i]) return fail(SG_ERR_INVALID, "sg_quotient_numerator_cosets: null permutation column");
   bool fused = false;
-  if (g_numerator_fused.load() && n_fixed + n_advice + n_instance <= NUM_MAX_COLS) {
+  if (g_sh.param[kRowFusedNumerator].load() && n_fixed + n_advice + n_instance <= NUM_MAX_COLS) {
     LOCKED_CTX();
     if (g_ctx->gate_cache.size() >= 62) g_ctx->gate_cache.clear();   // neither look-up below may evict the other's program
     GateProgram *pg = nullptr, *pi = nullptr;
@@ -3069,91 +3142,38 @@ int sg_mst_inclusion_witness_dev(const void* d_program, uint32_t n_items, uint32
 int sg_set_param(const char* name, int value) {
   if (!name || value < 0) return fail(SG_ERR_INVALID, "sg_set_param: bad argument");
   if (g_depth > 0) return fail(SG_ERR_INVALID, "sg_set_param: not from inside a call");
-  const std::string s(name);
-  if (s == "commit.combine_wait_us") {   // how long the combiner's runner waits for the other declared threads
-    g_comb.wait_us.store(std::min(value, 100000));
-    return SG_OK;
-  }
-  if (s == "commit.combine_target") {
-    g_comb.target.store(std::max(1, std::min(value, 32)));
-    return SG_OK;
-  }
-  if (s == "msm.host_chunks") {   // chunks of the host-pointer MSM entry points (0 = by size)
-    g_host_chunks.store(std::min(value, 8));
-    return SG_OK;
-  }
-  if (s == "msm.tiny_max") {   // sg_msm_g1 of at most this many points is ONE launch (0: always the engine's pipeline; at most 64)
-    g_msm_tiny_max.store(std::min(value, (int)MSM_TINY_MAX));
-    return SG_OK;
-  }
-  if (s == "host.wait_sleep_us") {   // how host threads wait for the device (csrc/host_wait.h): 0 = the runtime's wait, > 0 = poll and sleep
-    host_wait_sleep_us().store(std::min(value, 1000));
-    return SG_OK;
-  }
-  if (s == "debug.fail_next_fused_job") {
-    g_comb.fail_next.store(value ? 1 : 0);
-    return SG_OK;
-  }
-  if (s == "ntt.coset_scale_pass") {   // A-B: the coset shift of coeff_to_cosets as its own pass (1) or inside the first NTT pass (0, default)
-    g_coset_scale_pass.store(value ? 1 : 0);
-    return SG_OK;
-  }
-  if (s == "quotient.fused_numerator") {   // 1 (default): sg_quotient_numerator_cosets_dev may run its one-pass kernel; 0: always the separate kernels
-    g_numerator_fused.store(value ? 1 : 0);
-    return SG_OK;
-  }
-  if (s == "msm.acc_log") {   // profiling: record every msm_accumulate launch in issue order (sg_msm_launch_log); setting 1 clears the log
-    msm_acc_log_enable(value != 0);
-    return SG_OK;
-  }
-  if (s == "commit.combine_runners") {
-    g_comb.max_runners.store(std::max(1, std::min(value, 4)));
-    return SG_OK;
-  }
-  if (s == "lanes") {   // how many concurrent calls get a context of their own (1 .. 8); further callers wait for a lane
-    if (value < 1 || value > kLanes) return fail(SG_ERR_INVALID, "sg_set_param: lanes in [1, 8]");
-    g_lane_count.store(value);
-    return SG_OK;
-  }
+  const size_t i = param_index(name);
+  if (i == kNumParams) return fail(SG_ERR_INVALID, "sg_set_param: unknown parameter");
+  const ParamRow& row = kParams[i];
+  const int v = row.clamp(value);
+  if (v < 0) return fail(SG_ERR_INVALID, "sg_set_param: value out of range (lanes: 1..8)");
+  int device;
   {
-    LOCKED_CTX();   // makes sure a context exists to validate the name against
-    int rc = apply_param(*g_ctx, s, value);
-    if (rc != SG_OK) return rc;
     std::lock_guard<std::mutex> lk(g_sh.mu);
-    g_sh.params.emplace_back(s, value);   // lanes created later replay it
+    g_sh.param[i].store(v);
+    device = g_sh.device;
+    if (row.scope == Scope::process && row.to_process) return row.to_process(v);
   }
-  // the lanes that exist already, one at a time and with none held (two threads setting parameters at once cannot
-  // wait for each other's lane): each when it is idle
-  for (auto& l : g_lanes) {
-    std::lock_guard<std::mutex> lk(l.mu);
-    if (l.ctx) (void)apply_param(*l.ctx, s, value);
+  if (row.scope == Scope::device && device >= 0) {   // with no device bound yet, the first context applies it
+    CHECK_HIP(hipSetDevice(device), "sg_set_param");
+    return row.to_process(v);
+  }
+  if (row.scope == Scope::lane) {
+    // the lanes that exist already, one at a time and with none held (two threads setting parameters at once cannot
+    // wait for each other's lane): each when it is idle, with the value in effect then
+    for (auto& l : g_lanes) {
+      std::lock_guard<std::mutex> lk(l.mu);
+      if (l.ctx) row.to_lane(*l.ctx, g_sh.param[i].load());
+    }
   }
   return SG_OK;
 }
 
 int sg_get_param(const char* name, int* value) {
   if (!name || !value) return fail(SG_ERR_INVALID, "sg_get_param: bad argument");
-  const std::string s(name);
-  if (s == "commit.combine_wait_us") *value = g_comb.wait_us.load();
-  else if (s == "commit.combine_target") *value = g_comb.target.load();
-  else if (s == "commit.combine_runners") *value = g_comb.max_runners.load();
-  else if (s == "msm.host_chunks") *value = g_host_chunks.load();
-  else if (s == "msm.tiny_max") *value = g_msm_tiny_max.load();
-  else if (s == "host.wait_sleep_us") *value = host_wait_sleep_us().load();
-  else if (s == "lanes") *value = g_lane_count.load();
-  else {
-    // per-lane parameters: the value most recently set through sg_set_param (0 = never set: the built-in default applies)
-    std::lock_guard<std::mutex> lk(g_sh.mu);
-    *value = 0;
-    bool known = false;
-    for (const auto& kv : g_sh.params)
-      if (kv.first == s) {
-        *value = kv.second;
-        known = true;
-      }
-    if (!known && s.rfind("msm.", 0) != 0 && s.rfind("ntt.", 0) != 0 && s != "side_prio")
-      return fail(SG_ERR_INVALID, "sg_get_param: unknown parameter");
-  }
+  const size_t i = param_index(name);
+  if (i == kNumParams) return fail(SG_ERR_INVALID, "sg_get_param: unknown parameter");
+  *value = g_sh.param[i].load();
   return SG_OK;
 }
 

@@ -6,6 +6,7 @@ the library is missing -- there is no fallback implementation.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -78,6 +79,21 @@ def get_param(name: str) -> int:
     out = C.c_int(0)
     check(lib().sg_get_param(name.encode(), C.byref(out)))
     return out.value
+
+
+@contextlib.contextmanager
+def params(values: dict):
+    """Hold library parameters at `values` for the length of a `with` block; what sg_get_param reported before is put back on
+    the way out, whatever happens inside (include/summa_gpu.h: setting a parameter to what it reported changes nothing)."""
+    saved = {}
+    try:
+        for name, value in values.items():
+            saved[name] = get_param(name)
+            set_param(name, value)
+        yield
+    finally:
+        for name, value in saved.items():
+            set_param(name, value)
 
 
 def msm_launch_log():

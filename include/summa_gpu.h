@@ -536,43 +536,59 @@ int sg_msm_g1_dev_timed(const void* d_scalars, const void* d_bases, size_t n, vo
                         sg_msm_timings* timings);
 int sg_commit_dev_timed(uint64_t srs_handle, int basis, const void* d_scalars, size_t n, void* stream,
                         uint8_t out_affine[64], sg_msm_timings* timings);
-/* name: "lanes" (1..8, default 4: concurrent calls that get a context of their own, see the conventions at the top),
- * "commit.combine_wait_us" (default 300), "commit.combine_target" (default 4: a runner stops waiting once this many requests
- *   are pending), "commit.combine_runners" (default 1: fused jobs that may run side by side, each on a lane of its own) -- see
- *   sg_commit_combine_begin; process-wide, they stay as set until set again,
- * "host.wait_sleep_us" (0 | 1..1000: see sg_stream_wait; process-wide, takes effect at once),
- * "msm.host_chunks" (0 = by size | 1..8: the host-pointer entry points sg_msm_g1 / sg_commit cut inputs of 2^18 pairs and more into
- *   that many chunks, which run as jobs on two engines while the next chunk is uploaded; default 2),
- * "msm.tiny_max" (0..64, default 64: sg_msm_g1 of at most this many points -- the verifier's 37 -- is ONE launch that reads its
- *   inputs from mapped host memory instead of eleven launches and three staging copies; 0: always the engine's pipeline),
- * "msm.log_fuse_entries" (16..30; 0 = the defaults: a fused job holds at most 2^x (window, scalar) entries -- 27 for fixed-base
- *   jobs (sg_commit_batch*, the commit combiner: 64 polynomials of 2^17 rows over a 16-window table), 25 for generic ones
- *   (sg_msm_g1_batch*); larger batches are cut into several jobs; a value set here applies to both kinds),
- * "msm.acc_trace" (0 | 1: debug -- every wave of msm_accumulate records when it starts and leaves; the job's host tail prints the
- *   percentiles to stderr: tools/acc_trace.sh, profiles/r04_sweeps/accumulate_tail.txt),
- * "ntt.radix4" (0 = by size, default | 1 always | 2 never: an NTT pass runs two butterfly stages per sweep over its LDS tile --
- *   four elements per thread, half the barriers; same words; by size = transforms of 2^20 points and more and batched launches of
- *   four vectors and more, where it is 3-6 % faster: profiles/r05_sweeps/ntt_radix4.txt),
- * "ntt.coset_scale_pass" (0 | 1: A-B aid -- sg_coeff_to_cosets_batch_dev multiplies by the coset shifts inside the first NTT pass
- *   (0, default) or in a pass of its own before the transforms (1, rounds 3-4); same results), "msm.acc_log" (see sg_msm_launch_log),
- * "debug.fail_next_fused_job" (test hook: the next FUSED job of the commit combiner reports SG_ERR_NOMEM without running, so that
- *   its members fall back to jobs of their own),
- * "msm.window_bits", "msm.log_seg", "msm.log_red_chunk", "msm.quad", "ntt.tile_log", "ntt.threads",
- * "ntt.max_single_log", "ntt.max_multi_log";
- * how calls in flight share the device (DESIGN.md sections 4.1 and 4.4, docs/history.md section 4.11; the defaults are what the measurements chose):
- *   "side_prio" (1 | 0): every kernel but the MSM's accumulation runs at wave priority 3, so that a kernel of another call that
- *     lands beside an accumulation is not starved of issue slots by it (device-wide, not per lane);
- *   "msm.acc_waves" / "msm.acc_waves_fixed" (0 = default, 2, 3, 8): waves per SIMD of the persistent accumulation launch of
- *     generic / fixed-base jobs -- default: 3 (a full register file) for a generic job that has the device to itself, 2 (a
- *     third of the file left to other kernels) when other jobs are in flight and for fixed-base jobs; 8: one ticket per wave;
- *   "msm.acc_chain" (1 | 0): accumulations of different calls run one after the other;
- *   "msm.red_lean" (0 | 1 | 2): the bucket reduction's 168-register twin never / when other jobs are in flight / always;
- *   "msm.fused_frontend" (0 | 1 | 2): the scans and the task-length histogram of a job inside its sort's own kernels (five launches
- *     fewer) never / when the job has the device to itself (default) / always. */
+/* Runtime parameters.  sg_set_param(name, value >= 0) brings the value into the parameter's range (only "lanes" rejects one
+ * outside it) and makes it take effect: a process-wide one at once, a per-lane one in every context when it is idle and in every
+ * context made later.  It needs no bound device and creates no context.  A value stays as set until it is set again, across
+ * sg_shutdown too.  sg_get_param returns the value in effect: the one last set, as brought into range, or the default.  Both fail
+ * for every name not listed here.  Setting a parameter to what sg_get_param returned changes nothing -- except "msm.acc_log",
+ * where setting 1 clears the launch log.  One line per parameter: name, range, default, meaning.
+ * Process-wide:
+ *   "lanes"                      1..8, default 4: concurrent calls that get a context of their own (see the conventions at the top)
+ *   "commit.combine_wait_us"     0..100000, default 300: how long a runner of the commit combiner waits for the other declared threads (sg_commit_combine_begin)
+ *   "commit.combine_target"      1..32, default 4: ... or until this many requests are pending
+ *   "commit.combine_runners"     1..4, default 1: fused jobs that may run side by side, each on a lane of its own
+ *   "host.wait_sleep_us"         0..1000, default 0: how a thread waits for the device -- 0: the runtime's wait, else poll and sleep this long (sg_stream_wait)
+ *   "msm.host_chunks"            0..8, default 0: sg_msm_g1 / sg_commit cut inputs into this many chunks, run as jobs on two engines while the next is uploaded; 0: by size (2 from 2^18 pairs)
+ *   "msm.tiny_max"               0..64, default 64: sg_msm_g1 of at most this many points (the verifier's 37) is ONE launch that reads mapped host memory; 0: always the pipeline
+ *   "msm.acc_log"                0..1, default 0: record every msm_accumulate launch (sg_msm_launch_log); setting 1 clears the log
+ *   "ntt.coset_scale_pass"       0..1, default 0: A-B aid -- sg_coeff_to_cosets_batch_dev applies the coset shifts inside the first NTT pass (0) or in a pass of its own (1, rounds 3-4); same results
+ *   "quotient.fused_numerator"   0..1, default 1: sg_quotient_numerator_cosets_dev may run its one-pass kernel; 0: always the separate kernels
+ *   "debug.fail_next_fused_job"  0..1, default 0: test hook -- the next FUSED job of the commit combiner reports SG_ERR_NOMEM unrun, so that its members run alone; reads 0 once used
+ * Device-wide (how calls in flight share the device: DESIGN.md sections 4.1 and 4.4, docs/history.md section 4.11):
+ *   "side_prio"                  0..1, default 1: every kernel but the MSM's accumulation runs at wave priority 3, so that one beside an accumulation is not starved of issue slots
+ * Per lane, MSM (0 where it means "choose": chosen per job):
+ *   "msm.window_bits"            0..2147483647, default 0: window width; 0: from n (log2 n - 2 single / - 4 fused, within 4..16)
+ *   "msm.log_seg"                0..12, default 0: 2^x entries per accumulation task; 0: from n
+ *   "msm.log_fuse_entries"       0 | 16..30, default 0: a fused job holds at most 2^x (window, scalar) entries, larger batches are cut; 0: 27 for fixed-base jobs (sg_commit_batch*, the combiner), 25 for generic ones (sg_msm_g1_batch*); else both
+ *   "msm.red_threads"            64 | 128 | 256 (others round up), default 256: workgroup size of the level-0 bucket reduction
+ *   "msm.acc_threads"            0 | 64 | 128 | 256 (others: 0), default 0: workgroup size of msm_accumulate; 0: 128
+ *   "msm.log_scatter_rounds"     0..6, default 0: the counting sort's scatter runs in 2^x bucket-range rounds
+ *   "msm.two_pass"               0..2, default 1: two-pass (coarse bin, in-LDS fine) sort -- never / from 2^19 entries / always
+ *   "msm.fused_frontend"         0..2, default 1: the scans and task histogram inside the sort's own kernels (five launches fewer) -- never / when the job has the device to itself / always
+ *   "msm.acc_trace"              0..1, default 0: debug -- msm_accumulate's waves record when they start and leave; the host tail prints the percentiles to stderr
+ *   "msm.acc_chain"              0..1, default 1: accumulations of different calls run one after the other
+ *   "msm.red_lean"               0..2, default 1: the bucket reduction's 168-register twin -- never / when other jobs are in flight / always
+ *   "msm.acc_waves_fixed"        0..8, default 0: waves per SIMD of the persistent accumulation of fixed-base jobs; 0: 2; 8: one ticket per wave
+ *   "msm.acc_waves"              0..8, default 0: ... of generic jobs; 0: 3 with the device to itself, 2 when other jobs are in flight
+ *   "msm.merge_quad_tasks"       0..2147483647, default 2147483647: merge rounds with more tasks than this use one lane per addition even when "msm.quad" holds
+ *   "msm.red2d_max_sets"         0..32, default 6: the 2-D reduction's host-weights variant up to this many bucket sets
+ *   "msm.red2d_fold"             1..256, default 8: the 2-D reduction's line sums add up to this many partial sums per bucket themselves
+ *   "msm.red2d_prefold"          0..1, default 1: a pass adds every bucket's partial sums before the 2-D reduction (0: its line sums add them, twice)
+ *   "msm.prefold_quad_buckets"   0..2147483647, default 32768: that pass gives each bucket a quad up to this many buckets in the job, one lane beyond
+ *   "msm.red2d"                  0..2, default 1: 2-D (row / column / bit) bucket reduction -- never / jobs of at most 4 bucket sets / always
+ *   "msm.quad"                   0..2, default 1: quad-cooperative point additions in merge and reduction -- never / auto / always
+ *   "msm.log_red_chunk"          0..8, default 0: 2^x buckets per thread in the bucket reduction; 0: auto
+ * Per lane, NTT:
+ *   "ntt.tile_log"               6..12, default 9: log2 of the elements of a workgroup's tile
+ *   "ntt.threads"                64..1024, default 256: threads of that workgroup
+ *   "ntt.big_tile_log"           0 | 6..12, default 10: the tile of the throughput shape (batches of ntt.batch_min vectors and more, transforms of 2^ntt.big_log points and more); 0: one shape for all
+ *   "ntt.big_threads"            64..1024, default 512: threads of its workgroup
+ *   "ntt.batch_min"              1..2147483647, default 4: batched launches of at least this many vectors take the throughput shape
+ *   "ntt.big_log"                1..2147483647, default 20: ... and so do transforms of at least 2^x points
+ *   "ntt.radix4"                 0..2, default 0: two butterfly stages per sweep over the LDS tile (same words) -- by size (the throughput shapes, 3-6 % faster there: profiles/r05_sweeps/ntt_radix4.txt) / always / never
+ *   "ntt.max_single_log"         1..12, default 11: largest transform done in one LDS-resident pass (setting it drops the lane's plans)
+ *   "ntt.max_multi_log"          4..12, default 9: largest per-pass DFT length of multi-pass plans (likewise) */
 int sg_set_param(const char* name, int value);
-/* Reads a parameter back (so that a caller that changes a process-wide one for the length of a job can restore what it found):
- * the process-wide ones ("lanes", "commit.*", "host.wait_sleep_us", "msm.host_chunks", "msm.tiny_max") return their live value, the per-lane
- * ones ("msm.*", "ntt.*", "side_prio") the value most recently set through sg_set_param, 0 when none was (built-in default). */
 int sg_get_param(const char* name, int* value);
 /* Profiling aid.  With parameter "msm.acc_log" = 1 (setting it clears the log) every msm_accumulate launch of the process is
  * recorded in the order in which the chained launches run on the device, so the i-th msm_accumulate of a kernel trace ordered by
@@ -586,8 +602,10 @@ int sg_msm_launch_log(uint32_t* out_words, size_t cap_records, size_t* n_records
  *     sg_fr_flag_noncanonical_dev, sg_lookup_permute_small_async_dev, sg_grand_products_closing_dev, sg_fr_kate_division_rem_dev;
  *     sg_fr_kate_division_batch_dev no longer waits for the stream before it returns (it is asynchronous like its neighbours);
  *     nothing removed or resized
+ *   4: sg_get_param returns the value in effect of every parameter, its default until it is set (revision 3: 0 for a per-lane one
+ *     never set); sg_set_param and sg_get_param refuse the same names, and setting a per-lane parameter no longer binds a device
  * A binding built against revision r must refuse a library whose sg_abi_version() < r. */
-#define SG_ABI_VERSION 3
+#define SG_ABI_VERSION 4
 int sg_abi_version(void);
 /* Time `reps` back-to-back launches of the operation with HIP events on the library's
  * stream; returns average milliseconds per launch in *ms_out (used by bench.py for the

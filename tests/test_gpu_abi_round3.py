@@ -198,7 +198,6 @@ def test_calls_in_flight_are_bit_exact_under_every_sharing_setting():
     from circuits_halo2_amd import arithmetic as A, ffi
     from circuits_halo2_amd.utils import random_fr_canonical
     _gpu()
-    L = ffi.lib()
     n = 1 << 17
     scal = [A.fr_to_montgomery(torch.from_numpy(random_fr_canonical(900 + i, n)).cuda()) for i in range(3)]
     bases = A.g1_fixed_base_mul(A.fr_to_montgomery(torch.from_numpy(random_fr_canonical(77, n)).cuda()))
@@ -207,26 +206,20 @@ def test_calls_in_flight_are_bit_exact_under_every_sharing_setting():
     assert len(set(want)) == 3
     settings = [{"msm.acc_waves": 2, "msm.red_lean": 2}, {"msm.acc_waves": 8, "side_prio": 0, "msm.acc_chain": 0},
                 {"msm.acc_waves": 3, "msm.red_lean": 0, "side_prio": 1}, {}]
-    defaults = {"msm.acc_waves": 0, "msm.red_lean": 1, "side_prio": 1, "msm.acc_chain": 1}
-    try:
-        for setting in settings:
-            for name, value in {**defaults, **setting}.items():
-                ffi.check(L.sg_set_param(name.encode(), int(value)))
-            got = [[] for _ in range(3)]
+    for setting in settings:
+        got = [[] for _ in range(3)]
 
-            def run(i):
-                ffi.bind_thread()
-                for _ in range(6):
-                    got[i].append(bytes(sg.best_multiexp(scal[i], bases)))
+        def run(i):
+            ffi.bind_thread()
+            for _ in range(6):
+                got[i].append(bytes(sg.best_multiexp(scal[i], bases)))
+        with ffi.params(setting):
             threads = [threading.Thread(target=run, args=(i,)) for i in range(3)]
             for t in threads:
                 t.start()
             for t in threads:
                 t.join()
-            assert all(g == [want[i]] * 6 for i, g in enumerate(got)), setting
-    finally:
-        for name, value in defaults.items():
-            ffi.check(L.sg_set_param(name.encode(), int(value)))
+        assert all(g == [want[i]] * 6 for i, g in enumerate(got)), setting
 
 
 def test_low_polynomial_alone_is_a_column():

@@ -6,7 +6,6 @@ production, under skewed scalars, with jobs in flight beside them and back to ba
 Every expected point comes from outside the library's MSM: the bases are s_i * G (g1_fixed_base_mul), so a generic MSM
 must give <k, s> * G (oracle dot product and scalar multiplication); a commitment against ParamsKZG.setup(k, tau) must give
 a(tau) * G.  Nothing compares one mode of the library with another."""
-import contextlib
 import threading
 
 import numpy as np
@@ -15,9 +14,6 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 N_POOL = (1 << 21) + 8
-# the library's documented defaults: sg_get_param reports 0 for a per-lane parameter never set, and for fused_frontend /
-# two_pass 0 means "never", so these are restored by value, not by reading them back
-DEFAULTS = {"msm.fused_frontend": 1, "msm.two_pass": 1, "msm.window_bits": 0, "msm.acc_log": 0, "msm.host_chunks": 0}
 MODES = (0, 1, 2)
 
 
@@ -28,32 +24,13 @@ def gpu():
     import circuits_halo2_amd as sg
     from circuits_halo2_amd import ffi
     ffi.check(sg.lib().sg_init(0))
-    _restore_defaults()
-    yield sg
-    _restore_defaults()
+    return sg
 
 
 @pytest.fixture(scope="module")
 def O():
     from oracle import oracle
     return oracle
-
-
-def _restore_defaults():
-    from circuits_halo2_amd import ffi
-    for name, value in DEFAULTS.items():
-        ffi.set_param(name, value)
-
-
-@contextlib.contextmanager
-def _params(values):
-    from circuits_halo2_amd import ffi
-    try:
-        for name, value in values.items():
-            ffi.set_param(name, value)
-        yield
-    finally:
-        _restore_defaults()
 
 
 def _dev(a):
@@ -234,12 +211,13 @@ def test_msm_front_ends_known_answer(gpu, O, pool, n, dist, extra, modes):
     the two-pass sort with separate scans and with the fused ones, at the headline's NBc = 4096 bins and past it, at lengths
     that are not powers of two, under every skew the sort has a branch for (oversized bins, empty bins, deep buckets,
     cancelling points) and at the edges of the signed-digit recoding"""
+    from circuits_halo2_amd import ffi
     from circuits_halo2_amd.arithmetic import best_multiexp
     seed = 1000 * len(dist) + n % 9973 + 17 * sum(extra.values())
     k, bases, want = case(O, pool, dist, n, seed, off=seed % 8)
     bad = []
     for mode in modes:
-        with _params({"msm.fused_frontend": mode, **extra}):
+        with ffi.params({"msm.fused_frontend": mode, **extra}):
             got = best_multiexp(k, bases)
         if not (got == want).all():
             bad.append(mode)
@@ -274,7 +252,7 @@ def test_three_threads_in_flight(gpu, O, pool, mode):
             errors.append(e)
             barrier.abort()
 
-    with _params({"msm.fused_frontend": mode, "msm.acc_log": 1}):
+    with ffi.params({"msm.fused_frontend": mode, "msm.acc_log": 1}):
         threads = [threading.Thread(target=run, args=(i,), daemon=True) for i in range(len(cases))]
         for t in threads:
             t.start()
@@ -298,7 +276,7 @@ def test_batch_in_flight_and_fused_groups(gpu, O, pool, mode):
     mixed = [case(O, pool, d, n, 400 + i, off=i) for i, (n, d) in enumerate(zip(sizes, dists))]
     members = ["uniform", "equal", "byte", "selector", "sparse", "tiled32", "uniform"]
     fused = [case(O, pool, d, 1 << 17, 500 + i, off=(1 << 17) * i) for i, d in enumerate(members)]
-    with _params({"msm.fused_frontend": mode, "msm.acc_log": 1}):
+    with ffi.params({"msm.fused_frontend": mode, "msm.acc_log": 1}):
         got = A.best_multiexp_batch([(k, b) for k, b, _ in mixed])
         log = ffi.msm_launch_log()
         ffi.set_param("msm.acc_log", 1)
@@ -320,13 +298,14 @@ def test_back_to_back_jobs_on_one_engine(gpu, O, pool):
     """jobs of different sizes and skews one after the other on one engine, switching front-end modes on the way (2 -> 0 ->
     2 -> 1): the fused front end's two replica sets alternate by job, each job clears the other set for the next one even
     when that one has a different bin count, and msm_hist_prefix's finished-workgroup counter must be back at zero"""
+    from circuits_halo2_amd import ffi
     from circuits_halo2_amd.arithmetic import best_multiexp
     seq = [(1 << 15, "uniform"), (1 << 20, "equal"), (1 << 17, "selector"), (1 << 20, "uniform"), (1 << 15, "byte")] * 2
     modes = [2, 2, 2, 0, 0, 2, 2, 2, 1, 1]
     cases = [case(O, pool, d, n, 600 + i, off=i % 8) for i, (n, d) in enumerate(seq)]
     bad = []
     for i, ((k, b, want), mode) in enumerate(zip(cases, modes)):
-        with _params({"msm.fused_frontend": mode}):
+        with ffi.params({"msm.fused_frontend": mode}):
             if not (best_multiexp(k, b) == want).all():
                 bad.append((i, seq[i], mode))
     # the same sequence once more with the default mode throughout: nothing stale from the switching above
@@ -393,9 +372,10 @@ def _fixed_round(kzg, counts=(1, 5, 8, 9)):
 def test_fixed_base_commitments_at_k17(gpu, kzg, mode):
     """commitments of 2^17 rows against a(tau) G, first over the resident bases (generic fused jobs: 640 bins per column)
     and then over the window tables (fixed-base jobs: 512 bins per column, 8 columns = FE_MAX_BINS, 9 past it)"""
+    from circuits_halo2_amd import ffi
     p = kzg["params"]
     p.free()                     # (a fresh upload: no window tables from an earlier test)
-    with _params({"msm.fused_frontend": mode}):
+    with ffi.params({"msm.fused_frontend": mode}):
         bad = [("generic",) + (b if isinstance(b, tuple) else (b,)) for b in _fixed_round(kzg)]
         p.precompute()
         bad += [("fixed",) + (b if isinstance(b, tuple) else (b,)) for b in _fixed_round(kzg)]
@@ -426,7 +406,7 @@ def test_fixed_base_beside_generic_msm(gpu, O, pool, kzg):
             barrier.abort()
 
     got_f = []
-    with _params({"msm.fused_frontend": 2, "msm.acc_log": 1}):
+    with ffi.params({"msm.fused_frontend": 2, "msm.acc_log": 1}):
         t = threading.Thread(target=generic, daemon=True)
         t.start()
         try:
@@ -455,7 +435,7 @@ def test_host_pointer_msm_in_chunks_fused(gpu, O, pool, chunks):
     for i, dist in enumerate(("uniform", "equal")):
         k, b, want = case(O, pool, dist, n, 1000 + 10 * chunks + i, off=i)
         hk, hb = k.cpu().numpy().copy(), b.cpu().numpy().copy()
-        with _params({"msm.fused_frontend": 2, "msm.host_chunks": chunks, "msm.acc_log": 1}):
+        with ffi.params({"msm.fused_frontend": 2, "msm.host_chunks": chunks, "msm.acc_log": 1}):
             ffi.check(L.sg_msm_g1(ffi.ptr(hk), ffi.ptr(hb), C.c_size_t(n), ffi.ptr(out)))
             log = ffi.msm_launch_log()
         assert (out == want).all(), (chunks, dist)
@@ -464,13 +444,14 @@ def test_host_pointer_msm_in_chunks_fused(gpu, O, pool, chunks):
 
 # ----------------------------------------------------------------------------- 3: nothing left behind
 def test_defaults_after_the_module(gpu, O):
-    """(last in the file) every test restored the documented defaults, and a fresh MSM of 2^16 still matches the oracle"""
+    """(last in the file) every parameter reads back its documented default (include/summa_gpu.h), and a fresh MSM of 2^16
+    still matches the oracle"""
+    from param_doc import documented_defaults
     from circuits_halo2_amd import ffi
     from circuits_halo2_amd.arithmetic import best_multiexp
-    for name, value in DEFAULTS.items():
-        if name not in ("msm.acc_log", "msm.host_chunks"):   # (write-only switches / global: not in the per-lane history)
-            assert ffi.get_param(name) == value, name
-    assert ffi.get_param("msm.host_chunks") == 0
+    defaults = documented_defaults()
+    assert len(defaults) >= 40 and {"msm.acc_log", "msm.host_chunks", "msm.fused_frontend", "msm.two_pass"} <= set(defaults)
+    assert {name: ffi.get_param(name) for name in defaults} == defaults
     n = 1 << 16
     sc = O.random_fr(0x16, n)
     bases = O.fixed_base_mul(O.random_fr(0x61, n), O.ncpu())

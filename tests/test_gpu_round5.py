@@ -58,15 +58,12 @@ def test_fused_numerator_matches_the_separate_kernels(gpu, nc, k):
     none = np.zeros(0, dtype=np.uint8)
 
     def run(fused):
-        ffi.set_param("quotient.fused_numerator", 1 if fused else 0)
-        try:
+        with ffi.params({"quotient.fused_numerator": 1 if fused else 0}):
             values = _rand_fr(4242, rows)         # garbage in
             A.quotient_numerator_cosets(values, gates, look, fixed, advice, inst, challenges, zs, perm_cols, sigmas, 4, l0, l_last, l_active,
                                         lz, pin, ptab, fixed[4], beta, gamma, theta, y, k, ext_k, d, 6)
             torch.cuda.synchronize()
             return values
-        finally:
-            ffi.set_param("quotient.fused_numerator", 1)
 
     got, want = run(True), run(False)
     assert (got == want).all()
@@ -121,13 +118,10 @@ def test_coset_shift_inside_the_first_ntt_pass(gpu, k, count):
     keep = [c.clone() for c in coeffs]
 
     def run(own_pass):
-        ffi.set_param("ntt.coset_scale_pass", own_pass)
-        try:
+        with ffi.params({"ntt.coset_scale_pass": own_pass}):
             out = dom.coeff_to_cosets_batch(coeffs)
             torch.cuda.synchronize()
             return out
-        finally:
-            ffi.set_param("ntt.coset_scale_pass", 0)
 
     folded, separate = run(0), run(1)
     assert len(folded) == count
@@ -169,13 +163,13 @@ def test_lincomb_sets_is_the_single_combinations(gpu):
         A.fr_lincomb_sets(too_many, n)
 
 
-def test_launch_log_get_param_and_abi_revision(gpu):
+def test_launch_log_get_param_and_abi_revision_4(gpu):
     """msm.acc_log: one record per msm_accumulate launch, in issue order, describing the job; sg_get_param returns what
     sg_set_param set; the library reports the ABI revision of the header it was built from"""
     import torch
     from circuits_halo2_amd import arithmetic as A, ffi
     L = ffi.lib()
-    assert L.sg_abi_version() == 3
+    assert L.sg_abi_version() == 4
     n = 1 << 12
     scal = _rand_fr(5, n)
     bases = A.g1_fixed_base_mul(_rand_fr(6, n))
@@ -338,11 +332,8 @@ def test_one_launch_msm_of_a_handful_of_points(gpu):
 
     def pipeline(sc, bs):
         assert ffi.get_param("msm.tiny_max") == 64
-        ffi.set_param("msm.tiny_max", 0)
-        try:
+        with ffi.params({"msm.tiny_max": 0}):
             return gpu.best_multiexp(sc, bs)
-        finally:
-            ffi.set_param("msm.tiny_max", 64)
 
     for n in (1, 2, 3, 7, 8, 9, 31, 37, 63, 64, 65):
         sc, bs = O.random_fr(500 + n, n), bases_all[:64 * n]
@@ -406,15 +397,14 @@ def test_fused_job_size_and_its_default(gpu):
     try:
         whole, want = jobs()
         assert whole == [count]
-        ffi.set_param("msm.log_fuse_entries", 18)      # 2^18 / (22 windows x 2^12 rows) = 2 polynomials per job
-        cut, got = jobs()
+        with ffi.params({"msm.log_fuse_entries": 18}):      # 2^18 / (22 windows x 2^12 rows) = 2 polynomials per job
+            cut, got = jobs()
         assert sum(cut) == count and max(cut) <= 3 and len(cut) >= 7
         assert all((a == b).all() for a, b in zip(got, want))
-        ffi.set_param("msm.log_fuse_entries", 0)
+        assert ffi.get_param("msm.log_fuse_entries") == 0
         again, got = jobs()
         assert again == [count] and all((a == b).all() for a, b in zip(got, want))
     finally:
-        ffi.set_param("msm.log_fuse_entries", 0)
         params.free()
 
 
@@ -431,16 +421,13 @@ def test_ntt_with_two_stages_per_sweep_writes_the_same_words(gpu, log_n):
     cols = [_rand_fr(4000 + 10 * log_n + i, n) for i in range(5 if log_n <= 17 else 1)]
 
     def run(mode):
-        ffi.set_param("ntt.radix4", mode)
-        try:
+        with ffi.params({"ntt.radix4": mode}):
             fwd = A.best_fft_batch([c.clone() for c in cols], dom.get_omega(), log_n)
             inv = A.best_fft_batch([c.clone() for c in cols], dom.get_omega_inv(), log_n, dom.ifft_divisor())
             one = dom.lagrange_to_coeff(cols[0].clone())
             cos = dom.coeff_to_cosets_batch(cols) if log_n <= 17 else []
             torch.cuda.synchronize()
             return fwd + inv + [one] + cos
-        finally:
-            ffi.set_param("ntt.radix4", 0)
 
     for a, b in zip(run(1), run(2)):
         assert (a == b).all() and a.any()

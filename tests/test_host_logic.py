@@ -356,12 +356,12 @@ def test_sp_key_create_refuses_programs_outside_the_constraint_system_shape():
         assert rc == -1 and "does not fit" in msg and needle in msg, (needle, rc, msg)
 
 
-def test_process_wide_parameters_read_back_and_a_batch_restores_what_it_found():
+def test_process_wide_parameters_read_back_at_abi_revision_4_and_a_batch_restores_what_it_found():
     """sg_get_param / sg_abi_version and batch._ParamScope need no device: the process-wide parameters (combiner, sleeping waits) are
     plain atomics of the library.  A batch's settings are put back to what the CALLER had set when the last batch of the process
     ends, not to built-in defaults (advisor, round 4)."""
     from circuits_halo2_amd import batch as B, ffi
-    assert ffi.lib().sg_abi_version() == 3
+    assert ffi.lib().sg_abi_version() == 4
     ffi.set_param("host.wait_sleep_us", 25)
     ffi.set_param("commit.combine_wait_us", 777)
     try:
@@ -382,3 +382,94 @@ def test_process_wide_parameters_read_back_and_a_batch_restores_what_it_found():
     import pytest
     with pytest.raises(ffi.SummaGpuError):
         ffi.get_param("no.such.parameter")
+
+
+PARAMS_CHILD = r'''
+import json, os, sys
+sys.path.insert(0, os.environ["REPO_ROOT"])
+from circuits_halo2_amd import batch as B, ffi
+doc = json.loads(os.environ["DOCUMENTED_DEFAULTS"])
+
+def refused(call):
+    try:
+        call()
+    except ffi.SummaGpuError:
+        return True
+    return False
+
+now = lambda: {name: ffi.get_param(name) for name in doc}
+# every documented default reads back, and setting what was read changes nothing
+assert now() == doc, {n: v for n, v in now().items() if v != doc[n]}
+for name, value in doc.items():
+    ffi.set_param(name, ffi.get_param(name))
+assert now() == doc
+# out-of-range values come back clamped (only "lanes" refuses them), negative ones are refused
+for name, value, want in json.loads(os.environ["CLAMPS"]):
+    ffi.set_param(name, value)
+    assert ffi.get_param(name) == want, (name, value, ffi.get_param(name), want)
+    ffi.set_param(name, doc[name])
+assert refused(lambda: ffi.set_param("lanes", 0)) and refused(lambda: ffi.set_param("lanes", 9))
+assert refused(lambda: ffi.set_param("msm.log_seg", -1))
+assert now() == doc
+# what was set reads back, the parameters revision 3 lost included
+for name in ("ntt.coset_scale_pass", "quotient.fused_numerator", "side_prio", "msm.two_pass", "debug.fail_next_fused_job"):
+    ffi.set_param(name, 1 - doc[name])
+    assert ffi.get_param(name) == 1 - doc[name], name
+    ffi.set_param(name, doc[name])
+# a name the table lacks fails both ways, whatever its prefix
+for name in ("msm.nope", "ntt.nope", "quotient.nope", "no.such.parameter"):
+    assert refused(lambda: ffi.get_param(name)) and refused(lambda: ffi.set_param(name, 0)), name
+# a batch's scope over per-lane / device parameters puts their defaults back, not 0
+scope = B._ParamScope({"msm.two_pass": 0, "side_prio": 0})
+scope.enter()
+assert ffi.get_param("msm.two_pass") == 0 and ffi.get_param("side_prio") == 0
+scope.leave()
+assert ffi.get_param("msm.two_pass") == 1 and ffi.get_param("side_prio") == 1 and B._ParamScope._active == 0
+# a scope whose second value is refused sets nothing and does not count
+bad = B._ParamScope({"commit.combine_wait_us": 5000, "lanes": 0})
+assert refused(bad.enter)
+bad.leave()
+assert now() == doc and B._ParamScope._active == 0 and B._ParamScope._saved == {}
+# prove_batch that raises before its first proof: no scope left active, the caller's values in place
+ffi.set_param("commit.combine_wait_us", 777)
+def deal(items):
+    raise RuntimeError("deal failed")
+B.deal = deal
+try:
+    B.prove_batch(None, [1, 2, 3], None, None, 4, in_flight=16, combine=True)
+    raise AssertionError("prove_batch did not raise")
+except RuntimeError as e:
+    assert str(e) == "deal failed"
+assert B._ParamScope._active == 0 and B._ParamScope._saved == {}
+assert now() == dict(doc, **{"commit.combine_wait_us": 777})
+# values outlive sg_shutdown; none of this bound a device
+ffi.set_param("msm.two_pass", 2)
+ffi.lib().sg_shutdown()
+assert ffi.get_param("msm.two_pass") == 2 and ffi.get_param("commit.combine_wait_us") == 777
+assert ffi.lib().sg_device() == -1
+print("params ok")
+'''
+
+
+def test_every_parameter_reads_its_default_and_round_trips():
+    """include/summa_gpu.h documents every runtime parameter with its default, and the library's table holds exactly those; in a
+    fresh process (the parameters are process-wide) each reads back its default, set(get) changes nothing, values are clamped,
+    unknown names fail on get and set alike, and batch._ParamScope / prove_batch leave nothing behind when they fail"""
+    import json
+    import subprocess
+    import sys
+    import param_doc
+    doc = param_doc.documented_defaults()
+    assert set(doc) == param_doc.table_names() and len(doc) >= 40
+    clamps = [("commit.combine_wait_us", 10 ** 6, 100000), ("commit.combine_target", 0, 1), ("commit.combine_target", 99, 32),
+              ("commit.combine_runners", 9, 4), ("host.wait_sleep_us", 5000, 1000), ("msm.host_chunks", 20, 8), ("msm.tiny_max", 100, 64),
+              ("msm.acc_log", 3, 1), ("ntt.coset_scale_pass", 5, 1), ("quotient.fused_numerator", 2, 1), ("side_prio", 7, 1),
+              ("msm.log_seg", 99, 12), ("msm.log_fuse_entries", 3, 16), ("msm.log_fuse_entries", 40, 30), ("msm.red_threads", 1, 64),
+              ("msm.red_threads", 100, 128), ("msm.red_threads", 1000, 256), ("msm.acc_threads", 100, 0), ("msm.acc_threads", 128, 128),
+              ("msm.two_pass", 5, 2), ("msm.fused_frontend", 9, 2), ("msm.acc_chain", 4, 1), ("msm.red2d_fold", 0, 1),
+              ("msm.red2d_max_sets", 99, 32), ("msm.acc_waves", 20, 8), ("msm.log_red_chunk", 9, 8), ("msm.log_scatter_rounds", 7, 6),
+              ("ntt.tile_log", 1, 6), ("ntt.threads", 5000, 1024), ("ntt.big_tile_log", 3, 6), ("ntt.big_tile_log", 0, 0),
+              ("ntt.radix4", 7, 0), ("ntt.radix4", 2, 2), ("ntt.max_single_log", 0, 1), ("ntt.max_multi_log", 1, 4), ("ntt.batch_min", 0, 1)]
+    env = dict(os.environ, REPO_ROOT=ROOT, DOCUMENTED_DEFAULTS=json.dumps(doc), CLAMPS=json.dumps(clamps))
+    r = subprocess.run([sys.executable, "-c", PARAMS_CHILD], capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0 and "params ok" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
