@@ -1,0 +1,738 @@
+// C ABI, MSM family: sg_msm_*, the SRS cache, sg_commit* and the commit combiner (summa_gpu.hip holds the core).
+#include "abi_internal.h"
+
+using namespace sg;
+namespace {
+
+void report_timings(sg_msm_timings* timings, const MsmTimings& tm) {
+  if (!timings) return;
+  timings->digits_ms = tm.digits_ms; timings->sort_ms = tm.sort_ms; timings->accumulate_ms = tm.accumulate_ms;
+  timings->reduce_ms = tm.reduce_ms; timings->total_ms = tm.total_ms; timings->window_bits = tm.window_bits;
+  timings->windows = tm.windows; timings->tasks = tm.tasks; timings->max_bucket = tm.max_bucket;
+  timings->accumulate_threads = tm.accumulate_threads;
+  timings->order_ms = tm.order_ms;
+}
+// the SRS a commitment of n scalars runs against (a copy: find_srs)
+int srs_for_commit(uint64_t handle, size_t n, Srs* out) {
+  if (!find_srs(handle, out)) return fail(SG_ERR_INVALID, "unknown SRS handle");
+  if (n > ((size_t)1 << out->k)) return fail(SG_ERR_INVALID, "sg_commit: polynomial longer than the SRS");
+  return SG_OK;
+}
+// 2^k points of g and of g_lagrange into device memory of the cache's own, under a new handle: from host memory, or (from_device)
+// by device-to-device copies on `st` (e.g. out of the receive buffers of an RCCL broadcast)
+int srs_upload(uint32_t k, const void* g, const void* g_lagrange, bool from_device, hipStream_t st, uint64_t* handle_out, const char* what) {
+  const size_t bytes = (size_t)64 << k;
+  Srs s{k, nullptr, nullptr, {}};
+  hipError_t e = hipMalloc(&s.g, bytes);
+  if (e == hipSuccess) e = hipMalloc(&s.g_lagrange, bytes);
+  if (e == hipSuccess) e = from_device ? hipMemcpyAsync(s.g, g, bytes, hipMemcpyDeviceToDevice, st) : hipMemcpy(s.g, g, bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess)
+    e = from_device ? hipMemcpyAsync(s.g_lagrange, g_lagrange, bytes, hipMemcpyDeviceToDevice, st)
+                    : hipMemcpy(s.g_lagrange, g_lagrange, bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess && from_device) e = host_wait_stream(st);   // the bases are read from other streams afterwards
+  if (e != hipSuccess) {
+    if (s.g) (void)hipFree(s.g);
+    if (s.g_lagrange) (void)hipFree(s.g_lagrange);
+    return hip_fail(what, e);
+  }
+  std::lock_guard<std::mutex> lk(g_sh.mu);
+  const uint64_t h = g_sh.next_handle++;
+  g_sh.srs[h] = s;
+  *handle_out = h;
+  return SG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ------------------------------------------------------------------ MSM
+int sg_msm_g1_dev_timed(const void* d_scalars, const void* d_bases, size_t n, void* stream, uint8_t out_affine[64],
+                        sg_msm_timings* timings) {
+  if (!out_affine || (n && (!d_scalars || !d_bases))) return fail(SG_ERR_INVALID, "sg_msm_g1: null argument");
+  LOCKED_CTX();
+  MsmTimings tm;
+  // on the lane's own stream, after everything the caller has enqueued on his: the call returns the point, so nothing of
+  // it is left on any stream afterwards, and the lanes' streams sit on different hardware queues (make_lane_streams) --
+  // which the streams of callers on different threads may or may not
+  hipStream_t st = pick_stream(stream);
+  if (st != g_ctx->stream) {
+    // (an idle caller stream needs no edge -- and a marker on it would queue behind whatever shares ITS hardware queue,
+    // another lane's accumulation for instance)
+    if (hipStreamQuery(st) != hipSuccess) {
+      CHECK_HIP(hipEventRecord(g_ctx->ev_in, st), "event");
+      CHECK_HIP(hipStreamWaitEvent(g_ctx->stream, g_ctx->ev_in, 0), "wait");
+    }
+    st = g_ctx->stream;
+  }
+  hipError_t e = g_ctx->msm.run(static_cast<const fp_words*>(d_scalars), static_cast<const g1_affine_mem*>(d_bases), n,
+                                st, out_affine, timings ? &tm : nullptr);
+  if (e != hipSuccess) return hip_fail("msm", e);
+  report_timings(timings, tm);
+  return SG_OK;
+}
+int sg_msm_g1_dev(const void* d_scalars, const void* d_bases, size_t n, void* stream, uint8_t out_affine[64]) {
+  return sg_msm_g1_dev_timed(d_scalars, d_bases, n, stream, out_affine, nullptr);
+}
+// The host-pointer MSM entry points (sg_msm_g1: scalars and bases in host memory; sg_commit: scalars in host memory, bases
+// resident) pay the link -- 96 or 32 bytes per pair at the 56 GB/s this platform reaches from pageable memory just as from
+// page-locked memory -- before the last addition can run, and a lone MSM is a third latency chains (sort front end, bucket
+// reduction, host tail) besides.  Large inputs are therefore cut into K chunks that run as K jobs on the lane's two
+// engines (two streams) while a third stream carries the copies: chunk i's job runs while chunk i + 1 is still travelling,
+// and one job's latency chains run under the other's accumulation.  The K partial points are added on the host.
+//   [S0 B0] front(0) { back(i) [S i+1 B i+1] finish(i-1) front(i+1) } ... finish, sum
+// -- chunk i + 1 crosses the link while chunk i's accumulation runs.  K: "msm.host_chunks" (0 = by size: 2 from 2^18 pairs; more
+// chunks lose: every job brings its own latency chains, and small kernels beside an accumulation run slowly).
+static constexpr size_t MSM_HOST_SPLIT_MIN = (size_t)1 << 18;
+static int msm_host_chunked(const uint8_t* scalars, const uint8_t* bases_host, const g1_affine_mem* d_bases_resident, size_t n,
+                            uint8_t out_affine[64]) {
+  Context& c = *g_ctx;
+  hipError_t e = c.stage_a.reserve(n ? n * 32 : 1);
+  if (e == hipSuccess && bases_host) e = c.stage_b.reserve(n ? n * 64 : 1);
+  if (e != hipSuccess) return hip_fail("staging buffer", e);
+  const fp_words* d_s = reinterpret_cast<const fp_words*>(c.stage_a.p);
+  const g1_affine_mem* d_b = bases_host ? reinterpret_cast<const g1_affine_mem*>(c.stage_b.p) : d_bases_resident;
+  uint32_t K = (uint32_t)g_sh.param[kRowHostChunks].load();
+  if (K == 0) K = n < MSM_HOST_SPLIT_MIN ? 1u : 2u;   // measured at 2^20 (profiles/r04_sweeps/host_chunks.txt): 2 is the best for both entry points
+  K = std::min<uint32_t>(K, 8u);
+  if (n < 2 * (size_t)K) K = 1;
+  if (K == 1) {
+    if (n) {
+      CHECK_HIP(hipMemcpyAsync(c.stage_a.p, scalars, n * 32, hipMemcpyHostToDevice, c.stream), "H2D copy");
+      if (bases_host) CHECK_HIP(hipMemcpyAsync(c.stage_b.p, bases_host, n * 64, hipMemcpyHostToDevice, c.stream), "H2D copy");
+    }
+    e = c.msm.run(d_s, d_b, n, c.stream, out_affine, nullptr);
+    if (e != hipSuccess) return hip_fail("msm", e);
+    return SG_OK;
+  }
+  MsmEngine* eng[2] = {&c.msm, &c.msm_b};
+  hipStream_t st[2] = {c.stream, c.bstream[0]}, copy = c.bstream[1];
+  std::vector<size_t> lo(K + 1);
+  for (uint32_t i = 0; i <= K; i++) lo[i] = n * i / K;
+  std::vector<uint8_t> part(64 * (size_t)K, 0);
+  std::vector<hipEvent_t> ev_s(K, nullptr), ev_b(K, nullptr);
+  struct Events {
+    std::vector<hipEvent_t>&a, &b;
+    ~Events() {
+      for (auto v : {&a, &b})
+        for (hipEvent_t x : *v)
+          if (x) (void)hipEventDestroy(x);
+    }
+  } events_guard{ev_s, ev_b};
+  for (uint32_t i = 0; i < K; i++) {
+    CHECK_HIP(hipEventCreateWithFlags(&ev_s[i], hipEventDisableTiming), "event");
+    if (bases_host) CHECK_HIP(hipEventCreateWithFlags(&ev_b[i], hipEventDisableTiming), "event");
+  }
+  // the staging buffers may still be read by earlier work of the lane's stream: the other two streams start behind it
+  CHECK_HIP(hipEventRecord(c.ev_in, c.stream), "event");
+  CHECK_HIP(hipStreamWaitEvent(st[1], c.ev_in, 0), "stream wait");
+  CHECK_HIP(hipStreamWaitEvent(copy, c.ev_in, 0), "stream wait");
+  hipError_t err = hipSuccess;          // the first failure; from the first front on, every open job is still closed in order
+  auto copy_scalars = [&](uint32_t i) {
+    if (err != hipSuccess) return;
+    err = hipMemcpyAsync(c.stage_a.p + lo[i] * 32, scalars + lo[i] * 32, (lo[i + 1] - lo[i]) * 32, hipMemcpyHostToDevice, copy);
+    if (err == hipSuccess) err = hipEventRecord(ev_s[i], copy);
+  };
+  auto copy_bases = [&](uint32_t i) {
+    if (err != hipSuccess || !bases_host) return;
+    err = hipMemcpyAsync(c.stage_b.p + lo[i] * 64, bases_host + lo[i] * 64, (lo[i + 1] - lo[i]) * 64, hipMemcpyHostToDevice, copy);
+    if (err == hipSuccess) err = hipEventRecord(ev_b[i], copy);
+  };
+  int state[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // per chunk: 0 nothing, 1 front enqueued, 2 back enqueued, 3 finished
+  auto front = [&](uint32_t i) {
+    if (err != hipSuccess) return;
+    err = hipStreamWaitEvent(st[i & 1], ev_s[i], 0);
+    if (err == hipSuccess) err = eng[i & 1]->enqueue_front(d_s + lo[i], d_b + lo[i], lo[i + 1] - lo[i], st[i & 1], part.data() + 64 * i, nullptr);
+    if (err == hipSuccess) state[i] = 1;
+  };
+  auto back = [&](uint32_t i) {
+    if (state[i] != 1) return;
+    hipError_t e2 = bases_host ? hipStreamWaitEvent(st[i & 1], ev_b[i], 0) : hipSuccess;
+    const hipError_t e3 = eng[i & 1]->enqueue_back();    // (always: an engine left with an open job would poison the lane's next call)
+    state[i] = e3 == hipSuccess ? 2 : 3;
+    if (err == hipSuccess) err = e2 != hipSuccess ? e2 : e3;
+  };
+  auto finish = [&](uint32_t i) {
+    if (state[i] != 2) return;
+    const hipError_t e2 = eng[i & 1]->finish();
+    state[i] = 3;
+    if (err == hipSuccess) err = e2;
+  };
+  // every job of the call is "one of several in flight" from the start: a first accumulation launched at three waves per SIMD
+  // (a job that believes it has the device to itself) would leave the second job's front end no registers to run in
+  struct InFlight {
+    InFlight() { msm_hold_in_flight(true); }
+    ~InFlight() { msm_hold_in_flight(false); }
+  } in_flight_guard;
+  copy_scalars(0);
+  copy_bases(0);
+  front(0);
+  for (uint32_t i = 0; i < K; i++) {
+    back(i);                              // (waits for chunk i's sort; then its accumulation is on the device ...)
+    if (i + 1 < K) {
+      copy_scalars(i + 1);                // ... and runs while the next chunk crosses the link (a copy from pageable memory blocks the host)
+      copy_bases(i + 1);
+      if (i >= 1) finish(i - 1);          // the engine chunk i + 1 runs on
+      front(i + 1);
+    }
+  }
+  for (uint32_t i = 0; i < K; i++) {       // whatever is still open (the last two jobs; everything after a failure)
+    back(i);
+    finish(i);
+  }
+  if (err != hipSuccess) return hip_fail("msm (host chunks)", err);
+  return sg_g1_sum_affine(part.data(), K, out_affine);
+}
+
+int sg_msm_g1(const uint8_t* scalars, const uint8_t* bases, size_t n, uint8_t out_affine[64]) {
+  if (!out_affine || (n && (!scalars || !bases))) return fail(SG_ERR_INVALID, "sg_msm_g1: null argument");
+  LOCKED_CTX();
+  if (n && n <= (size_t)g_sh.param[kRowTinyMax].load()) {   // a handful of points (the verifier's 37): one launch, no staging (MsmEngine::run_tiny)
+    const hipError_t e = g_ctx->msm.run_tiny(scalars, bases, n, g_ctx->stream, out_affine);
+    if (e != hipSuccess) return hip_fail("msm (one launch)", e);
+    return SG_OK;
+  }
+  return msm_host_chunked(scalars, bases, nullptr, n, out_affine);
+}
+
+// A batch of independent MSMs (the commitments of one prover phase): two engines on two
+// streams, so that MSM i's latency-bound bucket reduction overlaps MSM i+1's sort/accumulate.
+// batch driver shared by sg_msm_g1_batch_dev (d_bases given) and sg_commit_batch_dev (tab given: every
+// MSM runs over the precomputed window table); caller holds the context lock
+static int msm_batch_locked(const void* const* d_scalars, const void* const* d_bases, const FixedTable* tab,
+                            const size_t* n, size_t count, void* stream, uint8_t* out_affine, const uint8_t* diff = nullptr) {
+  Context& c = *g_ctx;
+  MsmEngine* eng[2] = {&c.msm, &c.msm_b};
+  for (int k = 0; k < 2; k++) {
+    if (!c.tstream[k]) {
+      int lo = 0, hi = 0;
+      (void)hipDeviceGetStreamPriorityRange(&lo, &hi);  // hi = numerically lowest = highest priority
+      CHECK_HIP(hipStreamCreateWithPriority(&c.tstream[k], hipStreamNonBlocking, hi), "priority stream");
+    }
+    eng[k]->set_tail_stream(c.tstream[k]);
+  }
+  struct Restore {
+    MsmEngine** e;
+    ~Restore() { e[0]->set_tail_stream(nullptr); e[1]->set_tail_stream(nullptr); }
+  } restore{eng};
+  // inputs are ordered on the caller's stream
+  CHECK_HIP(hipEventRecord(c.ev_in, pick_stream(stream)), "event");
+  for (auto& bs : c.bstream) CHECK_HIP(hipStreamWaitEvent(bs, c.ev_in, 0), "stream wait");
+  // consecutive MSMs of equal length are fused into one job (all kernels span the whole
+  // group); groups alternate between the two engines
+  struct Group { size_t first, count; };
+  std::vector<Group> groups;
+  for (size_t i = 0; i < count;) {
+    size_t lim = tab ? eng[0]->max_fused_fixed(*tab, n[i]) : eng[0]->max_fused(n[i]), g = 1;
+    while (i + g < count && n[i + g] == n[i] && g < lim) g++;
+    groups.push_back({i, g});
+    i += g;
+  }
+  hipError_t e = hipSuccess;
+  for (size_t gi = 0; gi < groups.size() && e == hipSuccess; gi++) {
+    const int k = (int)(gi & 1);
+    if (gi >= 2) {
+      e = eng[k]->finish();
+      if (e != hipSuccess) break;
+    }
+    const Group& g = groups[gi];
+    if (tab) {  // d_bases then holds one window table per MSM (all with tab's plan)
+      uint64_t diff_mask = 0;
+      for (size_t m = 0; diff && m < g.count; m++) diff_mask |= (uint64_t)(diff[g.first + m] ? 1 : 0) << m;
+      e = eng[k]->enqueue_front_fixed(reinterpret_cast<const fp_words* const*>(d_scalars + g.first), *tab, g.count,
+                                      n[g.first], c.bstream[k], out_affine + 64 * g.first, nullptr,
+                                      reinterpret_cast<const g1_affine_mem* const*>(d_bases + g.first), diff_mask);
+    }
+    else
+      e = eng[k]->enqueue_front_fused(reinterpret_cast<const fp_words* const*>(d_scalars + g.first),
+                                      reinterpret_cast<const g1_affine_mem* const*>(d_bases + g.first), g.count,
+                                      n[g.first], c.bstream[k], out_affine + 64 * g.first, nullptr);
+    if (e == hipSuccess) e = eng[k]->enqueue_back();
+  }
+  for (size_t gi = (groups.size() >= 2 ? groups.size() - 2 : 0); gi < groups.size() && e == hipSuccess; gi++)
+    e = eng[gi & 1]->finish();
+  if (e != hipSuccess) {
+    (void)hipDeviceSynchronize();
+    return hip_fail("msm batch", e);
+  }
+  return SG_OK;
+}
+int sg_msm_g1_batch_dev(const void* const* d_scalars, const void* const* d_bases, const size_t* n, size_t count,
+                        void* stream, uint8_t* out_affine) {
+  if (count && (!d_scalars || !d_bases || !n || !out_affine)) return fail(SG_ERR_INVALID, "sg_msm_g1_batch: null argument");
+  for (size_t i = 0; i < count; i++) {
+    if (n[i] && (!d_scalars[i] || !d_bases[i])) return fail(SG_ERR_INVALID, "sg_msm_g1_batch: null argument");
+  }
+  LOCKED_CTX();
+  return msm_batch_locked(d_scalars, d_bases, nullptr, n, count, stream, out_affine);
+}
+int sg_msm_g1_batch(const uint8_t* const* scalars, const uint8_t* const* bases, const size_t* n, size_t count,
+                    uint8_t* out_affine) {
+  if (count && (!scalars || !bases || !n || !out_affine)) return fail(SG_ERR_INVALID, "sg_msm_g1_batch: null argument");
+  std::vector<const void*> ds(count), db(count);
+  LOCKED_CTX();   // held across staging AND the batch: the staging buffers are this lane's
+  {
+    size_t tot_s = 0, tot_b = 0;
+    for (size_t i = 0; i < count; i++) { tot_s += n[i] * 32; tot_b += n[i] * 64; }
+    hipError_t e = g_ctx->stage_a.reserve(tot_s + 64);
+    if (e == hipSuccess) e = g_ctx->stage_b.reserve(tot_b + 64);
+    if (e != hipSuccess) return hip_fail("staging buffer", e);
+    size_t os = 0, ob = 0;
+    for (size_t i = 0; i < count; i++) {
+      if (n[i] && (!scalars[i] || !bases[i])) return fail(SG_ERR_INVALID, "sg_msm_g1_batch: null argument");
+      if (n[i]) {
+        CHECK_HIP(hipMemcpyAsync(g_ctx->stage_a.p + os, scalars[i], n[i] * 32, hipMemcpyHostToDevice, g_ctx->stream), "H2D copy");
+        CHECK_HIP(hipMemcpyAsync(g_ctx->stage_b.p + ob, bases[i], n[i] * 64, hipMemcpyHostToDevice, g_ctx->stream), "H2D copy");
+      }
+      ds[i] = g_ctx->stage_a.p + os;
+      db[i] = g_ctx->stage_b.p + ob;
+      os += n[i] * 32;
+      ob += n[i] * 64;
+    }
+  }
+  return sg_msm_g1_batch_dev(ds.data(), db.data(), n, count, g_ctx->stream, out_affine);
+}
+
+// Sum of a handful of affine points on the host (combining the per-GPU partial results of a
+// point-sharded MSM after the all_gather): a few Jacobian additions + one normalisation.
+int sg_g1_sum_affine(const uint8_t* points, size_t n, uint8_t out_affine[64]) {
+  if (!out_affine || (n && !points)) return fail(SG_ERR_INVALID, "sg_g1_sum_affine: null argument");
+  if (n > 4096) return fail(SG_ERR_INVALID, "sg_g1_sum_affine: meant for a handful of points; use sg_msm_g1");
+  using namespace sg::host;
+  Jac acc = Jac::identity();
+  for (size_t i = 0; i < n; i++) {
+    Fq x, y;
+    std::memcpy(x.v, points + 64 * i, 32);
+    std::memcpy(y.v, points + 64 * i + 32, 32);
+    if (x.is_zero() && y.is_zero()) continue;
+    acc = jac_add(acc, Jac{x, y, Fq::one()});
+  }
+  jac_to_affine_bytes(acc, out_affine);
+  return SG_OK;
+}
+
+int sg_srs_upload(uint32_t k, const uint8_t* g, const uint8_t* g_lagrange, uint64_t* handle_out) {
+  if (!g || !g_lagrange || !handle_out || k > 28) return fail(SG_ERR_INVALID, "sg_srs_upload: bad argument");
+  LOCKED_CTX();
+  return srs_upload(k, g, g_lagrange, false, nullptr, handle_out, "sg_srs_upload");
+}
+// the same from device memory (e.g. the receive buffers of an RCCL broadcast): device-to-device copies on `stream`
+int sg_srs_upload_dev(uint32_t k, const void* d_g, const void* d_g_lagrange, void* stream, uint64_t* handle_out) {
+  if (!d_g || !d_g_lagrange || !handle_out || k > 28) return fail(SG_ERR_INVALID, "sg_srs_upload_dev: bad argument");
+  LOCKED_CTX();
+  return srs_upload(k, d_g, d_g_lagrange, true, pick_stream(stream), handle_out, "sg_srs_upload_dev");
+}
+// copies of the resident bases into caller-owned device buffers (2^k x 64 B each; either may be NULL)
+int sg_srs_copy_dev(uint64_t handle, void* d_g_out, void* d_g_lagrange_out, void* stream) {
+  LOCKED_CTX();
+  Srs srs_v;
+  if (!find_srs(handle, &srs_v)) return fail(SG_ERR_INVALID, "unknown SRS handle");
+  const size_t bytes = (size_t)64 << srs_v.k;
+  hipStream_t st = pick_stream(stream);
+  if (d_g_out) CHECK_HIP(hipMemcpyAsync(d_g_out, srs_v.g, bytes, hipMemcpyDeviceToDevice, st), "sg_srs_copy_dev");
+  if (d_g_lagrange_out) CHECK_HIP(hipMemcpyAsync(d_g_lagrange_out, srs_v.g_lagrange, bytes, hipMemcpyDeviceToDevice, st), "sg_srs_copy_dev");
+  return SG_OK;
+}
+// `SerdeFormat::RawBytes` validation of ParamsKZG::read (halo2: from_raw_bytes rejects points off the curve; the
+// `RawBytesUnchecked` format skips this): *bad_out = number of points of the resident SRS that fail y^2 = x^3 + 3
+int sg_srs_check(uint64_t handle, uint64_t* bad_out) {
+  if (!bad_out) return fail(SG_ERR_INVALID, "sg_srs_check: null argument");
+  LOCKED_CTX();
+  Srs srs;
+  if (!find_srs(handle, &srs)) return fail(SG_ERR_INVALID, "unknown SRS handle");
+  uint8_t* cnt = nullptr;
+  hipStream_t s = g_ctx->stream;
+  hipError_t e = scratch_for(s, 7, 64, &cnt);
+  uint32_t h[2] = {0, 0};
+  const size_t n = (size_t)1 << srs.k;
+  for (int b = 0; b < 2 && e == hipSuccess; b++) {
+    e = g1_on_curve(b ? srs.g_lagrange : srs.g, n, reinterpret_cast<uint32_t*>(cnt), s);
+    if (e == hipSuccess) e = host_copy_d2h(&h[b], cnt, 4, s);
+  }
+  if (e != hipSuccess) return hip_fail("sg_srs_check", e);
+  *bad_out = (uint64_t)h[0] + h[1];
+  return SG_OK;
+}
+int sg_srs_free(uint64_t handle) {
+  LOCKED_CTX();
+  Srs gone;
+  {
+    std::lock_guard<std::mutex> lk(g_sh.mu);
+    auto it = g_sh.srs.find(handle);
+    if (it == g_sh.srs.end()) return fail(SG_ERR_INVALID, "sg_srs_free: unknown handle");
+    gone = it->second;
+    g_sh.srs.erase(it);
+  }
+  (void)hipFree(gone.g);          // hipFree waits for the device: work in flight on these bases completes first
+  (void)hipFree(gone.g_lagrange);
+  if (gone.lagrange_prefix) (void)hipFree(gone.lagrange_prefix);
+  for (auto& t : gone.tab)
+    if (t.table) (void)hipFree(t.table);
+  return SG_OK;
+}
+// Precompute the fixed-base window table of one basis: W x 2^k points, row w = 2^(offset_w) * basis.
+// Later sg_commit* calls on this basis take the fixed-base path (same result bits).
+int sg_srs_precompute(uint64_t handle, int basis, uint32_t window_bits) {
+  if (basis < 0 || basis > 2) return fail(SG_ERR_INVALID, "sg_srs_precompute: bad basis");
+  if (window_bits && (window_bits < 4 || window_bits > 16)) return fail(SG_ERR_INVALID, "sg_srs_precompute: window_bits in [4, 16]");
+  LOCKED_CTX();
+  Srs s;   // a copy: the entry itself is updated under the lock once the table exists
+  if (!find_srs(handle, &s)) return fail(SG_ERR_INVALID, "unknown SRS handle");
+  const size_t n = (size_t)1 << s.k;
+  const uint32_t c = window_bits ? window_bits : fixed_window_bits_for(n);
+  hipError_t e = hipSuccess;
+  g1_affine_mem* new_prefix = nullptr;
+  if (basis == 2 && !s.lagrange_prefix) {   // Q_i = L_0 + ... + L_i, once per SRS
+    g1_affine_mem* q = nullptr;
+    e = hipMalloc(&q, n * sizeof(g1_affine_mem));
+    if (e == hipSuccess) e = g1_prefix_sums(s.g_lagrange, n, q, g_ctx->stream);
+    if (e != hipSuccess) {
+      if (q) (void)hipFree(q);
+      return hip_fail("sg_srs_precompute: prefix sums", e);
+    }
+    s.lagrange_prefix = new_prefix = q;
+  }
+  FixedTable t;
+  e = build_window_table(basis == 2 ? s.lagrange_prefix : basis ? s.g_lagrange : s.g, n, c, &t, g_ctx->stream);
+  if (e == hipSuccess) e = host_wait_stream(g_ctx->stream);
+  if (e != hipSuccess) {
+    if (new_prefix) (void)hipFree(new_prefix);
+    return hip_fail("sg_srs_precompute", e);
+  }
+  {
+    std::lock_guard<std::mutex> lk(g_sh.mu);
+    auto it = g_sh.srs.find(handle);
+    if (it == g_sh.srs.end()) {   // freed by another thread meanwhile
+      retire_device_memory(t.table);
+      retire_device_memory(new_prefix);
+      return fail(SG_ERR_INVALID, "sg_srs_precompute: the handle was freed during the call");
+    }
+    if (new_prefix) {
+      if (it->second.lagrange_prefix) retire_device_memory(new_prefix);   // two concurrent precomputes: keep the first
+      else it->second.lagrange_prefix = new_prefix;
+    }
+    retire_device_memory(it->second.tab[basis].table);   // commitments of other lanes may still be reading the old table
+    it->second.tab[basis] = t;
+  }
+  return SG_OK;
+}
+int sg_srs_device_ptrs(uint64_t handle, const void** d_g, const void** d_g_lagrange, uint32_t* k) {
+  LOCKED_CTX();
+  Srs srs;
+  if (!find_srs(handle, &srs)) return fail(SG_ERR_INVALID, "unknown SRS handle");
+  if (d_g) *d_g = srs.g;
+  if (d_g_lagrange) *d_g_lagrange = srs.g_lagrange;
+  if (k) *k = srs.k;
+  return SG_OK;
+}
+// basis 2 = a Lagrange column taken in difference form (same commitment as basis 1): possible when the prefix-sum table
+// exists and the column has the full 2^k rows
+static bool diff_form_ready(const Srs& s, size_t n) { return s.tab[2].table != nullptr && n == ((size_t)1 << s.k); }
+static hipError_t commit_run(const Srs& s, int basis, const fp_words* d_scalars, size_t n, hipStream_t stream,
+                             uint8_t out_affine[64], MsmTimings* tm = nullptr) {
+  MsmEngine& eng = g_ctx->msm;
+  const bool diff = basis == 2 && diff_form_ready(s, n);
+  if (basis == 2 && !diff) basis = 1;
+  if (s.tab[basis].table && n) {
+    const fp_words* sc[1] = {d_scalars};
+    hipError_t e = eng.enqueue_front_fixed(sc, s.tab[basis], 1, n, stream, out_affine, tm, nullptr, diff ? 1u : 0u);
+    if (e == hipSuccess) e = eng.enqueue_back();
+    if (e == hipSuccess) e = eng.finish();
+    return e;
+  }
+  return eng.run(d_scalars, basis ? s.g_lagrange : s.g, n, stream, out_affine, tm);
+}
+int sg_commit_dev_timed(uint64_t srs_handle, int basis, const void* d_scalars, size_t n, void* stream,
+                        uint8_t out_affine[64], sg_msm_timings* timings) {
+  if (!out_affine || (n && !d_scalars) || basis < 0 || basis > 2) return fail(SG_ERR_INVALID, "sg_commit: bad argument");
+  LOCKED_CTX();
+  Srs s;
+  TRY(srs_for_commit(srs_handle, n, &s));
+  MsmTimings tm;
+  hipError_t e = commit_run(s, basis, static_cast<const fp_words*>(d_scalars), n, pick_stream(stream), out_affine,
+                            timings ? &tm : nullptr);
+  if (e != hipSuccess) return hip_fail("msm", e);
+  report_timings(timings, tm);
+  return SG_OK;
+}
+int sg_commit_dev(uint64_t srs_handle, int basis, const void* d_scalars, size_t n, void* stream,
+                  uint8_t out_affine[64]) {
+  return sg_commit_dev_timed(srs_handle, basis, d_scalars, n, stream, out_affine, nullptr);
+}
+// `count` commitments of equal length against one basis as fused jobs (the advice / quotient-piece
+// commitments of one proof phase); takes the fixed-base path when the table exists
+int sg_commit_batch_dev(uint64_t srs_handle, int basis, const void* const* d_scalars, size_t count, size_t n,
+                        void* stream, uint8_t* out_affine) {
+  if ((count && (!d_scalars || !out_affine)) || basis < 0 || basis > 2) return fail(SG_ERR_INVALID, "sg_commit_batch: bad argument");
+  for (size_t i = 0; i < count; i++)
+    if (n && !d_scalars[i]) return fail(SG_ERR_INVALID, "sg_commit_batch: null argument");
+  LOCKED_CTX();
+  Srs s;
+  TRY(srs_for_commit(srs_handle, n, &s));
+  std::vector<size_t> ns(count, n);
+  const bool diff = basis == 2 && diff_form_ready(s, n);
+  if (basis == 2 && !diff) basis = 1;
+  const bool fixed = s.tab[basis].table != nullptr;
+  std::vector<const void*> bases(count, fixed ? (const void*)s.tab[basis].table : (const void*)(basis ? s.g_lagrange : s.g));
+  std::vector<uint8_t> flags(count, diff ? 1 : 0);
+  return msm_batch_locked(d_scalars, bases.data(), fixed ? &s.tab[basis] : nullptr, ns.data(), count, stream, out_affine, flags.data());
+}
+// the same with one basis per polynomial (0 = g, 1 = g_lagrange): e.g. the grand-product commitments (Lagrange)
+// and the random polynomial (coefficients) of one prover phase as ONE fused job
+// ---- commit combiner.  Proofs in flight on several host threads (circuits_halo2_amd/batch.py) each issue five commitment
+// jobs; alone, every job pays its own sort front-end, bucket reduction and host tail, and the jobs of different threads
+// compete for the chip.  A thread that has declared itself (sg_commit_combine_begin) hands its sg_commit_batch*_dev calls
+// to the combiner instead: the first caller to find no job running becomes the runner, waits a bounded time for the
+// other declared threads to arrive (they do: after one fused job all of them get their points at the same moment and
+// reach their next commitment together), takes EVERYTHING pending with the same SRS and length and runs it as ONE
+// fused job on a lane of its own; callers that arrive while a job runs form the next one.  No caller ever waits for a
+// thread that might not come -- only for a deadline -- so a failed or finished proof cannot block the others.
+struct CommitReq {
+  uint64_t srs;
+  size_t n, count;
+  const int* basis;
+  const void* const* scalars;
+  uint8_t* out;
+  hipEvent_t ready;      // recorded on the caller's stream after its inputs were enqueued
+  int rc = SG_OK;
+  bool done = false;
+  char err[256] = "";
+};
+struct Combiner {
+  std::mutex mu;
+  std::condition_variable cv;
+  std::deque<CommitReq*> pending;
+  int runners = 0;                       // fused jobs running now
+  int busy = 0;                          // requests inside those jobs
+  int members = 0;                       // threads between sg_commit_combine_begin and _end
+  std::atomic<uint64_t> jobs{0}, requests{0};   // statistics: fused jobs run, requests served
+  std::atomic<uint64_t> isolated{0};     // members re-run alone after their fused job failed as a whole
+};
+Combiner g_comb;
+thread_local bool t_combine = false;
+thread_local hipEvent_t t_ready = nullptr;
+
+static int commit_batch_mixed_core(uint64_t srs_handle, const int* basis, const void* const* d_scalars, size_t count, size_t n,
+                                   void* stream, uint8_t* out_affine);
+
+// runs on the runner's thread: one fused job for all requests of `batch` (same SRS, same n)
+static void combiner_run_unguarded(const std::vector<CommitReq*>& batch);
+static void combiner_run(const std::vector<CommitReq*>& batch) {
+  try {
+    combiner_run_unguarded(batch);
+  } catch (const std::exception& e) {   // (allocation failures of the host vectors: every member learns of it)
+    for (CommitReq* r : batch) {
+      r->rc = SG_ERR_NOMEM;
+      std::snprintf(r->err, sizeof r->err, "commit combiner: %s", e.what());
+    }
+  }
+}
+static void combiner_run_unguarded(const std::vector<CommitReq*>& batch) {
+  std::vector<int> basis;
+  std::vector<const void*> scalars;
+  size_t total = 0;
+  for (CommitReq* r : batch) total += r->count;
+  basis.reserve(total);
+  scalars.reserve(total);
+  for (CommitReq* r : batch)
+    for (size_t i = 0; i < r->count; i++) {
+      basis.push_back(r->basis[i]);
+      scalars.push_back(r->scalars[i]);
+    }
+  std::vector<uint8_t> out(64 * total);
+  int rc;
+  {
+    LaneHold hold;     // the job's own lane: its stream waits for every member's inputs
+    rc = hold.rc;
+    if (rc == SG_OK) {
+      for (CommitReq* r : batch) {
+        hipError_t e = hipStreamWaitEvent(g_ctx->stream, r->ready, 0);
+        if (e != hipSuccess) { rc = hip_fail("commit combiner: stream wait", e); break; }
+      }
+    }
+    if (rc == SG_OK && batch.size() > 1 && g_sh.param[kRowFailNextFusedJob].exchange(0)) rc = fail(SG_ERR_NOMEM, "commit combiner: injected failure of a fused job");
+    else if (rc == SG_OK) rc = commit_batch_mixed_core(batch[0]->srs, basis.data(), scalars.data(), total, batch[0]->n, g_ctx->stream, out.data());
+  }
+  size_t at = 0;
+  for (CommitReq* r : batch) {
+    r->rc = rc;
+    if (rc == SG_OK) std::memcpy(r->out, out.data() + 64 * at, 64 * r->count);
+    else std::snprintf(r->err, sizeof r->err, "%s", g_err);
+    at += r->count;
+  }
+  if (rc != SG_OK && batch.size() > 1) {
+    // The fused job failed AS A WHOLE -- out of device memory at this size, one member's bad pointer or stale handle.  One
+    // member's fault must not cost the others their proofs: every member gets a job of its own (same lane discipline:
+    // the job's stream waits for that member's inputs) and its own return value and message.
+    for (CommitReq* r : batch) {
+      LaneHold hold;
+      int rc1 = hold.rc;
+      if (rc1 == SG_OK) {
+        const hipError_t e = hipStreamWaitEvent(g_ctx->stream, r->ready, 0);
+        if (e != hipSuccess) rc1 = hip_fail("commit combiner: stream wait", e);
+      }
+      if (rc1 == SG_OK) rc1 = commit_batch_mixed_core(r->srs, r->basis, r->scalars, r->count, r->n, g_ctx->stream, r->out);
+      r->rc = rc1;
+      if (rc1 != SG_OK) std::snprintf(r->err, sizeof r->err, "%s", g_err);
+      else r->err[0] = 0;
+      g_comb.isolated.fetch_add(1);
+    }
+  }
+  g_comb.jobs.fetch_add(1);
+  g_comb.requests.fetch_add(batch.size());
+}
+
+static int commit_combined(uint64_t srs_handle, const int* basis, const void* const* d_scalars, size_t count, size_t n,
+                           void* stream, uint8_t* out_affine) {
+  if (!t_ready) CHECK_HIP(hipEventCreateWithFlags(&t_ready, hipEventDisableTiming), "event");
+  CHECK_HIP(hipEventRecord(t_ready, pick_stream(stream)), "event");
+  CommitReq req{srs_handle, n, count, basis, d_scalars, out_affine, t_ready};
+  std::unique_lock<std::mutex> lk(g_comb.mu);
+  g_comb.pending.push_back(&req);
+  g_comb.cv.notify_all();                         // a runner waiting for stragglers counts again
+  while (!req.done) {
+    const bool mine_pending = std::find(g_comb.pending.begin(), g_comb.pending.end(), &req) != g_comb.pending.end();
+    if (!mine_pending || g_comb.runners >= g_sh.param[kRowCombineRunners].load()) {   // my request is inside a running job, or no runner slot is free
+      g_comb.cv.wait(lk);
+      continue;
+    }
+    g_comb.runners++;                             // this thread runs the next job
+    // the bounded wait shrinks with the company that can still come: a thread is a member for the whole of its proof, not
+    // only around its commitments, so at the tail of a batch the few proofs left would otherwise sit out the full wait
+    // (5 ms in batch.prove_batch) at every one of their five jobs for members that are busy elsewhere
+    const int may_come = std::max(1, g_comb.members - g_comb.busy - (int)g_comb.pending.size());
+    const int wait_us = std::min(g_sh.param[kRowCombineWaitUs].load(), 400 * may_come);
+    const auto deadline = std::chrono::steady_clock::now() + std::chrono::microseconds(wait_us);
+    // wait for company: until `target` requests are pending, or every declared thread that is not inside a running job
+    // has arrived, or the deadline
+    while ((int)g_comb.pending.size() < std::min(g_sh.param[kRowCombineTarget].load(), g_comb.members - g_comb.busy))
+      if (g_comb.cv.wait_until(lk, deadline) == std::cv_status::timeout) break;
+    // everything pending with the first request's SRS and length, up to MAX_FUSED polynomials
+    if (g_comb.pending.empty()) {   // another runner took everything meanwhile (this thread's request included)
+      g_comb.runners--;
+      g_comb.cv.notify_all();
+      continue;
+    }
+    std::vector<CommitReq*> batch;
+    size_t polys = 0;
+    CommitReq* first = g_comb.pending.front();
+    for (auto it = g_comb.pending.begin(); it != g_comb.pending.end();) {
+      CommitReq* r = *it;
+      if (r->srs == first->srs && r->n == first->n && polys + r->count <= MAX_FUSED) {
+        batch.push_back(r);
+        polys += r->count;
+        it = g_comb.pending.erase(it);
+      } else {
+        ++it;
+      }
+    }
+    g_comb.busy += (int)batch.size();
+    lk.unlock();
+    combiner_run(batch);
+    lk.lock();
+    for (CommitReq* r : batch) r->done = true;
+    g_comb.busy -= (int)batch.size();
+    g_comb.runners--;
+    g_comb.cv.notify_all();
+  }
+  if (req.rc != SG_OK) std::snprintf(g_err, sizeof g_err, "%s", req.err);
+  return req.rc;
+}
+
+int sg_commit_combine_begin(void) {
+  if (t_combine) return SG_OK;
+  t_combine = true;
+  std::lock_guard<std::mutex> lk(g_comb.mu);
+  g_comb.members++;
+  return SG_OK;
+}
+int sg_commit_combine_end(void) {
+  if (!t_combine) return SG_OK;
+  t_combine = false;
+  {
+    std::lock_guard<std::mutex> lk(g_comb.mu);
+    g_comb.members--;
+    g_comb.cv.notify_all();          // a runner waiting for this thread stops counting it
+  }
+  if (t_ready) {                     // this thread's requests have all returned: nothing waits on the event any more
+    (void)hipEventDestroy(t_ready);
+    t_ready = nullptr;
+  }
+  return SG_OK;
+}
+int sg_commit_combining(void) { return t_combine ? 1 : 0; }
+int sg_commit_combine_stats(uint64_t* jobs, uint64_t* requests) {
+  if (jobs) *jobs = g_comb.jobs.load();
+  if (requests) *requests = g_comb.requests.load();
+  return SG_OK;
+}
+
+int sg_commit_batch_mixed_dev(uint64_t srs_handle, const int* basis, const void* const* d_scalars, size_t count, size_t n,
+                              void* stream, uint8_t* out_affine) {
+  if (count && (!d_scalars || !out_affine || !basis)) return fail(SG_ERR_INVALID, "sg_commit_batch_mixed: bad argument");
+  for (size_t i = 0; i < count; i++)
+    if ((n && !d_scalars[i]) || basis[i] < 0 || (basis[i] & ~SG_BASIS_SPARSE) > 2) return fail(SG_ERR_INVALID, "sg_commit_batch_mixed: bad argument");
+  if (t_combine && count && n && count <= MAX_FUSED && g_depth == 0)
+    return commit_combined(srs_handle, basis, d_scalars, count, n, stream, out_affine);
+  return commit_batch_mixed_core(srs_handle, basis, d_scalars, count, n, stream, out_affine);
+}
+static int commit_batch_mixed_core(uint64_t srs_handle, const int* basis, const void* const* d_scalars, size_t count, size_t n,
+                                   void* stream, uint8_t* out_affine) {
+  LOCKED_CTX();
+  Srs s;
+  TRY(srs_for_commit(srs_handle, n, &s));
+  // fixed-base only when both tables exist with one plan; otherwise the generic fused path over g / g_lagrange
+  const bool fixed = s.tab[0].table && s.tab[1].table && s.tab[0].c == s.tab[1].c && s.tab[0].n == s.tab[1].n;
+  // difference form (basis 2) needs the prefix-sum table on the same plan; otherwise such a column is an ordinary Lagrange one
+  const bool diff_ok = fixed && diff_form_ready(s, n) && s.tab[2].c == s.tab[0].c && s.tab[2].n == s.tab[0].n;
+  std::vector<size_t> ns(count, n);
+  std::vector<const void*> bases(count);
+  std::vector<uint8_t> flags(count, 0);
+  bool all_sparse = count > 0;
+  for (size_t i = 0; i < count; i++) {
+    const int want = basis[i] & ~SG_BASIS_SPARSE;
+    all_sparse = all_sparse && (basis[i] & SG_BASIS_SPARSE);
+    const int b = want == 2 ? (diff_ok ? 2 : 1) : want;
+    flags[i] = b == 2;
+    bases[i] = fixed ? (const void*)s.tab[b].table : (const void*)(b ? s.g_lagrange : s.g);
+  }
+  // A job whose columns are all witness-like (mostly zeros and small values: few entries, some of them in heavy buckets) is a
+  // latency chain of one task length whatever its size: tasks of 8 instead of 16 halve it (a proof's first commitment job
+  // 1.07 -> 1.00 ms) where dense jobs lose by them (profiles/r04_sweeps/task_length_by_phase.txt).  A hint, never semantics.
+  struct SegRestore {
+    Context& c;
+    uint32_t seg;
+    ~SegRestore() { msm_set(c, &MsmConfig::log_seg, (int)seg); }
+  } seg_restore{*g_ctx, g_ctx->msm.config().log_seg};
+  // (only for jobs small enough for the 2-D reduction, which adds up to eight partial sums per bucket itself: a fused job of many
+  // proofs' columns goes through merge rounds, and shorter tasks would add one)
+  if (all_sparse && fixed && count <= 5 && g_ctx->msm.config().log_seg == 0 && n >= ((size_t)1 << 14))
+    msm_set(*g_ctx, &MsmConfig::log_seg, 3);
+  return msm_batch_locked(d_scalars, bases.data(), fixed ? &s.tab[0] : nullptr, ns.data(), count, stream, out_affine, flags.data());
+}
+int sg_commit(uint64_t srs_handle, int basis, const uint8_t* scalars, size_t n, uint8_t out_affine[64]) {
+  if (!out_affine || (n && !scalars) || basis < 0 || basis > 2) return fail(SG_ERR_INVALID, "sg_commit: bad argument");
+  LOCKED_CTX();
+  Srs sr;
+  TRY(srs_for_commit(srs_handle, n, &sr));
+  {
+    // no window table for this basis (sg_srs_precompute not called): the generic MSM over the resident bases, in chunks, so that
+    // the scalars' upload and one job's latency chains run under another job's accumulation (msm_host_chunked)
+    const int b = (basis == 2 && !diff_form_ready(sr, n)) ? 1 : basis;
+    if (b != 2 && !sr.tab[b].table && n >= MSM_HOST_SPLIT_MIN)
+      return msm_host_chunked(scalars, nullptr, b ? sr.g_lagrange : sr.g, n, out_affine);
+  }
+  TRY(upload(g_ctx->stage_a, scalars, n * 32, g_ctx->stream));
+  hipError_t e = commit_run(sr, basis, reinterpret_cast<const fp_words*>(g_ctx->stage_a.p), n, g_ctx->stream, out_affine);
+  if (e != hipSuccess) return hip_fail("msm", e);
+  return SG_OK;
+}
+
+int sg_msm_launch_log(uint32_t* out_words, size_t cap_records, size_t* n_records) {
+  if (!n_records || (cap_records && !out_words)) return fail(SG_ERR_INVALID, "sg_msm_launch_log: bad argument");
+  static_assert(sizeof(AccLaunchRecord) == 8 * sizeof(uint32_t), "record layout is part of the ABI");
+  *n_records = msm_acc_log_read(reinterpret_cast<AccLaunchRecord*>(out_words), cap_records);
+  return SG_OK;
+}
+
+}  // extern "C"
