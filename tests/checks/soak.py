@@ -1,5 +1,6 @@
 """randomised soak of the MSM paths against the oracle: sizes, batch shapes, fixed / generic, skewed scalars,
-parameter toggles; stops after SECONDS (default 120).  Exit code 1 on the first mismatch."""
+parameter toggles; stops after SECONDS (default 120).  Exit code 1 on the first mismatch.
+Its deterministic counterpart, collected by pytest, is tests/test_gpu_msm_backends.py."""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import ctypes as C

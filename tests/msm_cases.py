@@ -1,0 +1,472 @@
+"""Scalar and case builders shared by the MSM GPU tests (test_gpu_msm_frontends.py, test_gpu_msm_backends.py) and checked
+without a GPU by test_msm_cases_cpu.py; a plain helper module like quotient_witness.py and mst_assignment.py.
+
+Three parts: the scalar distributions and known-answer cases of the front-end tests; the signed-digit recoding of
+csrc/msm.hip restated in Python (`recode`, `digits_np`) with a builder that puts a prescribed number of entries into chosen
+buckets (`place`, `populations`); and the decision rules of MsmEngine::enqueue_back_impl restated as `expected_backend` /
+`accumulate_threads` -- whoever moves a threshold in msm.hip updates the restatement here."""
+from collections import Counter
+
+import numpy as np
+
+R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
+_R_LIMBS = np.array([(R >> (64 * i)) & ((1 << 64) - 1) for i in range(4)], dtype=np.uint64)
+
+
+def _dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _mont(canon):
+    """canonical 32-B little-endian values -> (device tensor, host copy), both Montgomery"""
+    from circuits_halo2_amd.arithmetic import fr_to_montgomery
+    t = fr_to_montgomery(_dev(canon))
+    return t, t.cpu().numpy()
+
+
+def make_pool(n_pool):
+    """n_pool bases s_i * G on the device and their discrete logs s_i (Montgomery, host); cases take slices"""
+    from circuits_halo2_amd.arithmetic import g1_fixed_base_mul
+    from circuits_halo2_amd.utils import random_fr_canonical
+    s_dev, s_host = _mont(random_fr_canonical(0x5EED5, n_pool))
+    return {"bases": g1_fixed_base_mul(s_dev), "s": s_host}
+
+
+# ----------------------------------------------------------------------------- scalars (canonical, numpy uint8 n x 32)
+def _neg(canon):
+    """r - x limb-wise (0 stays 0), vectorised"""
+    x = np.ascontiguousarray(canon).view(np.uint64).reshape(-1, 4)
+    out = np.zeros_like(x)
+    borrow = np.zeros(x.shape[0], dtype=bool)
+    with np.errstate(over="ignore"):
+        for i in range(4):
+            a, b = _R_LIMBS[i], x[:, i]
+            out[:, i] = a - b - borrow.astype(np.uint64)
+            borrow = (b > a) | ((b == a) & borrow)
+    out[(x == 0).all(axis=1)] = 0
+    return out.view(np.uint8).reshape(-1)
+
+
+def _ints(values):
+    return np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in values), dtype=np.uint8).copy()
+
+
+def window_plan(c):
+    """widths of the windows (make_window_plan in csrc/msm.hip): W - 1 signed windows of c or c - 1 bits and an unsigned
+    top window of c - 1 bits, 254 bits in all"""
+    W = (255 + c - 1) // c
+    width = [c] * (W - 1) + [c - 1]
+    for k in range(W * c - 255):
+        width[W - 2 - k] -= 1
+    assert sum(width) == 254
+    return width
+
+
+def signed_digit_specials(c):
+    """scalars at the edges of the signed-digit recoding for window width c: every digit -2^(w-1) (the largest bucket,
+    negative), every digit 2^(w-1) - 1, every raw window value 2^(w-1) (the K offset itself), all-ones windows (carry
+    chains), the top window at its largest (r - 1, r - 2) and the single-window edges"""
+    width = window_plan(c)
+    off = [sum(width[:j]) for j in range(len(width))]
+    top = off[-1]
+    K = sum(1 << (off[j] + width[j] - 1) for j in range(len(width) - 1))
+    low_half = sum(((1 << (width[j] - 1)) - 1) << off[j] for j in range(len(width) - 1))
+    vals = [
+        (1 << top) - K,                          # every signed digit -2^(w-1), top digit 1
+        ((R - 1) >> top << top) - K,             # ... with the largest top digit that stays below r
+        low_half,                                # every signed digit 2^(w-1) - 1
+        low_half + (5 << top),
+        K,                                       # every raw window value 2^(w-1)
+        K - sum(1 << o for o in off[:-1]),       # every raw window value 2^(w-1) - 1
+        (1 << top) - 1,                          # every signed window all ones: a carry through all of them
+        (1 << 253) - 1,
+        R - 1, R - 2, (R - 1) // 2, R - (1 << top),
+        1 << (c - 1), (1 << (c - 1)) - 1, (1 << c) - 1, 1 << top,
+    ]
+    assert all(0 < v < R for v in vals)
+    return vals
+
+
+def scalars(dist, n, seed):
+    """canonical scalars of one distribution (pm_pairs / s_neg_s: see `case`)"""
+    from circuits_halo2_amd.utils import random_fr_canonical
+    rng = np.random.default_rng(seed)
+    out = np.zeros((n, 32), dtype=np.uint8)
+    if dist == "uniform":
+        return random_fr_canonical(seed, n)
+    if dist == "equal":                          # one bucket per window: one oversized bin per set
+        return np.tile(random_fr_canonical(seed, 1), n)
+    if dist == "byte":                           # the range-check column: window 0 only, its first coarse bins oversized
+        out[:, 0] = rng.integers(0, 256, size=n)
+    elif dist == "selector":                     # 0 / 1, about half ones
+        out[:, 0] = rng.random(n) < 0.5
+    elif dist == "sparse":                       # 99 % zero, the rest below 2^64: mostly empty bins
+        keep = rng.random(n) < 0.01
+        out[keep, :8] = rng.integers(0, 256, size=(int(keep.sum()), 8))
+    elif dist == "tiled32":                      # 32 distinct values: deep buckets, merge rounds
+        return np.tile(random_fr_canonical(seed, 32), (n + 31) // 32)[:32 * n].copy()
+    elif dist.startswith("signed"):              # signed-digit edges for window width int(dist[6:]), every 4th point uniform
+        sp = _ints(signed_digit_specials(int(dist[6:]))).reshape(-1, 32)
+        out[:] = sp[np.arange(n) % sp.shape[0]]
+        u = random_fr_canonical(seed, n).reshape(n, 32)
+        out[3::4] = u[3::4]
+    else:
+        raise ValueError(dist)
+    return out.reshape(-1)
+
+
+def case_with_scalars(O, pool, dist, n, seed, off=0):
+    """`case` and the canonical scalars it was built from (for the bucket counts: `digits_np`)"""
+    import torch
+    from circuits_halo2_amd.arithmetic import g1_fixed_base_mul
+    from circuits_halo2_amd.utils import random_fr_canonical
+    if dist == "pm_pairs":
+        assert n % 2 == 0
+        half = random_fr_canonical(seed, n // 2).reshape(-1, 32)
+        logs = np.empty((n, 32), dtype=np.uint8)
+        logs[0::2], logs[1::2] = half, _neg(half).reshape(-1, 32)
+        logs[-8:] = random_fr_canonical(seed + 1, 8).reshape(8, 32)
+        s_dev, s_host = _mont(logs.reshape(-1))
+        bases = g1_fixed_base_mul(s_dev)
+        k = np.repeat(random_fr_canonical(seed + 2, n // 2).reshape(-1, 32), 2, axis=0)
+        k[-8:] = random_fr_canonical(seed + 3, 8).reshape(8, 32)
+        canon = k.reshape(-1)
+        k_dev, k_host = _mont(canon)
+    elif dist == "s_neg_s":
+        assert n % 2 == 0
+        half = random_fr_canonical(seed, n // 2).reshape(-1, 32)
+        k = np.empty((n, 32), dtype=np.uint8)
+        k[0::2], k[1::2] = half, _neg(half).reshape(-1, 32)
+        k[-8:] = random_fr_canonical(seed + 1, 8).reshape(8, 32)
+        canon = k.reshape(-1)
+        k_dev, k_host = _mont(canon)
+        bases = _dev(np.tile(O.g1_generator(), n))
+        s_host = O.fr_to_mont(np.tile(_ints([1]), n))
+    else:
+        canon = scalars(dist, n, seed)
+        k_dev, k_host = _mont(canon)
+        bases = pool["bases"][64 * off:64 * (off + n)]
+        s_host = pool["s"][32 * off:32 * (off + n)]
+    want = O.g1_mul(O.g1_generator(), O.fr_dot(k_host, s_host))
+    torch.cuda.synchronize()
+    return k_dev, bases, want, canon
+
+
+def case(O, pool, dist, n, seed, off=0):
+    """(scalars on the device, bases on the device, the expected point) for one MSM of `n` points.
+    pm_pairs: bases P, -P alternating with equal scalars in pairs (they cancel inside one bucket); s_neg_s: one repeated base G
+    with scalars s, r - s alternating (their total is the identity).  Both end in 8 unpaired uniform points so that the
+    answer is not the identity (a kernel that lost every point would not pass)."""
+    return case_with_scalars(O, pool, dist, n, seed, off)[:3]
+
+
+# ----------------------------------------------------------------------------- the signed-digit recoding, restated
+def window_offsets(c):
+    width = window_plan(c)
+    return [sum(width[:j]) for j in range(len(width))]
+
+
+def recode(v, c):
+    """the signed digits of the canonical scalar v, one per window (msm_digits): with K = sum over the signed windows of
+    2^(o_j + w_j - 1), d_j = (((v + K) >> o_j) & (2^w_j - 1)) - 2^(w_j - 1); the top window keeps its raw value"""
+    width, off = window_plan(c), window_offsets(c)
+    W = len(width)
+    s = v + sum(1 << (off[j] + width[j] - 1) for j in range(W - 1))
+    return [((s >> off[j]) & ((1 << width[j]) - 1)) - ((1 << (width[j] - 1)) if j + 1 < W else 0) for j in range(W)]
+
+
+def bucket_map(values, c):
+    """(window, bucket, negative) -> entries, for canonical scalars `values` (ints); digit d lands in bucket |d| - 1"""
+    m = Counter()
+    for v in values:
+        for j, d in enumerate(recode(v, c)):
+            if d:
+                m[(j, abs(d) - 1, d < 0)] += 1
+    return m
+
+
+def digits_np(canon, c):
+    """`recode` of n canonical scalars (uint8 n x 32) at once -> int32 array (windows, n)"""
+    width, off = window_plan(c), window_offsets(c)
+    W = len(width)
+    K = sum(1 << (off[j] + width[j] - 1) for j in range(W - 1))
+    x = np.ascontiguousarray(canon).view(np.uint64).reshape(-1, 4)
+    s = np.zeros((x.shape[0], 5), dtype=np.uint64)
+    carry = np.zeros(x.shape[0], dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        for i in range(4):
+            t = x[:, i] + np.uint64((K >> (64 * i)) & ((1 << 64) - 1))
+            c1 = t < x[:, i]
+            t2 = t + carry
+            carry = (c1 | (t2 < t)).astype(np.uint64)
+            s[:, i] = t2
+    out = np.empty((W, x.shape[0]), dtype=np.int32)
+    for j in range(W):
+        q, r = divmod(off[j], 64)
+        v = s[:, q] >> np.uint64(r)
+        if r + width[j] > 64:
+            v = v | (s[:, q + 1] << np.uint64(64 - r))
+        v = (v & np.uint64((1 << width[j]) - 1)).astype(np.int32)
+        out[j] = v - (1 << (width[j] - 1)) if j + 1 < W else v
+    return out
+
+
+def bucket_counts(canon, c, fixed=False):
+    """entries per bucket: (windows, 2^(c-1)) for a generic MSM; (1, 2^(c-1)) for a fixed-base job, whose windows share
+    one bucket set"""
+    d = np.abs(digits_np(canon, c))
+    nbw = 1 << (c - 1)
+    cnt = np.stack([np.bincount(row, minlength=nbw + 1)[1:nbw + 1] for row in d])
+    return cnt.sum(axis=0, keepdims=True) if fixed else cnt
+
+
+def tasks_and_max(counts, log_seg):
+    """(sum_b ceil(cnt_b / L), the largest bucket): what MsmTimings reports as `tasks` and `max_bucket`"""
+    L = 1 << log_seg
+    return int(((counts + (L - 1)) // L).sum()), int(counts.max())
+
+
+def max_top_digit(c):
+    """the largest digit of the top (unsigned) window for which digit << offset stays below r"""
+    return (R >> window_offsets(c)[-1]) - 1
+
+
+def place(c, window, bucket, negative=False):
+    """(scalar, {(window, bucket, negative): 1, ...}): a canonical scalar whose only entries are one in `bucket` of `window`
+    and -- for a negative digit -- the carry of 1 it sends into bucket 0 of the next window.  A value 0 < v < 2^(w-1) at a
+    window's offset is the digit v there and zero elsewhere; 2^(w-1) <= v < 2^w is the digit v - 2^w and a carry."""
+    width, off = window_plan(c), window_offsets(c)
+    w, top = width[window], len(width) - 1
+    d = bucket + 1
+    if not negative:
+        assert d <= ((1 << (w - 1)) - 1 if window < top else max_top_digit(c)), (c, window, bucket)
+        return d << off[window], Counter({(window, bucket, False): 1})
+    assert window < top and d <= 1 << (w - 1), (c, window, bucket)
+    return ((1 << w) - d) << off[window], Counter({(window, bucket, True): 1, (window + 1, 0, False): 1})
+
+
+def population_sizes(log_seg, fold):
+    """bucket populations at the edges of the task length L = 2^log_seg and of the merge loop's `fold`"""
+    L = 1 << log_seg
+    return sorted({1, L - 1, L, L + 1, 2 * L, fold * L, fold * L + 1, L * L + 1} - {0})
+
+
+def population_spots(c, log_G):
+    """where the populations go: the first bucket, the two around a chunk boundary of the scan reduction (2^log_G - 1,
+    2^log_G) and the last one (nbw - 1: only the digit -2^(c-1) reaches it) of window 0, the same in a middle window, and
+    the first, chunk-boundary and largest reachable bucket of the top (unsigned, c - 1 bits) window"""
+    width = window_plan(c)
+    nbw, G, top, mid = 1 << (c - 1), 1 << log_G, len(width) - 1, 2
+    assert width[0] == c and width[mid] == c and G < nbw - 1
+    # (one negative spot per window: its carries are then a population of their own in bucket 0 of the next window)
+    spots = [(0, 0, False), (0, G - 1, False), (0, G, False), (0, nbw - 1, True),
+             (mid, G - 1, False), (mid, G, False), (mid, nbw - 1, True), (mid, nbw - 2, False),
+             (top, 0, False), (top, min(G, max_top_digit(c) - 2), False), (top, max_top_digit(c) - 1, False)]
+    assert len(set(spots)) == len(spots)
+    return spots
+
+
+def populations(c, log_seg, fold=1, log_G=2, extra=()):
+    """(scalars as ints, the intended (window, bucket, negative) -> entries map): every size of `population_sizes` (and of
+    `extra`) in one spot of `population_spots`, the sizes walking through the spots so that the largest ones land in
+    different kinds of bucket from one (c, log_seg, fold) to the next"""
+    spots = population_spots(c, log_G)
+    sizes = population_sizes(log_seg, fold) + list(extra)
+    assert len(sizes) <= len(spots)
+    values, want = [], Counter()
+    start = (c + log_seg + fold) % len(spots)
+    for i, m in enumerate(sizes):
+        v, one = place(c, *spots[(start + i) % len(spots)])
+        values += [v] * m
+        for key, cnt in one.items():
+            want[key] += cnt * m
+    return values, want
+
+
+def interleave(values, seed):
+    """the same scalars in a fixed shuffled order: entries of one bucket come from bases all over the input"""
+    order = np.random.default_rng(seed).permutation(len(values))
+    return [values[i] for i in order]
+
+
+def counts_from_map(want, c, fixed=False):
+    """`bucket_counts` of an intended map"""
+    W, nbw = len(window_plan(c)), 1 << (c - 1)
+    cnt = np.zeros((1 if fixed else W, nbw), dtype=np.int64)
+    for (w, b, _), m in want.items():
+        cnt[0 if fixed else w, b] += m
+    return cnt
+
+
+# (log_seg, fold, log_G, extra sizes) of the populations the GPU tests use; 700 entries in tasks of 4 are four merge rounds
+POPULATIONS = [(2, 1, 2, (700,)), (2, 8, 2, (700,)), (4, 1, 2, ()), (4, 8, 3, ()), (2, 256, 2, ())]
+EDGE_WIDTHS = (6, 13)     # c - 1 = 5 and 12 bits: odd and even, so rows and columns of the 2-D reduction split differently
+_P, _Q = 0x1234567, 0x89ABCDE   # discrete logs of the edge cases' points P and Q
+
+
+def edge_cases(c):
+    """[(name, scalars as ints, discrete logs of the bases as ints; 0 = the identity point)]: inputs at which the reductions
+    add equal, opposite and identity values (xyzz29_add / xyzz29_add_quad treat each separately); none sums to the identity"""
+    width, off = window_plan(c), window_offsets(c)
+    nbw = 1 << (c - 1)
+    rng = np.random.default_rng(c)
+    cases = []
+    # every bucket of window 0 holds G (the last one: the digit -2^(c-1) on the base -G; its carry leaves -G in window 1)
+    cases.append(("same_point", list(range(1, nbw + 1)), [1] * (nbw - 1) + [R - 1]))
+    # neighbouring buckets hold P and -P: running sums return to the identity every other step
+    cases.append(("alternating", list(range(1, nbw)), [_P if v & 1 else R - _P for v in range(1, nbw)]))
+    every = sum(1 << o for o in off)
+    cases.append(("only_first", [1, 1, 1, every, every], [_P, _Q, 5, 7, _P]))
+    cases.append(("only_last", [nbw] * 5, [_P, _Q, 3, R - 9, 11]))
+    digits = [int(d) for d in rng.integers(1, nbw, size=200)]
+    cases.append(("one_window", [d << off[3] for d in digits], [int(x) for x in rng.integers(1, 1 << 62, size=200)]))
+    # window 0: a (-b P) + b (a P) = 0 over non-empty buckets; window 1 beside it does not cancel
+    pairs = [(1, 2), (3, nbw - 1), (nbw // 2, 5)]
+    vals, logs = [], []
+    for a, b in pairs:
+        vals += [a, b]
+        logs += [R - b * _P % R, a * _P % R]
+    cases.append(("cancel_beside", vals + [5 << off[1], 9 << off[1]], logs + [_Q, 77]))
+    # deep buckets (tasks of 4 and of 16) with the identity among their bases at entries k, k + L - 1, k + L
+    vals = [7] * 14 + [9 << off[2]] * 50
+    logs = [int(x) for x in rng.integers(1, 1 << 62, size=64)]
+    for i in (0, 3, 4, 14 + 0, 14 + 15, 14 + 16):
+        logs[i] = 0
+    cases.append(("identity_bases", vals, logs))
+    assert all(len(v) == len(l) and all(0 < x < R for x in v) and all(0 <= x < R for x in l) for _, v, l in cases)
+    return cases
+
+
+# ----------------------------------------------------------------------------- the back end's decision rules, restated
+# documented defaults (include/summa_gpu.h) of the parameters the rules below read
+BACKEND_DEFAULTS = {"window_bits": 0, "log_seg": 0, "acc_threads": 0, "acc_waves": 0, "acc_waves_fixed": 0, "quad": 1,
+                    "merge_quad_tasks": 0x7fffffff, "red2d": 1, "red2d_max_sets": 6, "red2d_fold": 8, "red2d_prefold": 1,
+                    "prefold_quad_buckets": 1 << 15, "red_lean": 1, "red_threads": 256, "log_red_chunk": 0}
+
+
+def _cfg(params):
+    unknown = [k for k in params if k.startswith("msm.") and k[4:] not in BACKEND_DEFAULTS]
+    assert not unknown or all(k in ("msm.fused_frontend", "msm.two_pass", "msm.acc_log") for k in unknown), unknown
+    return {**BACKEND_DEFAULTS, **{k[4:]: v for k, v in params.items() if k.startswith("msm.") and k[4:] in BACKEND_DEFAULTS}}
+
+
+def generic_window_bits(n, fused, params=None):
+    """MsmEngine::window_bits_for: msm.window_bits, or log2 n - 2 (- 4 in a fused job), within [4, 16]"""
+    wb = _cfg(params or {})["window_bits"]
+    return min(16, max(4, wb if wb else n.bit_length() - 1 - (4 if fused else 2)))
+
+
+def auto_log_seg(entries, NB):
+    """the task length a job picks when msm.log_seg is 0 (enqueue_front_fused_impl)"""
+    share, depth = 2 * entries // (256 * 4 * 64 * 4), entries // NB
+    if entries < 1 << 16:
+        return 2
+    if entries < 1 << 19:
+        return 3
+    if depth < 40 and entries >= 1 << 20:
+        need, r = depth + 8, 1
+        while r * r <= 64 * depth:
+            need, r = depth + 8 + r, r + 1
+        lg = 6
+        while lg < 8 and ((1 << lg) < share or (1 << lg) < need):
+            lg += 1
+        return lg
+    if entries <= 7 << 20:
+        return 4
+    if entries <= 12 << 20:
+        return 5
+    lg = 4
+    while lg < 8 and (1 << lg) < share:
+        lg += 1
+    return lg
+
+
+def _shape(n, M, fixed, c, cfg):
+    W1 = len(window_plan(c))
+    Wm = 1 if fixed else W1
+    nbw = 1 << (c - 1)
+    NB, entries = Wm * M * nbw, W1 * M * n
+    return W1, Wm, Wm * M, nbw, NB, entries, cfg["log_seg"] or auto_log_seg(entries, NB)
+
+
+def accumulate_threads(n, M, fixed, c, params, jobs_in_flight, cus):
+    """the grid rule of msm_accumulate (threads in all): a persistent launch of `waves` per SIMD on every CU, or one
+    workgroup per `acc_threads` tasks of the host's upper bound when that is smaller or `waves` is 8"""
+    cfg = _cfg(params)
+    _, _, _, _, NB, entries, log_L = _shape(n, M, fixed, c, cfg)
+    ntasks_ub = min(NB, entries) + (entries >> log_L)
+    at = cfg["acc_threads"] or 128
+    if fixed:
+        waves = cfg["acc_waves_fixed"] or (3 if ntasks_ub >= 3 * cus * 4 * 64 * 2 else 2)
+    else:
+        waves = cfg["acc_waves"] or (2 if jobs_in_flight >= 2 else 3)
+    wg_all = (ntasks_ub + at - 1) // at
+    return at * (wg_all if waves >= 8 else min(wg_all, cus * (waves * 4 * 64 // at)))
+
+
+def expected_backend(n, M, fixed, c, params, jobs_in_flight, max_bucket=1, tasks=None):
+    """What a job of M MSMs of n points at window width c dispatches after the sort (MsmEngine::enqueue_back_impl), with
+    `params` set and `jobs_in_flight` jobs of the process in flight (this one included): the kernel names in launch order,
+    the merge rounds for a largest bucket of `max_bucket` entries (`tasks`: the job's task count, for msm.merge_quad_tasks;
+    default the host's upper bound), and the shape of the reduction -- log_G / threads / blocks / T1 of the scan path,
+    per_win terms per window for the host tail."""
+    cfg = _cfg(params)
+    W1, Wm, W, nbw, NB, entries, log_L = _shape(n, M, fixed, c, cfg)
+    others = jobs_in_flight >= 2
+    quad = cfg["quad"] == 2 or (cfg["quad"] == 1 and NB <= 1 << 18)
+    if cfg["red2d"] and c >= 5:
+        red2d = 1 if (W <= cfg["red2d_max_sets"] and Wm <= 4) else (2 if cfg["red2d"] >= 2 else 0)
+    else:
+        red2d = 0
+    fold = cfg["red2d_fold"] if red2d else 1
+    out = {"c": c, "windows": W1, "sets": W, "log_seg": log_L, "quad": quad, "red2d": red2d, "fold": fold,
+           "log_G": None, "threads": None, "blocks": None, "T1": None}
+    kernels = ["msm_accumulate"]
+    L = 1 << log_L
+    items_ub = tasks if tasks is not None else min(NB, entries) + (entries >> log_L)
+    rounds, max_items = 0, (max_bucket + L - 1) >> log_L
+    while max_items > fold:
+        items_ub = min(NB, items_ub) + (items_ub >> log_L)
+        kernels.append("msm_merge<4>" if quad and items_ub <= cfg["merge_quad_tasks"] else "msm_merge<1>")
+        rounds += 1
+        max_items = (max_items + L - 1) >> log_L
+    out["merge_rounds"] = rounds
+    if red2d:
+        q = "<4>" if quad else "<1>"
+        if cfg["red2d_prefold"]:
+            kernels.append("msm_fold_buckets<4>" if quad and NB <= cfg["prefold_quad_buckets"] else "msm_fold_buckets<1>")
+            kernels.append("msm_reduce2d_lines_folded" + q)
+        else:
+            kernels.append("msm_reduce2d_lines" + q)
+        kernels.append("msm_reduce2d_bits" + q)
+        if red2d == 2:
+            kernels.append("msm_reduce2d_combine")
+        kernels.append("msm_export_points")
+        out["per_win"] = c if red2d == 1 else 1
+    else:
+        max_threads, max_blocks = (64, 64) if quad else (cfg["red_threads"], 256)
+        auto = (4 if (not quad and others) else 3) if nbw >= 1 << 14 else 2
+        log_G = min(cfg["log_red_chunk"] or auto, c - 1)
+        while (nbw >> log_G) > max_threads * max_blocks:
+            log_G += 1
+        items = nbw >> log_G
+        threads = min(max_threads, max(16, items))
+        blocks = (items + threads - 1) // threads
+        assert blocks <= max_blocks
+        if quad:
+            kernels.append("msm_reduce_buckets<4>")
+        elif cfg["red_lean"] == 2 or (cfg["red_lean"] == 1 and others):
+            kernels.append("msm_reduce_buckets_lean<1>")
+        else:
+            kernels.append("msm_reduce_buckets<1>")
+        T1 = None
+        if blocks > 1:
+            T1 = 16
+            while T1 < blocks:
+                T1 <<= 1
+            kernels.append("msm_reduce_items<4>" if quad or T1 <= 64 else "msm_reduce_items<1>")
+        kernels.append("msm_export_windows")
+        out.update(log_G=log_G, threads=threads, blocks=blocks, T1=T1, per_win=3)
+    out["kernels"] = kernels
+    return out

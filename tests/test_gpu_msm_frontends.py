@@ -11,6 +11,8 @@ import threading
 import numpy as np
 import pytest
 
+from msm_cases import _dev, _mont, case, make_pool, scalars
+
 pytestmark = pytest.mark.gpu
 
 N_POOL = (1 << 21) + 8
@@ -33,149 +35,10 @@ def O():
     return oracle
 
 
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _mont(canon):
-    """canonical 32-B little-endian values -> (device tensor, host copy), both Montgomery"""
-    from circuits_halo2_amd.arithmetic import fr_to_montgomery
-    t = fr_to_montgomery(_dev(canon))
-    return t, t.cpu().numpy()
-
-
 @pytest.fixture(scope="module")
 def pool(gpu):
     """N_POOL bases s_i * G on the device and their discrete logs s_i (Montgomery, host); cases take slices"""
-    from circuits_halo2_amd.arithmetic import g1_fixed_base_mul
-    from circuits_halo2_amd.utils import random_fr_canonical
-    s_dev, s_host = _mont(random_fr_canonical(0x5EED5, N_POOL))
-    return {"bases": g1_fixed_base_mul(s_dev), "s": s_host}
-
-
-# ----------------------------------------------------------------------------- scalars (canonical, numpy uint8 n x 32)
-R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
-_R_LIMBS = np.array([(R >> (64 * i)) & ((1 << 64) - 1) for i in range(4)], dtype=np.uint64)
-
-
-def _neg(canon):
-    """r - x limb-wise (0 stays 0), vectorised"""
-    x = np.ascontiguousarray(canon).view(np.uint64).reshape(-1, 4)
-    out = np.zeros_like(x)
-    borrow = np.zeros(x.shape[0], dtype=bool)
-    with np.errstate(over="ignore"):
-        for i in range(4):
-            a, b = _R_LIMBS[i], x[:, i]
-            out[:, i] = a - b - borrow.astype(np.uint64)
-            borrow = (b > a) | ((b == a) & borrow)
-    out[(x == 0).all(axis=1)] = 0
-    return out.view(np.uint8).reshape(-1)
-
-
-def _ints(values):
-    return np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in values), dtype=np.uint8).copy()
-
-
-def window_plan(c):
-    """widths of the windows (make_window_plan in csrc/msm.hip): W - 1 signed windows of c or c - 1 bits and an unsigned
-    top window of c - 1 bits, 254 bits in all"""
-    W = (255 + c - 1) // c
-    width = [c] * (W - 1) + [c - 1]
-    for k in range(W * c - 255):
-        width[W - 2 - k] -= 1
-    assert sum(width) == 254
-    return width
-
-
-def signed_digit_specials(c):
-    """scalars at the edges of the signed-digit recoding for window width c: every digit -2^(w-1) (the largest bucket,
-    negative), every digit 2^(w-1) - 1, every raw window value 2^(w-1) (the K offset itself), all-ones windows (carry
-    chains), the top window at its largest (r - 1, r - 2) and the single-window edges"""
-    width = window_plan(c)
-    off = [sum(width[:j]) for j in range(len(width))]
-    top = off[-1]
-    K = sum(1 << (off[j] + width[j] - 1) for j in range(len(width) - 1))
-    low_half = sum(((1 << (width[j] - 1)) - 1) << off[j] for j in range(len(width) - 1))
-    vals = [
-        (1 << top) - K,                          # every signed digit -2^(w-1), top digit 1
-        ((R - 1) >> top << top) - K,             # ... with the largest top digit that stays below r
-        low_half,                                # every signed digit 2^(w-1) - 1
-        low_half + (5 << top),
-        K,                                       # every raw window value 2^(w-1)
-        K - sum(1 << o for o in off[:-1]),       # every raw window value 2^(w-1) - 1
-        (1 << top) - 1,                          # every signed window all ones: a carry through all of them
-        (1 << 253) - 1,
-        R - 1, R - 2, (R - 1) // 2, R - (1 << top),
-        1 << (c - 1), (1 << (c - 1)) - 1, (1 << c) - 1, 1 << top,
-    ]
-    assert all(0 < v < R for v in vals)
-    return vals
-
-
-def scalars(dist, n, seed):
-    """canonical scalars of one distribution (pm_pairs / s_neg_s: see `case`)"""
-    from circuits_halo2_amd.utils import random_fr_canonical
-    rng = np.random.default_rng(seed)
-    out = np.zeros((n, 32), dtype=np.uint8)
-    if dist == "uniform":
-        return random_fr_canonical(seed, n)
-    if dist == "equal":                          # one bucket per window: one oversized bin per set
-        return np.tile(random_fr_canonical(seed, 1), n)
-    if dist == "byte":                           # the range-check column: window 0 only, its first coarse bins oversized
-        out[:, 0] = rng.integers(0, 256, size=n)
-    elif dist == "selector":                     # 0 / 1, about half ones
-        out[:, 0] = rng.random(n) < 0.5
-    elif dist == "sparse":                       # 99 % zero, the rest below 2^64: mostly empty bins
-        keep = rng.random(n) < 0.01
-        out[keep, :8] = rng.integers(0, 256, size=(int(keep.sum()), 8))
-    elif dist == "tiled32":                      # 32 distinct values: deep buckets, merge rounds
-        return np.tile(random_fr_canonical(seed, 32), (n + 31) // 32)[:32 * n].copy()
-    elif dist.startswith("signed"):              # signed-digit edges for window width int(dist[6:]), every 4th point uniform
-        sp = _ints(signed_digit_specials(int(dist[6:]))).reshape(-1, 32)
-        out[:] = sp[np.arange(n) % sp.shape[0]]
-        u = random_fr_canonical(seed, n).reshape(n, 32)
-        out[3::4] = u[3::4]
-    else:
-        raise ValueError(dist)
-    return out.reshape(-1)
-
-
-def case(O, pool, dist, n, seed, off=0):
-    """(scalars on the device, bases on the device, the expected point) for one MSM of `n` points.
-    pm_pairs: bases P, -P alternating with equal scalars in pairs (they cancel inside one bucket); s_neg_s: one repeated base G
-    with scalars s, r - s alternating (their total is the identity).  Both end in 8 unpaired uniform points so that the
-    answer is not the identity (a kernel that lost every point would not pass)."""
-    import torch
-    from circuits_halo2_amd.arithmetic import g1_fixed_base_mul
-    from circuits_halo2_amd.utils import random_fr_canonical
-    if dist == "pm_pairs":
-        assert n % 2 == 0
-        half = random_fr_canonical(seed, n // 2).reshape(-1, 32)
-        logs = np.empty((n, 32), dtype=np.uint8)
-        logs[0::2], logs[1::2] = half, _neg(half).reshape(-1, 32)
-        logs[-8:] = random_fr_canonical(seed + 1, 8).reshape(8, 32)
-        s_dev, s_host = _mont(logs.reshape(-1))
-        bases = g1_fixed_base_mul(s_dev)
-        k = np.repeat(random_fr_canonical(seed + 2, n // 2).reshape(-1, 32), 2, axis=0)
-        k[-8:] = random_fr_canonical(seed + 3, 8).reshape(8, 32)
-        k_dev, k_host = _mont(k.reshape(-1))
-    elif dist == "s_neg_s":
-        assert n % 2 == 0
-        half = random_fr_canonical(seed, n // 2).reshape(-1, 32)
-        k = np.empty((n, 32), dtype=np.uint8)
-        k[0::2], k[1::2] = half, _neg(half).reshape(-1, 32)
-        k[-8:] = random_fr_canonical(seed + 1, 8).reshape(8, 32)
-        k_dev, k_host = _mont(k.reshape(-1))
-        bases = _dev(np.tile(O.g1_generator(), n))
-        s_host = O.fr_to_mont(np.tile(_ints([1]), n))
-    else:
-        k_dev, k_host = _mont(scalars(dist, n, seed))
-        bases = pool["bases"][64 * off:64 * (off + n)]
-        s_host = pool["s"][32 * off:32 * (off + n)]
-    want = O.g1_mul(O.g1_generator(), O.fr_dot(k_host, s_host))
-    torch.cuda.synchronize()
-    return k_dev, bases, want
+    return make_pool(N_POOL)
 
 
 # ----------------------------------------------------------------------------- 1: each mode against exact answers
