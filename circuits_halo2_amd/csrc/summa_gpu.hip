@@ -117,6 +117,7 @@ constexpr int kNoLimit = 0x7fffffff;
 // side_prio is device-wide, not per lane: wave priority 3 for every kernel but msm_accumulate (side_prio.cuh)
 int set_side_prio(int on) {
   hipError_t e = msm_set_side_prio(on);
+  if (e == hipSuccess) e = msm_tiny_set_side_prio(on);
   if (e == hipSuccess) e = ntt_set_side_prio(on);
   if (e == hipSuccess) e = poly_set_side_prio(on);
   if (e == hipSuccess) e = quotient_set_side_prio(on);

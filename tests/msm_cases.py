@@ -2,9 +2,10 @@
 without a GPU by test_msm_cases_cpu.py; a plain helper module like quotient_witness.py and mst_assignment.py.
 
 Three parts: the scalar distributions and known-answer cases of the front-end tests; the signed-digit recoding of
-csrc/msm.hip restated in Python (`recode`, `digits_np`) with a builder that puts a prescribed number of entries into chosen
-buckets (`place`, `populations`); and the decision rules of MsmEngine::enqueue_back_impl restated as `expected_backend` /
-`accumulate_threads` -- whoever moves a threshold in msm.hip updates the restatement here."""
+csrc/msm_sort.cuh restated in Python (`recode`, `digits_np`) with a builder that puts a prescribed number of entries into chosen
+buckets (`place`, `populations`); and the decision rules of csrc/msm_plan.h (plan_front, plan_accumulate, plan_reduce) restated
+as `expected_backend` / `accumulate_threads` -- test_msm_cases_cpu.py runs the C++ rules themselves (tests/cpp/msm_plan_check.cpp)
+against the restatement, so whoever moves a threshold in msm_plan.h finds out there."""
 from collections import Counter
 
 import numpy as np
@@ -53,7 +54,7 @@ def _ints(values):
 
 
 def window_plan(c):
-    """widths of the windows (make_window_plan in csrc/msm.hip): W - 1 signed windows of c or c - 1 bits and an unsigned
+    """widths of the windows (make_window_plan in csrc/msm_plan.h): W - 1 signed windows of c or c - 1 bits and an unsigned
     top window of c - 1 bits, 254 bits in all"""
     W = (255 + c - 1) // c
     width = [c] * (W - 1) + [c - 1]
@@ -352,13 +353,13 @@ def _cfg(params):
 
 
 def generic_window_bits(n, fused, params=None):
-    """MsmEngine::window_bits_for: msm.window_bits, or log2 n - 2 (- 4 in a fused job), within [4, 16]"""
+    """window_bits_for (csrc/msm_plan.h): msm.window_bits, or log2 n - 2 (- 4 in a fused job), within [4, 16]"""
     wb = _cfg(params or {})["window_bits"]
     return min(16, max(4, wb if wb else n.bit_length() - 1 - (4 if fused else 2)))
 
 
 def auto_log_seg(entries, NB):
-    """the task length a job picks when msm.log_seg is 0 (enqueue_front_fused_impl)"""
+    """the task length a job picks when msm.log_seg is 0 (auto_log_L in csrc/msm_plan.h)"""
     share, depth = 2 * entries // (256 * 4 * 64 * 4), entries // NB
     if entries < 1 << 16:
         return 2
@@ -387,11 +388,12 @@ def _shape(n, M, fixed, c, cfg):
     Wm = 1 if fixed else W1
     nbw = 1 << (c - 1)
     NB, entries = Wm * M * nbw, W1 * M * n
+    assert NB <= 1 << 21 and entries < 1 << 32 and n < 1 << 31 and M <= 64     # the job limits of plan_front
     return W1, Wm, Wm * M, nbw, NB, entries, cfg["log_seg"] or auto_log_seg(entries, NB)
 
 
 def accumulate_threads(n, M, fixed, c, params, jobs_in_flight, cus):
-    """the grid rule of msm_accumulate (threads in all): a persistent launch of `waves` per SIMD on every CU, or one
+    """the grid rule of msm_accumulate (plan_accumulate in csrc/msm_plan.h; threads in all): a persistent launch of `waves` per SIMD on every CU, or one
     workgroup per `acc_threads` tasks of the host's upper bound when that is smaller or `waves` is 8"""
     cfg = _cfg(params)
     _, _, _, _, NB, entries, log_L = _shape(n, M, fixed, c, cfg)
@@ -406,7 +408,7 @@ def accumulate_threads(n, M, fixed, c, params, jobs_in_flight, cus):
 
 
 def expected_backend(n, M, fixed, c, params, jobs_in_flight, max_bucket=1, tasks=None):
-    """What a job of M MSMs of n points at window width c dispatches after the sort (MsmEngine::enqueue_back_impl), with
+    """What a job of M MSMs of n points at window width c dispatches after the sort (plan_reduce in csrc/msm_plan.h), with
     `params` set and `jobs_in_flight` jobs of the process in flight (this one included): the kernel names in launch order,
     the merge rounds for a largest bucket of `max_bucket` entries (`tasks`: the job's task count, for msm.merge_quad_tasks;
     default the host's upper bound), and the shape of the reduction -- log_G / threads / blocks / T1 of the scan path,

@@ -1,9 +1,9 @@
-"""GPU tests of the MSM back end (csrc/msm.hip), all through the C ABI: msm_accumulate at every workgroup size, wave count and
+"""GPU tests of the MSM back end (csrc/msm.hip, msm_accumulate.cuh, msm_reduce.cuh), all through the C ABI: msm_accumulate at every workgroup size, wave count and
 task length, the merge rounds, and every bucket-reduction path -- the scan reduction (msm_reduce_buckets<1> / <4> / _lean<1>,
 msm_reduce_items<1> / <4>), the 2-D reduction with the powers of two on the host (msm_fold_buckets, msm_reduce2d_lines_folded,
 msm_reduce2d_lines, msm_reduce2d_bits) and on the device (msm_reduce2d_combine) -- with the host tail behind each, forced by
 runtime parameters where the defaults never go.  Each case says which path it is for; `expected_backend` (tests/msm_cases.py,
-the decision rules of MsmEngine::enqueue_back_impl restated) must agree before the MSM runs.
+the decision rules of csrc/msm_plan.h restated) must agree before the MSM runs.
 
 Every expected point comes from outside the library's MSM: the bases are s_i * G with known s_i, so an MSM must give
 <k, s> * G (oracle dot product and scalar multiplication); a commitment against ParamsKZG.setup(k, tau) must give a(tau) * G.

@@ -1,4 +1,4 @@
-"""GPU tests of the MSM sort front ends (csrc/msm.hip), all through the C ABI: the single-pass sort, the two-pass sort with
+"""GPU tests of the MSM sort front ends (csrc/msm.hip, msm_sort.cuh), all through the C ABI: the single-pass sort, the two-pass sort with
 separate scans ("legacy", msm.fused_frontend = 0 or another job in flight) and the two-pass sort whose scans and task
 histogram ride on its own kernels (msm.fused_frontend = 1 with the device to itself, 2 always), at the sizes they run at in
 production, under skewed scalars, with jobs in flight beside them and back to back on one engine.

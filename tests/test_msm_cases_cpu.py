@@ -1,7 +1,10 @@
 """CPU checks of tests/msm_cases.py, the builders behind the MSM GPU tests: the signed-digit recoding restated from
-msm_digits / make_window_plan (csrc/msm.hip), the buckets with prescribed populations that test_gpu_msm_backends.py feeds
+msm_digits / make_window_plan (csrc/msm_sort.cuh, csrc/msm_plan.h), the buckets with prescribed populations that test_gpu_msm_backends.py feeds
 to the accumulation, the merge rounds and the reductions, and the expected points computed from dot products.  A case that
 silently stopped producing L + 1 entries in its bucket fails here, without a GPU."""
+import itertools
+import os
+import subprocess
 from collections import Counter
 
 import numpy as np
@@ -159,3 +162,86 @@ def test_backend_defaults_are_the_documented_ones():
     from param_doc import documented_defaults
     doc = documented_defaults()
     assert {f"msm.{k}": v for k, v in mc.BACKEND_DEFAULTS.items()} == {f"msm.{k}": doc[f"msm.{k}"] for k in mc.BACKEND_DEFAULTS}
+
+
+# ----------------------------------------------------------------------------- the restated rules against the real ones
+def _plan_param_sets():
+    """the msm.* settings the GPU back-end tests run under (test_gpu_msm_backends.py: SCAN_PATHS, DEVICE_2D, HOST_2D, _GRID and
+    the forced shapes of the scan reduction, the task length, the merge rounds and the fold), without the "msm." prefix"""
+    scan = [{"red2d": 0, "quad": 0, "red_lean": 0}, {"red2d": 0, "quad": 2}, {"red2d": 0, "quad": 0, "red_lean": 2}]
+    dev2d = [{"red2d": 2, "red2d_prefold": pf, "quad": q} for pf in (1, 0) for q in (0, 2)]
+    host2d = [{"red2d": 1, "red2d_prefold": pf, "quad": q} for pf in (1, 0) for q in (0, 2)]
+    sets = [{}] + scan + dev2d + host2d
+    sets += [{"red2d": 0, "quad": 0, "red_threads": 64}, {"red2d": 0, "quad": 0, "red_threads": 64, "log_red_chunk": 1},
+             {"red2d": 0, "log_red_chunk": 1}, {"red2d": 0, "log_red_chunk": 8}, {"red2d": 0, "quad": 2, "log_red_chunk": 1}]
+    sets += [{"log_seg": 2}, {"log_seg": 2, "merge_quad_tasks": 0}, {"merge_quad_tasks": 0}]
+    sets += [{"acc_threads": at, "acc_waves": w} for at in (64, 128, 256) for w in (1, 2, 3, 7, 8)]
+    sets += [{"acc_waves_fixed": 2}, {"acc_waves_fixed": 3}]
+    sets += [{"red2d": 2, "log_seg": 2, "red2d_fold": 1}, {"red2d": 2, "log_seg": 2, "red2d_fold": 8}, {"red2d_fold": 1}]
+    return sets
+
+
+def _fmt(v):
+    return "-" if v is None else str(int(v))
+
+
+def _restated(n, M, fixed, c, params, jobs, largest, tasks):
+    """everything but the grid of one line of msm_plan_check, from the restatement in msm_cases.py; None: not a valid job"""
+    p = {f"msm.{k}": v for k, v in params.items()}
+    cc = c if fixed else mc.generic_window_bits(n, M > 1, {**p, **({"msm.window_bits": c} if c else {})})
+    try:
+        e = mc.expected_backend(n, M, fixed, cc, p, jobs, max_bucket=largest, tasks=tasks or None)
+    except AssertionError:
+        return None
+    width = mc.window_plan(cc)
+    W1, sets = len(width), (1 if fixed else len(width)) * M
+    log_seg = params.get("log_seg") or mc.auto_log_seg(W1 * M * n, sets << (cc - 1))
+    assert (e["c"], e["windows"], e["sets"], e["log_seg"]) == (cc, W1, sets, log_seg)
+    return cc, (f"c={cc} windows={W1} widths={','.join(map(str, width))} sets={sets} log_seg={log_seg} quad={int(e['quad'])} "
+                f"red2d={e['red2d']} fold={e['fold']} log_G={_fmt(e['log_G'])} threads={_fmt(e['threads'])} blocks={_fmt(e['blocks'])} "
+                f"T1={_fmt(e['T1'])} merge_rounds={e['merge_rounds']} per_win={e['per_win']} kernels={','.join(e['kernels'])}")
+
+
+def test_restated_rules_are_the_engines_own(tmp_path):
+    """tests/cpp/msm_plan_check.cpp runs the engine's planning (csrc/msm_plan.h, no HIP) on every job of a grid; `expected_backend`,
+    `accumulate_threads`, `auto_log_seg`, `generic_window_bits` and `window_plan` must say the same, field by field: the
+    GPU tests name the kernel a case exercises on the strength of these restatements.  A job the engine rejects (more than
+    2^21 buckets: generic jobs of 6, 7 or 9 MSMs at c = 16) must be one the restatement rejects, and the other way round; at
+    least 95 % of the grid are valid jobs.  The C++ rules are the reference: a difference is fixed in msm_cases.py."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "msm_plan_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(root, "circuits_halo2_amd", "csrc"),
+                           os.path.join(root, "tests", "cpp", "msm_plan_check.cpp"), "-o", exe])
+    shapes = [(n, M, fixed, c) for n in (1 << 10, 1 << 12, 1 << 15, 1 << 17, 1 << 20) for M in (1, 4, 6, 7, 9)
+              for fixed in (False, True) for c in (0, 4, 5, 6, 10, 11, 12, 13, 16) if c or not fixed]
+    cases = [(n, M, fixed, c, params, jobs, cus, largest, 0)
+             for (n, M, fixed, c), params, jobs in itertools.product(shapes, _plan_param_sets(), (1, 2))
+             for cus in (256, 64) for largest in (1, 33, 700, 70000)]
+    # the job's exact task count, which msm.merge_quad_tasks is compared with (the grid above leaves it at the upper bound)
+    cases += [(1 << 12, 1, False, 13, {"red2d": 0, "log_seg": 2, "merge_quad_tasks": mqt}, 1, 256, 700, tasks)
+              for mqt in (0, 1000, 1001, 0x7fffffff) for tasks in (900, 1300, 4000)]
+    text = "".join(f"{n} {M} {int(fixed)} {c} {jobs} {cus} {largest} {tasks} " + " ".join(f"{k}={v}" for k, v in params.items()) + "\n"
+                   for n, M, fixed, c, params, jobs, cus, largest, tasks in cases)
+    got = subprocess.run([exe], input=text, capture_output=True, text=True, check=True).stdout.split("\n")[:-1]
+    assert len(got) == len(cases)
+    backend, grid = {}, {}
+    valid = 0
+    for line, (n, M, fixed, c, params, jobs, cus, largest, tasks) in zip(got, cases):
+        pk = tuple(params.items())
+        key = (n, M, fixed, c, pk, jobs, largest, tasks)
+        if key not in backend:
+            backend[key] = _restated(n, M, fixed, c, params, jobs, largest, tasks)
+        if backend[key] is None:
+            assert line == "invalid", (key, line)
+            continue
+        cc, want = backend[key]
+        gkey = (n, M, fixed, cc, pk, jobs, cus)
+        if gkey not in grid:
+            grid[gkey] = mc.accumulate_threads(n, M, fixed, cc, {f"msm.{k}": v for k, v in params.items()}, jobs, cus)
+        want = f"{want} acc_threads={grid[gkey]}"
+        if line != want:
+            diff = [(a, b) for a, b in zip(line.split(" "), want.split(" ")) if a != b]
+            raise AssertionError(f"n={n} M={M} fixed={fixed} c={c} {params} jobs={jobs} cus={cus} largest={largest} tasks={tasks}: "
+                                 f"engine / restatement {diff or (line, want)}")
+        valid += 1
+    assert valid >= 0.95 * len(cases), (valid, len(cases))
