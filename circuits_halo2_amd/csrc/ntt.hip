@@ -215,24 +215,6 @@ hipError_t NttEngine::local_twiddles(const words8& omega_r, uint32_t log_r, hipS
   return hipSuccess;
 }
 
-// choose the pass factorisation for a 2^log_n transform
-static void factor(uint32_t log_n, uint32_t max_single, uint32_t max_multi, int* npass, uint32_t l[3]) {
-  l[0] = l[1] = l[2] = 0;
-  if (log_n <= max_single) {
-    *npass = 1;
-    l[0] = log_n;
-  } else if (log_n <= 2 * max_multi) {
-    *npass = 2;
-    l[0] = (log_n + 1) / 2;  // n1 (second pass DFT length)
-    l[1] = log_n - l[0];     // n2 (first pass DFT length)
-  } else {
-    *npass = 3;
-    l[0] = (log_n + 2) / 3;
-    l[1] = (log_n - l[0] + 1) / 2;
-    l[2] = log_n - l[0] - l[1];
-  }
-}
-
 hipError_t NttEngine::get_plan(uint32_t log_n, const words8& omega, const words8* scale, hipStream_t stream,
                                const NttPlan** out) {
   for (auto& pl : plans_) {
@@ -247,7 +229,9 @@ hipError_t NttEngine::get_plan(uint32_t log_n, const words8& omega, const words8
   pl.omega = omega;
   pl.has_scale = scale != nullptr;
   if (scale) pl.scale = *scale;
-  factor(log_n, cfg_.max_single_log, cfg_.max_multi_log, &pl.npass, pl.l);
+  const NttFactors f = ntt_factor(cfg_, log_n);
+  pl.npass = f.npass;
+  std::copy(f.l, f.l + 3, pl.l);
   const size_t n = (size_t)1 << log_n;
   hipError_t err;
   // omega_R for a length-R sub-transform is omega^(n/R): square omega (log_n - log_r) times
@@ -296,38 +280,20 @@ hipError_t NttEngine::get_plan(uint32_t log_n, const words8& omega, const words8
   return hipSuccess;
 }
 
-
-// leading stages of a zero-padded FIRST pass that can be skipped: rows r >= in_len >> log_b are zero
-static uint32_t skippable_stages(const PassArgs& a, uint32_t log_n) {
-  if (a.kind != 1 || a.in_len == 0 || (a.in_len & (a.in_len - 1)) || a.in_len >= (1u << log_n)) return 0;
-  const uint32_t rows = a.in_len >> a.log_b;   // nonzero rows of every column (in_len is a power of two)
-  if (rows == 0 || rows >= (1u << a.log_r)) return 0;
-  uint32_t z = 0;
-  while ((1u << z) < rows) z++;
-  return a.log_r - z;
-}
-
-static hipError_t launch_pass(const NttConfig& cfg, PassArgs& a, uint32_t log_n, hipStream_t stream) {
-  a.skip = skippable_stages(a, log_n);
-  // tile width: as many contiguous columns as the LDS budget allows
-  const bool big = (a.nbatch >= cfg.batch_min || log_n >= cfg.big_log) && cfg.big_tile_log;
-  const uint32_t tile_log = big ? cfg.big_tile_log : cfg.tile_log, max_threads = big ? cfg.big_threads : cfg.threads;
-  uint32_t log_e = std::min<uint32_t>(tile_log, log_n);
-  if (log_e < a.log_r) log_e = a.log_r;
-  uint32_t log_t = std::min<uint32_t>(log_e - a.log_r, a.log_b);
-  a.log_t = log_t;
-  size_t E = (size_t)1 << (a.log_r + log_t);
-  size_t lds = (E + ((size_t)1 << a.log_r) / 2 + 8) * 36 + 64;
-  // two stages per sweep: measured (profiles/r05_sweeps/ntt_radix4.txt) 3-6 % faster for the throughput shapes -- lone transforms
-  // of 2^20 points and more, the batched launches of a proof (25 coset blocks: 323 -> 310 us) --, 25 % slower for a lone 2^17
-  // transform (two launches at their latency floor, which want many threads)
-  const bool want_r4 = cfg.radix4 == 2 || (cfg.radix4 == 1 && big);
-  a.radix4 = want_r4 && a.log_r - a.skip >= 2 ? 1u : 0u;
-  // one butterfly (radix-4 sweeps: one group of four elements) per thread per sweep
-  uint32_t threads = (uint32_t)std::min<size_t>(a.radix4 ? std::min<uint32_t>(max_threads, 512u) : max_threads, std::max<size_t>(64, E / (a.radix4 ? 4 : 2)));
-  uint32_t tiles = 1u << (log_n - a.log_r - log_t);
-  if (a.radix4) hipLaunchKernelGGL(ntt_pass_r4, dim3(tiles, a.nbatch ? a.nbatch : 1), dim3(threads), lds, stream, a);
-  else hipLaunchKernelGGL(ntt_pass, dim3(tiles, a.nbatch ? a.nbatch : 1), dim3(threads), lds, stream, a);
+// one launch of pass `i` of the plan: geometry, tile and workgroup from ntt_plan.h; the caller has filled the buffers, in_len and
+// the pre / post factors
+static hipError_t launch_pass(const NttConfig& cfg, const NttPlan& pl, int i, PassArgs& a, hipStream_t stream) {
+  const NttPassGeom g = ntt_pass_geom(NttFactors{pl.npass, {pl.l[0], pl.l[1], pl.l[2]}}, i);
+  a.tw_local = pl.tw_local[g.tw_local];
+  a.tw_pass = g.tw_pass < 0 ? nullptr : pl.tw_pass[g.tw_pass];
+  a.log_r = g.log_r; a.log_b = g.log_b; a.kind = g.kind; a.sig_lo = g.sig_lo; a.sig_hi = g.sig_hi; a.fold29 = g.fold29;
+  const NttPassShape s = ntt_pass_shape(cfg, g, pl.log_n, a.in_len, a.nbatch);
+  if (s.lds_bytes > NTT_LDS_BUDGET || s.threads > (s.radix4 ? NTT_MAX_THREADS_R4 : NTT_MAX_THREADS)) return hipErrorInvalidConfiguration;
+  a.skip = s.skip;
+  a.log_t = s.log_t;
+  a.radix4 = s.radix4;
+  if (s.radix4) hipLaunchKernelGGL(ntt_pass_r4, dim3(s.grid_x, s.grid_y), dim3(s.threads), s.lds_bytes, stream, a);
+  else hipLaunchKernelGGL(ntt_pass, dim3(s.grid_x, s.grid_y), dim3(s.threads), s.lds_bytes, stream, a);
   return hipGetLastError();
 }
 
@@ -339,7 +305,7 @@ hipError_t NttEngine::transform_batch(fp_words* const* a, uint32_t count, fp_wor
   if (pre_tab && (!src || src_len < ((size_t)1 << log_n))) return hipErrorInvalidValue;   // (the zero-padded load path does not take a table)
   if (count > NTT_BATCH_MAX || log_n == 0) return hipErrorInvalidValue;
   const NttPlan* pl;
-  const bool fold_scale = scale && log_n > cfg_.max_single_log;
+  const bool fold_scale = ntt_scale_in_table(ntt_factor(cfg_, log_n), scale != nullptr, false);
   hipError_t err = get_plan(log_n, omega, fold_scale ? scale : nullptr, stream, &pl);
   if (err != hipSuccess) return err;
   const size_t n = (size_t)1 << log_n;
@@ -375,44 +341,21 @@ hipError_t NttEngine::transform_batch(fp_words* const* a, uint32_t count, fp_wor
       for (int i = 0; i < 3; i++) std::memcpy(p.post[i], scale->l, 32);
     }
   };
-  if (pl->npass == 1) {
-    io(DATA, DATA);
-    p.tw_local = pl->tw_local[0]; p.tw_pass = nullptr; p.log_r = log_n; p.log_b = 0; p.kind = 0;
-    last_scale(true);
-    return launch_pass(cfg_, p, log_n, stream);
-  }
-  if (pl->npass == 2) {
-    const uint32_t l1 = pl->l[0], l2 = pl->l[1];
-    io(DATA, MID);
-    p.tw_local = pl->tw_local[1]; p.tw_pass = pl->tw_pass[0]; p.log_r = l2; p.log_b = l1; p.kind = 1; p.sig_lo = l1; p.sig_hi = 0;
-    last_scale(false);
-    err = launch_pass(cfg_, p, log_n, stream);
+  // one pass: in place; several: the first writes the intermediate, the last the data, a middle one stays in the intermediate
+  for (int i = 0; i < pl->npass; i++) {
+    const bool last = i == pl->npass - 1;
+    io(i == 0 ? DATA : MID, last ? DATA : MID);
+    last_scale(last);
+    err = launch_pass(cfg_, *pl, i, p, stream);
     if (err != hipSuccess) return err;
-    io(MID, DATA);
-    p.tw_local = pl->tw_local[0]; p.tw_pass = nullptr; p.log_r = l1; p.log_b = l2; p.kind = 0; p.fold29 = 1;
-    last_scale(true);
-    return launch_pass(cfg_, p, log_n, stream);
   }
-  const uint32_t l1 = pl->l[0], l2 = pl->l[1], l3 = pl->l[2];
-  io(DATA, MID);
-  p.tw_local = pl->tw_local[2]; p.tw_pass = pl->tw_pass[0]; p.log_r = l3; p.log_b = l1 + l2; p.kind = 1; p.sig_lo = l1; p.sig_hi = l2;
-  last_scale(false);
-  err = launch_pass(cfg_, p, log_n, stream);
-  if (err != hipSuccess) return err;
-  io(MID, MID);
-  p.tw_local = pl->tw_local[1]; p.tw_pass = pl->tw_pass[1]; p.log_r = l2; p.log_b = l3; p.kind = 0;
-  err = launch_pass(cfg_, p, log_n, stream);
-  if (err != hipSuccess) return err;
-  io(MID, DATA);
-  p.tw_local = pl->tw_local[0]; p.tw_pass = nullptr; p.log_r = l1; p.log_b = l2 + l3; p.kind = 0; p.fold29 = 1;
-  last_scale(true);
-  return launch_pass(cfg_, p, log_n, stream);
+  return hipSuccess;
 }
 
 hipError_t NttEngine::init() {
   // allow the large dynamic-LDS tiles (up to the full 160 KiB of a CU)
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ntt_pass), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(ntt_pass_r4), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ntt_pass), hipFuncAttributeMaxDynamicSharedMemorySize, (int)NTT_LDS_BUDGET);
+  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(ntt_pass_r4), hipFuncAttributeMaxDynamicSharedMemorySize, (int)NTT_LDS_BUDGET);
   return e;
 }
 
@@ -421,7 +364,7 @@ hipError_t NttEngine::transform(const fp_words* in, size_t in_len, fp_words* out
                                 hipStream_t stream) {
   const NttPlan* pl;
   // a plain scale is folded into the first inter-pass twiddle table when there is one
-  bool fold_scale = scale && !post3 && log_n > cfg_.max_single_log;
+  const bool fold_scale = ntt_scale_in_table(ntt_factor(cfg_, log_n), scale != nullptr, post3 != nullptr);
   hipError_t err = get_plan(log_n, omega, fold_scale ? scale : nullptr, stream, &pl);
   if (err != hipSuccess) return err;
   if (log_n == 0) {
@@ -445,49 +388,19 @@ hipError_t NttEngine::transform(const fp_words* in, size_t in_len, fp_words* out
       for (int i = 0; i < 3; i++) std::memcpy(a.post[i], scale->l, 32);
     }
   };
-  const bool inplace = (in == out);
-  if (pl->npass == 1) {
-    a.in = in; a.out = out; a.tw_local = pl->tw_local[0]; a.tw_pass = nullptr;
-    a.log_r = log_n; a.log_b = 0; a.kind = 0; a.in_len = (uint32_t)std::min<size_t>(in_len, (size_t)1 << log_n);
-    set_prepost(true, true);
-    return launch_pass(cfg_, a, log_n, stream);
-  }
-  if (pl->npass == 2) {
-    const uint32_t l1 = pl->l[0], l2 = pl->l[1];
-    fp_words* mid = inplace ? scratch : out;
-    // pass X: DFT over i2 (length n2, stride n1), columns i1 contiguous
-    a.in = in; a.out = mid; a.tw_local = pl->tw_local[1]; a.tw_pass = pl->tw_pass[0];
-    a.log_r = l2; a.log_b = l1; a.kind = 1; a.sig_lo = l1; a.sig_hi = 0;
-    a.in_len = (uint32_t)std::min<size_t>(in_len, (size_t)1 << log_n);
-    set_prepost(true, false);
-    err = launch_pass(cfg_, a, log_n, stream);
+  // multi-pass plans: the first pass writes the intermediate (`scratch` for an in-place call, else `out`), a middle pass works
+  // in place there, the last one writes `out`
+  fp_words* mid = in == out ? scratch : out;
+  for (int i = 0; i < pl->npass; i++) {
+    const bool first = i == 0, last = i == pl->npass - 1;
+    a.in = first ? in : mid;
+    a.out = last ? out : mid;
+    a.in_len = first ? (uint32_t)std::min<size_t>(in_len, (size_t)1 << log_n) : 1u << log_n;
+    set_prepost(first, last);
+    err = launch_pass(cfg_, *pl, i, a, stream);
     if (err != hipSuccess) return err;
-    // pass Y: DFT over i1 (length n1, stride n2), columns j2 contiguous
-    a.in = mid; a.out = out; a.tw_local = pl->tw_local[0]; a.tw_pass = nullptr;
-    a.log_r = l1; a.log_b = l2; a.kind = 0; a.in_len = 1u << log_n; a.fold29 = 1;
-    set_prepost(false, true);
-    return launch_pass(cfg_, a, log_n, stream);
   }
-  const uint32_t l1 = pl->l[0], l2 = pl->l[1], l3 = pl->l[2];
-  fp_words* mid = inplace ? scratch : out;
-  // pass A: DFT over i3 (length n3, stride n1 n2); writes j3 + n3*(i2 + n2*i1)
-  a.in = in; a.out = mid; a.tw_local = pl->tw_local[2]; a.tw_pass = pl->tw_pass[0];
-  a.log_r = l3; a.log_b = l1 + l2; a.kind = 1; a.sig_lo = l1; a.sig_hi = l2;
-  a.in_len = (uint32_t)std::min<size_t>(in_len, (size_t)1 << log_n);
-  set_prepost(true, false);
-  err = launch_pass(cfg_, a, log_n, stream);
-  if (err != hipSuccess) return err;
-  // pass B: DFT over i2 (length n2, stride n3) for each i1, in place
-  a.in = mid; a.out = mid; a.tw_local = pl->tw_local[1]; a.tw_pass = pl->tw_pass[1];
-  a.log_r = l2; a.log_b = l3; a.kind = 0; a.in_len = 1u << log_n;
-  set_prepost(false, false);
-  err = launch_pass(cfg_, a, log_n, stream);
-  if (err != hipSuccess) return err;
-  // pass C: DFT over i1 (length n1, stride n2 n3)
-  a.in = mid; a.out = out; a.tw_local = pl->tw_local[0]; a.tw_pass = nullptr;
-  a.log_r = l1; a.log_b = l2 + l3; a.kind = 0; a.fold29 = 1;
-  set_prepost(false, true);
-  return launch_pass(cfg_, a, log_n, stream);
+  return hipSuccess;
 }
 
 hipError_t ntt_scale(fp_words* a, const words8& s, size_t n, hipStream_t stream) {

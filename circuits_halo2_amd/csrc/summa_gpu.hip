@@ -184,10 +184,10 @@ constexpr ParamRow kParams[] = {
     // 0: by size, 1: always, 2: never (NttConfig::radix4 counts the other way round: 1, 2, 0)
     {"ntt.radix4", Scope::lane, 0, [](int v) { return v == 1 || v == 2 ? v : 0; },
      [](Context& c, int v) { c.ntt.config().radix4 = v == 1 ? 2u : v == 2 ? 0u : 1u; }, nullptr},
-    // the plans are cut by these two: the cached ones go
-    {"ntt.max_single_log", Scope::lane, (int)NttConfig{}.max_single_log, in_range<1, 12>,
+    // the plans are cut by these two: the cached ones go.  No pass longer than 2^NTT_MAX_PASS_LOG points: its tile would not fit the LDS
+    {"ntt.max_single_log", Scope::lane, (int)NttConfig{}.max_single_log, in_range<1, (int)NTT_MAX_PASS_LOG>,
      [](Context& c, int v) { c.ntt.config().max_single_log = (uint32_t)v; c.ntt.clear(); }, nullptr},
-    {"ntt.max_multi_log", Scope::lane, (int)NttConfig{}.max_multi_log, in_range<4, 12>,
+    {"ntt.max_multi_log", Scope::lane, (int)NttConfig{}.max_multi_log, in_range<4, (int)NTT_MAX_PASS_LOG>,
      [](Context& c, int v) { c.ntt.config().max_multi_log = (uint32_t)v; c.ntt.clear(); }, nullptr},
 };
 #undef MSM_ROW

@@ -579,15 +579,15 @@ int sg_commit_dev_timed(uint64_t srs_handle, int basis, const void* d_scalars, s
  *   "msm.quad"                   0..2, default 1: quad-cooperative point additions in merge and reduction -- never / auto / always
  *   "msm.log_red_chunk"          0..8, default 0: 2^x buckets per thread in the bucket reduction; 0: auto
  * Per lane, NTT:
- *   "ntt.tile_log"               6..12, default 9: log2 of the elements of a workgroup's tile
+ *   "ntt.tile_log"               6..12, default 9: log2 of the elements of a workgroup's tile (narrowed, for a pass, to what fits the LDS beside that pass's twiddles: 2^12 elements with passes of up to 2^9 points)
  *   "ntt.threads"                64..1024, default 256: threads of that workgroup
  *   "ntt.big_tile_log"           0 | 6..12, default 10: the tile of the throughput shape (batches of ntt.batch_min vectors and more, transforms of 2^ntt.big_log points and more); 0: one shape for all
  *   "ntt.big_threads"            64..1024, default 512: threads of its workgroup
  *   "ntt.batch_min"              1..2147483647, default 4: batched launches of at least this many vectors take the throughput shape
  *   "ntt.big_log"                1..2147483647, default 20: ... and so do transforms of at least 2^x points
  *   "ntt.radix4"                 0..2, default 0: two butterfly stages per sweep over the LDS tile (same words) -- by size (the throughput shapes, 3-6 % faster there: profiles/r05_sweeps/ntt_radix4.txt) / always / never
- *   "ntt.max_single_log"         1..12, default 11: largest transform done in one LDS-resident pass (setting it drops the lane's plans)
- *   "ntt.max_multi_log"          4..12, default 9: largest per-pass DFT length of multi-pass plans (likewise) */
+ *   "ntt.max_single_log"         1..11, default 11: largest transform done in one LDS-resident pass (setting it drops the lane's plans); 2^11 points are the longest pass whose tile fits the 160 KiB of LDS
+ *   "ntt.max_multi_log"          4..11, default 9: largest per-pass DFT length of multi-pass plans (likewise) */
 int sg_set_param(const char* name, int value);
 int sg_get_param(const char* name, int* value);
 /* Profiling aid.  With parameter "msm.acc_log" = 1 (setting it clears the log) every msm_accumulate launch of the process is

@@ -469,7 +469,10 @@ def test_every_parameter_reads_its_default_and_round_trips():
               ("msm.two_pass", 5, 2), ("msm.fused_frontend", 9, 2), ("msm.acc_chain", 4, 1), ("msm.red2d_fold", 0, 1),
               ("msm.red2d_max_sets", 99, 32), ("msm.acc_waves", 20, 8), ("msm.log_red_chunk", 9, 8), ("msm.log_scatter_rounds", 7, 6),
               ("ntt.tile_log", 1, 6), ("ntt.threads", 5000, 1024), ("ntt.big_tile_log", 3, 6), ("ntt.big_tile_log", 0, 0),
-              ("ntt.radix4", 7, 0), ("ntt.radix4", 2, 2), ("ntt.max_single_log", 0, 1), ("ntt.max_multi_log", 1, 4), ("ntt.batch_min", 0, 1)]
+              ("ntt.radix4", 7, 0), ("ntt.radix4", 2, 2), ("ntt.max_single_log", 0, 1), ("ntt.max_multi_log", 1, 4), ("ntt.batch_min", 0, 1),
+              # a pass of 2^12 points does not fit the LDS: both plan cuts stop at 11
+              ("ntt.max_single_log", 12, 11), ("ntt.max_multi_log", 12, 11), ("ntt.max_multi_log", 99, 11), ("ntt.tile_log", 13, 12),
+              ("ntt.big_tile_log", 13, 12), ("ntt.big_threads", 1, 64)]
     env = dict(os.environ, REPO_ROOT=ROOT, DOCUMENTED_DEFAULTS=json.dumps(doc), CLAMPS=json.dumps(clamps))
     r = subprocess.run([sys.executable, "-c", PARAMS_CHILD], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0 and "params ok" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
