@@ -425,7 +425,7 @@ int sg_grand_products_closing_dev(const void* const* d_values, const void* const
     return fail(SG_ERR_INVALID, "sg_grand_products: null argument");
   if (n_chunks + n_lookups == 0) return SG_OK;
   if (n_chunks + n_lookups > GRAND_MAX) return fail(SG_ERR_INVALID, "sg_grand_products: at most 8 products per call");
-  if (k == 0 || k > 20) return fail(SG_ERR_INVALID, "sg_grand_products: 1 <= k <= 20");
+  if (k == 0 || k > 21) return fail(SG_ERR_INVALID, "sg_grand_products: 1 <= k <= 21");
   const size_t n = (size_t)1 << k;
   if (usable_rows >= n) return fail(SG_ERR_INVALID, "sg_grand_products: usable_rows must be below 2^k");
   LOCKED_CTX();

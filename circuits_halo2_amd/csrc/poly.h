@@ -17,8 +17,9 @@ hipError_t poly_eval_batch(const fp_words* const* d_polys, const words8* xs, uin
                            fp_words* d_out, hipStream_t stream);
 // in place; zeros stay zero
 hipError_t poly_batch_invert(fp_words* d_a, size_t n, hipStream_t stream);
-// out[0] = 1, out[i] = a[0] * ... * a[i-1], i <= n (n + 1 outputs); n <= 2^21
-// count_out <= n + 1 values are written; *init (optional) multiplies every output (z[0] = init)
+// out[0] = 1, out[i] = a[0] * ... * a[i-1], i <= n; count_out <= n + 1 values are written: all n + 1 outputs while
+// n + 1 <= 2^21, or n <= 2^21 with count_out <= n (a grand product's z: n rows); *init (optional) multiplies every
+// output (z[0] = init)
 hipError_t poly_prefix_product(const fp_words* d_a, size_t n, fp_words* d_tmp, fp_words* d_out, size_t count_out,
                                const words8* init, hipStream_t stream);
 static constexpr uint32_t PERM_MAX_COLS = 8;

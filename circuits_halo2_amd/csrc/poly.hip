@@ -586,8 +586,11 @@ hipError_t poly_batch_invert(fp_words* d_a, size_t n, hipStream_t stream) {
 size_t prefix_product_tmp_elems(size_t n) { return (n + PP_BLOCK - 1) / PP_BLOCK + 1; }
 hipError_t poly_prefix_product(const fp_words* d_a, size_t n, fp_words* d_tmp, fp_words* d_out, size_t count_out,
                                const words8* init, hipStream_t stream) {
-  const uint32_t nblk = (uint32_t)((n + 1 + PP_BLOCK - 1) / PP_BLOCK);  // covers out[0..n]
-  if (nblk > 1024 || count_out > n + 1) return hipErrorInvalidValue;    // n <= 2^21
+  // the blocks kernel covers a[0..n), the write kernel out[0..count_out): n + 1 outputs <= 2^21, or n <= 2^21 with count_out <= n
+  const size_t span = std::max(n, count_out);
+  if (span > (size_t)1024 * PP_BLOCK || count_out > n + 1) return hipErrorInvalidValue;
+  if (span == 0) return hipSuccess;
+  const uint32_t nblk = (uint32_t)((span + PP_BLOCK - 1) / PP_BLOCK);
   prefix_product_blocks<<<nblk, PP_THREADS, 0, stream>>>(d_a, (uint32_t)n, d_tmp);
   prefix_product_scan_blocks<<<1, 1024, 0, stream>>>(d_tmp, nblk);
   words8 one{};
@@ -746,7 +749,7 @@ hipError_t poly_grand_products(const GrandProducts& g, const words8& beta, const
   const uint32_t Pn = g.n_perm + g.n_lookup;
   if (Pn == 0) return hipSuccess;
   if (Pn > GRAND_MAX || n == 0 || usable >= n || (g.n_perm && !d_pow_tab)) return hipErrorInvalidValue;
-  const uint32_t nblk = (uint32_t)((n + 1 + PP_BLOCK - 1) / PP_BLOCK);   // covers out[0..n]
+  const uint32_t nblk = (uint32_t)((n + PP_BLOCK - 1) / PP_BLOCK);       // n rows are read and n written: z[0..n)
   if (nblk > 1024) return hipErrorInvalidValue;                          // n <= 2^21
   const dim3 rows((unsigned)((n + 255) / 256), Pn);
   grand_fraction_kernel<<<rows, 256, 0, stream>>>(g, beta, gamma, delta, (uint32_t)n, 0u, d_pow_tab, d_mod);

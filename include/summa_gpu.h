@@ -333,7 +333,7 @@ int sg_lookup_product_dev(const void* d_input, const void* d_table, const void* 
  * to synchronise.  Same values as the calls above chained by hand.
  *   d_values / d_sigma: the permutation's columns in order, chunk after chunk (chunk j has chunk_cols[j] <= 8 of them);
  *   d_lookup_cols: 4 per lookup -- input, table, permuted input, permuted table (theta-compressed by the caller);
- *   d_z: n_chunks + n_lookups outputs of 2^k values each (the caller overwrites the blinding rows); k <= 20,
+ *   d_z: n_chunks + n_lookups outputs of 2^k values each (the caller overwrites the blinding rows); k <= 21,
  *   n_chunks + n_lookups <= 8. */
 int sg_grand_products_dev(const void* const* d_values, const void* const* d_sigma, const uint32_t* chunk_cols, uint32_t n_chunks,
                           const void* const* d_lookup_cols, uint32_t n_lookups, const uint8_t beta[32], const uint8_t gamma[32],
