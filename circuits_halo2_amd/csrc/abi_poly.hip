@@ -291,7 +291,7 @@ int sg_fr_eval_poly_dev(const void* d_coeffs, size_t n, const uint8_t x[32], voi
 int sg_fr_eval_poly_batch_dev(const void* const* d_polys, size_t n, const uint8_t* points, uint32_t m, void* stream,
                               uint8_t* out) {
   if (m && (!d_polys || !points || !out)) return fail(SG_ERR_INVALID, "sg_fr_eval_poly_batch: null argument");
-  if (n > (1ull << 26)) return fail(SG_ERR_INVALID, "sg_fr_eval_poly_batch: polynomial too long");
+  if (n > EVAL_BATCH_MAX_N) return fail(SG_ERR_INVALID, "sg_fr_eval_poly_batch: polynomial too long");
   if (m == 0) return SG_OK;
   if (n == 0) {
     std::memset(out, 0, 32 * (size_t)m);
@@ -300,8 +300,7 @@ int sg_fr_eval_poly_batch_dev(const void* const* d_polys, size_t n, const uint8_
   for (uint32_t j = 0; j < m; j++)
     if (!d_polys[j]) return fail(SG_ERR_INVALID, "sg_fr_eval_poly_batch: null polynomial");
   LOCKED_CTX();
-  const size_t blocks = poly_eval_batch_blocks(n);
-  hipError_t e = g_ctx->scratch.reserve((EVAL_BATCH_MAX * (blocks + 1)) * 32);
+  hipError_t e = g_ctx->scratch.reserve(eval_batch_tmp_elems(n) * 32);
   if (e != hipSuccess) return hip_fail("eval_poly work space", e);
   fp_words* partial = reinterpret_cast<fp_words*>(g_ctx->scratch.p);
   // the values land in page-locked host memory the last kernel writes directly: the host waits for the stream once and reads them
@@ -311,7 +310,7 @@ int sg_fr_eval_poly_batch_dev(const void* const* d_polys, size_t n, const uint8_
   static_assert(EVAL_BATCH_MAX * 32 <= Context::MAIL_BYTES, "the mailbox holds one batch of evaluations");
   hipStream_t s = pick_stream(stream);
   for (uint32_t first = 0; first < m; first += EVAL_BATCH_MAX) {
-    const uint32_t cnt = std::min<uint32_t>(EVAL_BATCH_MAX, m - first);
+    const uint32_t cnt = eval_batch_count(m, first);
     words8 xs[EVAL_BATCH_MAX];
     std::memcpy(xs, points + 32 * (size_t)first, 32 * (size_t)cnt);
     e = poly_eval_batch(reinterpret_cast<const fp_words* const*>(d_polys + first), xs, cnt, n, partial, reinterpret_cast<fp_words*>(d_mail), s);
@@ -337,7 +336,7 @@ int sg_fr_batch_invert_dev(void* d_a, size_t n, void* stream) {
 }
 int sg_fr_prefix_product_dev(const void* d_a, size_t n, void* d_out, void* stream) {
   if (!d_out || (n && !d_a)) return fail(SG_ERR_INVALID, "sg_fr_prefix_product: null argument");
-  if (n > (1ull << 21) - 1) return fail(SG_ERR_INVALID, "sg_fr_prefix_product: at most 2^21 - 1 elements");
+  if (n > PREFIX_MAX_SPAN - 1) return fail(SG_ERR_INVALID, "sg_fr_prefix_product: at most 2^21 - 1 elements");
   LOCKED_CTX();
   hipStream_t s = pick_stream(stream);
   uint8_t* tmp = nullptr;
@@ -363,7 +362,7 @@ int sg_permutation_product_dev(const void* const* d_values, const void* const* d
                                const uint8_t beta[32], const uint8_t gamma[32], const uint8_t delta_start[32],
                                uint32_t k, const uint8_t* z0, void* d_z, void* stream) {
   if (!d_values || !d_sigma || !beta || !gamma || !delta_start || !d_z || ncols == 0 || ncols > PERM_MAX_COLS ||
-      k > 21)
+      k > GRAND_MAX_K)
     return fail(SG_ERR_INVALID, "sg_permutation_product: bad argument");
   LOCKED_CTX();
   const size_t n = (size_t)1 << k;
@@ -381,11 +380,11 @@ int sg_permutation_product_dev(const void* const* d_values, const void* const* d
   if (e != hipSuccess) return hip_fail("grand product work space", e);
   fp_words* mod = reinterpret_cast<fp_words*>(modb);
   const words8 b = load32(beta), g = load32(gamma), ds = load32(delta_start), &dl = DELTA_M;
-  e = poly_perm_fraction(cols, ncols, b, g, ds, dl, dc->omega, n, 0, mod, s);
+  e = poly_perm_fraction(cols, ncols, b, g, ds, dl, n, 0, mod, s);
   if (e == hipSuccess) e = poly_batch_invert(mod, n, s);
   fp_words* pw = nullptr;   // omega^i, i < n (cached per domain): one product instead of one exponentiation per row
-  if (e == hipSuccess && n == ((size_t)1 << k)) e = g_ctx->ntt.local_twiddles(dc->omega, k + 1, s, &pw);
-  if (e == hipSuccess) e = poly_perm_fraction(cols, ncols, b, g, ds, dl, dc->omega, n, 1, mod, s, pw);
+  if (e == hipSuccess) e = g_ctx->ntt.local_twiddles(dc->omega, k + 1, s, &pw);
+  if (e == hipSuccess) e = poly_perm_fraction(cols, ncols, b, g, ds, dl, n, 1, mod, s, pw);
   if (e != hipSuccess) return hip_fail("permutation product", e);
   return grand_product_tail(mod, n, z0, d_z, s);
 }
@@ -393,7 +392,7 @@ int sg_lookup_product_dev(const void* d_input, const void* d_table, const void* 
                           const void* d_permuted_table, const uint8_t beta[32], const uint8_t gamma[32], size_t n,
                           void* d_z, void* stream) {
   if (!d_input || !d_table || !d_permuted_input || !d_permuted_table || !beta || !gamma || !d_z || n == 0 ||
-      n > (1u << 21) - 1)
+      n > PREFIX_MAX_SPAN - 1)
     return fail(SG_ERR_INVALID, "sg_lookup_product: bad argument");
   LOCKED_CTX();
   hipStream_t s = pick_stream(stream);
@@ -425,7 +424,7 @@ int sg_grand_products_closing_dev(const void* const* d_values, const void* const
     return fail(SG_ERR_INVALID, "sg_grand_products: null argument");
   if (n_chunks + n_lookups == 0) return SG_OK;
   if (n_chunks + n_lookups > GRAND_MAX) return fail(SG_ERR_INVALID, "sg_grand_products: at most 8 products per call");
-  if (k == 0 || k > 21) return fail(SG_ERR_INVALID, "sg_grand_products: 1 <= k <= 21");
+  if (k == 0 || k > GRAND_MAX_K) return fail(SG_ERR_INVALID, "sg_grand_products: 1 <= k <= 21");
   const size_t n = (size_t)1 << k;
   if (usable_rows >= n) return fail(SG_ERR_INVALID, "sg_grand_products: usable_rows must be below 2^k");
   LOCKED_CTX();
@@ -491,7 +490,7 @@ int sg_fr_mul_dev(const void* d_a, const void* d_b, size_t n, void* d_out, void*
 int sg_fr_kate_division_dev(const void* d_a, size_t n, const uint8_t b[32], void* d_q, uint8_t* remainder_out,
                             void* stream) {
   if (!b || (n && (!d_a || !d_q))) return fail(SG_ERR_INVALID, "sg_fr_kate_division: null argument");
-  if (n > (1ull << 21)) return fail(SG_ERR_INVALID, "sg_fr_kate_division: at most 2^21 coefficients");
+  if (n > KATE_MAX_N) return fail(SG_ERR_INVALID, "sg_fr_kate_division: at most 2^21 coefficients");
   if (d_a == d_q && n) return fail(SG_ERR_INVALID, "sg_fr_kate_division: the quotient must not alias the input");
   if (n == 0) {
     if (remainder_out) std::memset(remainder_out, 0, 32);
@@ -501,7 +500,7 @@ int sg_fr_kate_division_dev(const void* d_a, size_t n, const uint8_t b[32], void
   const words8 bw = load32(b);
   hipStream_t s = pick_stream(stream);
   uint8_t* tb = nullptr;
-  hipError_t e = scratch_for(s, 0, 1025 * 32 + 64, &tb);
+  hipError_t e = scratch_for(s, 0, kate_tmp_elems() * 32 + 64, &tb);
   if (e != hipSuccess) return hip_fail("kate_division work space", e);
   fp_words* tmp = reinterpret_cast<fp_words*>(tb);
   uint8_t *h_mail = nullptr, *d_mail = nullptr;
@@ -521,13 +520,13 @@ int sg_fr_kate_division_dev(const void* d_a, size_t n, const uint8_t b[32], void
 }
 int sg_fr_kate_division_rem_dev(const void* d_a, size_t n, const uint8_t b[32], void* d_q, void* d_remainder, void* stream) {
   if (!b || !d_remainder || (n && (!d_a || !d_q))) return fail(SG_ERR_INVALID, "sg_fr_kate_division_rem: null argument");
-  if (n == 0 || n > (1ull << 21)) return fail(SG_ERR_INVALID, "sg_fr_kate_division_rem: between 1 and 2^21 coefficients");
+  if (n == 0 || n > KATE_MAX_N) return fail(SG_ERR_INVALID, "sg_fr_kate_division_rem: between 1 and 2^21 coefficients");
   if (d_a == d_q) return fail(SG_ERR_INVALID, "sg_fr_kate_division_rem: the quotient must not alias the input");
   LOCKED_CTX();
   const words8 bw = load32(b);
   hipStream_t s = pick_stream(stream);
   uint8_t* tb = nullptr;
-  hipError_t e = scratch_for(s, 0, 1025 * 32 + 64, &tb);
+  hipError_t e = scratch_for(s, 0, kate_tmp_elems() * 32 + 64, &tb);
   if (e != hipSuccess) return hip_fail("kate_division work space", e);
   e = poly_kate_division(static_cast<const fp_words*>(d_a), n, bw, reinterpret_cast<fp_words*>(tb), static_cast<fp_words*>(d_q),
                          static_cast<fp_words*>(d_remainder), s);
@@ -553,15 +552,15 @@ int sg_fr_count_noncanonical_dev(const void* const* d_cols, uint32_t m, size_t n
 int sg_fr_kate_division_batch_dev(const void* const* d_a, size_t n, const uint8_t* points, uint32_t m, void* const* d_q,
                                   void* stream) {
   if (m && (!d_a || !points || !d_q)) return fail(SG_ERR_INVALID, "sg_fr_kate_division_batch: null argument");
-  if (m > 16) return fail(SG_ERR_INVALID, "sg_fr_kate_division_batch: at most 16 divisions per call");
-  if (n > (1ull << 21)) return fail(SG_ERR_INVALID, "sg_fr_kate_division_batch: at most 2^21 coefficients");
+  if (m > KATE_BATCH_MAX) return fail(SG_ERR_INVALID, "sg_fr_kate_division_batch: at most 16 divisions per call");
+  if (n > KATE_MAX_N) return fail(SG_ERR_INVALID, "sg_fr_kate_division_batch: at most 2^21 coefficients");
   for (uint32_t j = 0; j < m; j++)
     if (n && (!d_a[j] || !d_q[j] || d_a[j] == d_q[j])) return fail(SG_ERR_INVALID, "sg_fr_kate_division_batch: bad vector");
   if (m == 0 || n == 0) return SG_OK;
   LOCKED_CTX();
   hipStream_t s = pick_stream(stream);
   uint8_t* d_tmp = nullptr;
-  hipError_t e = scratch_for(s, 6, kate_batch_tmp_elems(n, 16) * 32 + 64, &d_tmp);
+  hipError_t e = scratch_for(s, 6, kate_batch_tmp_elems(n, KATE_BATCH_MAX) * 32 + 64, &d_tmp);
   if (e != hipSuccess) return hip_fail("kate_division_batch work space", e);
   std::vector<words8> b(m);
   std::memcpy(b.data(), points, 32 * (size_t)m);
@@ -569,7 +568,7 @@ int sg_fr_kate_division_batch_dev(const void* const* d_a, size_t n, const uint8_
   // call used to wait for the whole stream so that a local staging buffer could die -- 0.16 ms of a proof with the device idle
   // behind it); a slot is reused once the kernels that read it have run (an event; normally long complete)
   Context::BlobSlot* slot_p = nullptr;
-  e = ring_slot(g_ctx->kate_ring, kate_batch_powers_bytes(16), kate_batch_powers_bytes(16), &slot_p);
+  e = ring_slot(g_ctx->kate_ring, kate_batch_powers_bytes(KATE_BATCH_MAX), kate_batch_powers_bytes(KATE_BATCH_MAX), &slot_p);
   Context::BlobSlot& slot = *slot_p;
   if (e == hipSuccess)
     e = poly_kate_division_batch(reinterpret_cast<const fp_words* const*>(d_a), n, b.data(), m, reinterpret_cast<fp_words* const*>(d_q),

@@ -3,16 +3,15 @@
 #include <hip/hip_runtime.h>
 
 #include "msm.h"
+#include "poly_plan.h"
 
 namespace sg {
+// The sizes, limits and work-space functions named below are in poly_plan.h.
 // *d_out = sum_i coeffs[i] x^i; tmp buffers of poly_eval_tmp_elems(n) elements each
 hipError_t poly_eval(const fp_words* d_coeffs, size_t n, const words8& x, fp_words* d_tmp_a, fp_words* d_tmp_b,
                      fp_words* d_out, hipStream_t stream);
-size_t poly_eval_tmp_elems(size_t n);
 // out[j] = polys[j](xs[j]) for m <= EVAL_BATCH_MAX polynomials of n <= 2^26 coefficients each, two launches;
 // d_partial: m * poly_eval_batch_blocks(n) elements
-size_t poly_eval_batch_blocks(size_t n);
-static constexpr uint32_t EVAL_BATCH_MAX = 40;
 hipError_t poly_eval_batch(const fp_words* const* d_polys, const words8* xs, uint32_t m, size_t n, fp_words* d_partial,
                            fp_words* d_out, hipStream_t stream);
 // in place; zeros stay zero
@@ -28,17 +27,15 @@ struct PermCols {  // one chunk of the permutation argument (kernel argument)
   const fp_words* sigma[PERM_MAX_COLS];
 };
 // numer = 0: io[i] = prod_c (beta sigma_c[i] + gamma + v_c[i]);  numer = 1: io[i] *= prod_c (delta_start
-// delta^c omega^i beta + gamma + v_c[i])
+// delta^c omega^i beta + gamma + v_c[i]), with d_pow_tab (required then): omega^i, i < n, as for poly_grand_products
 hipError_t poly_perm_fraction(const PermCols& cols, uint32_t ncols, const words8& beta, const words8& gamma,
-                              const words8& delta_start, const words8& delta, const words8& omega, size_t n,
-                              int numer, fp_words* d_io, hipStream_t stream, const fp_words* d_pow_tab = nullptr);
+                              const words8& delta_start, const words8& delta, size_t n, int numer, fp_words* d_io,
+                              hipStream_t stream, const fp_words* d_pow_tab = nullptr);
 // numer = 0: io[i] = (x[i] + beta)(y[i] + gamma);  numer = 1: io[i] *= (x[i] + beta)(y[i] + gamma)
 hipError_t poly_lookup_fraction(const fp_words* d_x, const fp_words* d_y, const words8& beta, const words8& gamma,
                                 size_t n, int numer, fp_words* d_io, hipStream_t stream);
-size_t prefix_product_tmp_elems(size_t n);
-// all grand products of one proof in batched launches (poly.hip): products 0 .. n_perm-1 are the chunks of the permutation
+// all grand products of one proof in batched launches (poly_scan.cuh): products 0 .. n_perm-1 are the chunks of the permutation
 // argument in order (chunk j's z continues from chunk j-1's value at row `usable`), then n_lookup lookup products
-static constexpr uint32_t GRAND_MAX = 8;
 struct GrandProducts {   // kernel argument
   uint32_t n_perm, n_lookup;
   uint32_t ncols[GRAND_MAX];             // columns of permutation chunk p
@@ -53,16 +50,12 @@ struct GrandOut {
   fp_words* closing = nullptr;
   uint32_t closing_row = 0;
 };
-size_t grand_products_mod_elems(size_t n, uint32_t products);
-size_t grand_products_tmp_elems(size_t n, uint32_t products);
 // d_pow_tab: omega^i, i < n, as 2^261-domain words (NttEngine::local_twiddles); d_mod / d_tmp: work space of the sizes above
 hipError_t poly_grand_products(const GrandProducts& g, const words8& beta, const words8& gamma, const words8& delta, size_t n,
                                size_t usable, const fp_words* d_pow_tab, fp_words* d_mod, fp_words* d_tmp, const GrandOut& outs,
                                hipStream_t stream);
 // Kate division a(X) = q(X)(X - b) + a(b): q_out gets n slots (q_0..q_{n-2}, then a zero) and must not alias a,
-// rem_out (optional) a(b); n <= 2^21; d_tmp: 1024 elements
-size_t kate_batch_powers_bytes(uint32_t m);
-size_t kate_batch_tmp_elems(size_t n, uint32_t m);
+// rem_out (optional) a(b); n <= 2^21; d_tmp: kate_tmp_elems() elements
 hipError_t poly_kate_division_batch(const fp_words* const* d_a, size_t n, const words8* b, uint32_t m, fp_words* const* d_q,
                                     uint8_t* h_pw, uint8_t* d_pw, fp_words* d_tmp, hipStream_t stream);
 hipError_t poly_kate_division(const fp_words* d_a, size_t n, const words8& b, fp_words* d_tmp, fp_words* d_q,
@@ -73,15 +66,12 @@ hipError_t poly_count_noncanonical(const fp_words* const* d_cols, uint32_t m, si
 // clears it; it may live in page-locked host memory mapped into the device: no memset launch, no copy back)
 hipError_t poly_flag_noncanonical(const fp_words* const* d_cols, uint32_t m, size_t n, uint32_t* d_flag, hipStream_t stream);
 // out[i] = sum_j coeffs[j] * polys[j][i], m <= LINCOMB_MAX
-static constexpr uint32_t LINCOMB_MAX = 32;
 // optionally + low[i] for i < n_low <= LINCOMB_LOW_MAX (a polynomial of a few coefficients, passed by value)
-static constexpr uint32_t LINCOMB_LOW_MAX = 8;
 hipError_t poly_lincomb(const fp_words* const* d_polys, const words8* coeffs, uint32_t m, size_t n, fp_words* d_out,
                         hipStream_t stream, const words8* low = nullptr, uint32_t n_low = 0);
 // the same for up to LINCOMB_SETS_MAX independent combinations of one length in ONE launch (grid.y = combination): combination s
 // takes polys / coeffs [first[s], first[s + 1]) (at most LINCOMB_MAX of LINCOMB_SETS_POLYS in all) and n_low[s] <= LINCOMB_SETS_LOW
 // low coefficients -- the rotation sets of the multi-open
-static constexpr uint32_t LINCOMB_SETS_MAX = 8, LINCOMB_SETS_POLYS = 48, LINCOMB_SETS_LOW = 4;
 hipError_t poly_lincomb_sets(const fp_words* const* d_polys, const words8* coeffs, const uint32_t* first, uint32_t n_sets, size_t n,
                              const words8* low, const uint32_t* n_low, fp_words* const* d_out, hipStream_t stream);
 // halo2 lookup::prover::permute_expression_pair for range tables (every table value < 2^16), on the device:

@@ -1,7 +1,7 @@
-"""The host-side geometry of csrc/poly.hip restated in Python (the blocks of the prefix product, the Kate division and the grand
+"""The host-side geometry of csrc/poly_plan.h restated in Python (the blocks of the prefix product, the Kate division and the grand
 products, the width of the Kate scan, the levels of either evaluation path, the mid-sum reduction of the linear combination), the
 input generators, and the list of cases that tests/test_gpu_poly_edges.py runs against the oracle.  tests/test_poly_cases_cpu.py
-compares the restated constants with the source text, checks the generators against the oracle and asserts that the case list
+compares the restatement with the compiled rules (tests/cpp/poly_plan_check.cpp), checks the generators against the oracle and asserts that the case list
 reaches every class of launch -- without a GPU."""
 import numpy as np
 
@@ -17,6 +17,8 @@ EV_THREADS, EV_CH = 256, 32
 EV_BATCH_CH_SMALL, EV_BATCH_CH_BIG, EV_BATCH_SMALL_MAX = 16, 32, 1 << 24
 EVAL_BATCH_MAX = 40
 LINCOMB_MAX, LINCOMB_LOW_MAX = 32, 8
+KATE_BATCH_MAX, GRAND_MAX = 16, 8
+KATE_POWERS_BYTES = (1 + 8 + 10) * 9 * 4     # b, b^(8 * 2^j) for j < 8, b^(2048 * 2^j) for j < 10, nine limbs each
 SCAN_MAX = 1024                  # one workgroup scans the per-block values
 FAST_ABOVE = 1 << 17             # longer random vectors come from fast_words
 
@@ -73,6 +75,32 @@ def eval_batch_plan(n, m):
     if n == 0 or n > 1 << 26 or blocks > ch * EV_THREADS:
         return None
     return ch, blocks, [min(EVAL_BATCH_MAX, m - f) for f in range(0, m, EVAL_BATCH_MAX)]
+
+
+def plan_constants():
+    """the first line of tests/cpp/poly_plan_check.cpp"""
+    c = dict(PP_CH=PP_CH, PP_THREADS=PP_THREADS, PP_BLOCK=PP_BLOCK, KD_CH=KD_CH, KD_THREADS=KD_THREADS, KD_BLOCK=KD_BLOCK, BI_CH=BI_CH,
+             EV_THREADS=EV_THREADS, EV_CH=EV_CH, EV_LOG=(EV_CH * EV_THREADS).bit_length() - 1, EVAL_BATCH_MAX=EVAL_BATCH_MAX,
+             EVAL_BATCH_SMALL_MAX=EV_BATCH_SMALL_MAX, EVAL_BATCH_MAX_N=(EV_BATCH_CH_BIG * EV_THREADS) ** 2, POLY_SCAN_MAX=SCAN_MAX,
+             PREFIX_MAX_SPAN=SCAN_MAX * PP_BLOCK, KATE_MAX_N=SCAN_MAX * KD_BLOCK, KATE_BATCH_MAX=KATE_BATCH_MAX, KATE_POWERS_BYTES=KATE_POWERS_BYTES,
+             GRAND_MAX=GRAND_MAX, GRAND_MAX_K=(SCAN_MAX * PP_BLOCK).bit_length() - 1, LINCOMB_MAX=LINCOMB_MAX, LINCOMB_LOW_MAX=LINCOMB_LOW_MAX,
+             LINCOMB_SETS_MAX=8, LINCOMB_SETS_POLYS=48, LINCOMB_SETS_LOW=4)
+    return " ".join(f"{k}={v}" for k, v in c.items())
+
+
+def plan_line(n, m):
+    """what tests/cpp/poly_plan_check.cpp answers to `size n m`, from the rules above and the work-space sizes restated here"""
+    f = lambda v: "none" if v is None else str(v)
+    kb, batch = kate_blocks(n), eval_batch_plan(n, m)
+    ch = EV_BATCH_CH_SMALL if n <= EV_BATCH_SMALL_MAX else EV_BATCH_CH_BIG
+    partials = _ceil(n, ch * EV_THREADS)
+    launches = ",".join(str(min(EVAL_BATCH_MAX, m - first)) for first in range(0, m, EVAL_BATCH_MAX)) or "-"
+    return (f"size n={n} m={m} prefix={f(prefix_blocks(n, n + 1))} prefix_rows={f(prefix_blocks(n, n))} prefix_tmp={_ceil(n + 1, PP_BLOCK) + 1} "
+            f"grand={f(grand_blocks(n))} grand_mod={m * n} grand_tmp={m * _ceil(n + 1, PP_BLOCK) + 1} kate={f(kb)} "
+            f"kate_scan={kate_scan_threads(kb) if kb is not None and kb > 1 else '-'} kate_tmp={SCAN_MAX + 1} kate_batch_tmp={m * _ceil(n, KD_BLOCK) + 1} "
+            f"kate_batch_powers={m * KATE_POWERS_BYTES} eval_levels={','.join(map(str, eval_levels(n))) if n else '-'} "
+            f"eval_tmp={_ceil(n, EV_CH * EV_THREADS) + 1} batch_ch={batch[0] if batch else '-'} batch_blocks={f(batch and batch[1])} "
+            f"batch_partials={partials} batch_tmp={EVAL_BATCH_MAX * (partials + 1)} batch_launches={launches}")
 
 
 def lincomb_mid_reductions(m):
@@ -217,6 +245,17 @@ KATE_ALL_CLASSES_UP_TO = KD_BLOCK * 65
 KATE_BATCH_BLOCKS = (65, 1024)
 
 
+# one block (no carries, one launch) and two blocks (the first carry): the paths the single and the batched division share
+# now that both run one body.  n = 1 (a constant: empty quotient, the remainder is the constant) is accepted by the oracle.
+KATE_SMALL_SIZES = (1, 2, 2047, 2048)
+KATE_SMALL_CLASSES, KATE_SMALL_POINTS = ("random", "last"), ("random", R - 1)
+KATE_BATCH_SMALL_SIZES = (1, 2, 2048, 2049, 4096)
+KATE_BATCH_M = (1, 16)                   # 16: every division reads the one input, at sixteen different points
+# the grid on which tests/test_poly_cases_cpu.py compares the restated rules with the compiled ones, beside the case lists
+PLAN_EDGE_BLOCKS = (1, 2, 64, 128, 256, 512, 1024)
+PLAN_EVAL_EDGES = ((1 << 24) - 1, (1 << 24) + 1, (1 << 26) - 1, (1 << 26) + 1)
+
+
 def kate_classes(n):
     return KATE_CLASSES if n <= KATE_ALL_CLASSES_UP_TO else KATE_LARGE_CLASSES
 
@@ -300,6 +339,13 @@ def reached():
         seen.add("kate: first refused size")
     for b in KATE_BATCH_BLOCKS:
         seen.add(f"kate batch: scan of {kate_scan_threads(b)} threads")
+    if {kate_blocks(n) for n in KATE_SMALL_SIZES} == {1}:
+        seen.add("kate: one block")
+    for n in KATE_BATCH_SMALL_SIZES:
+        if kate_blocks(n) in (1, 2):
+            seen.add("kate batch: one block" if kate_blocks(n) == 1 else "kate batch: two blocks")
+    if max(KATE_BATCH_M) == KATE_BATCH_MAX:
+        seen.add("kate batch: 16 divisions")
     for n in EVAL_SIZES:
         lv = eval_levels(n)
         seen.add(f"eval: {len(lv)} level{'s' * (len(lv) > 1)}")
@@ -358,6 +404,7 @@ WANTED = {
     "kate: one coefficient in the last block", "kate: 1024 full blocks", "kate: first refused size",
     *(f"kate: class {c} at small sizes" for c in KATE_CLASSES), *(f"kate: class {c} at large sizes" for c in KATE_LARGE_CLASSES),
     "kate batch: scan of 128 threads", "kate batch: scan of 1024 threads",
+    "kate: one block", "kate batch: one block", "kate batch: two blocks", "kate batch: 16 divisions",
     "eval: 1 level", "eval: 2 levels", "eval: one coefficient in the last workgroup", "eval: a thread of the second level has two rows",
     "eval batch: 16 per thread", "eval batch: 32 per thread", "eval batch: one partial", "eval batch: several partials",
     "eval batch: the last full second level of the 16-per-thread kernel", "eval batch: more than 40 polynomials", "eval batch: 40 in one launch",

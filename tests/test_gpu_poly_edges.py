@@ -1,5 +1,5 @@
-"""The polynomial helpers of csrc/poly.hip (evaluation, batch inversion, prefix product, Kate division, grand products, linear
-combinations, element-wise product) at the sizes where their launch geometry changes and on the inputs uniform sampling never
+"""The polynomial helpers of csrc/poly.hip and csrc/poly_scan.cuh (evaluation, batch inversion, prefix product, Kate division,
+grand products, linear combinations, element-wise product) at the sizes where their launch geometry changes and on the inputs uniform sampling never
 gives, against the oracle.
 
 tests/poly_cases.py restates the geometry and lists the cases; tests/test_poly_cases_cpu.py asserts, without a GPU, that they
@@ -145,9 +145,36 @@ def _kate_want(O, name, n, b, seed):
     if name == "last":
         c, bv = pc.single_value(seed), pc.value_of(b)
         at = sorted({0, n - 2} | {pc.KD_BLOCK * j - 1 for j in range(1, pc.kate_blocks(n))} | {pc.KD_BLOCK * j for j in range(1, pc.kate_blocks(n)) if pc.KD_BLOCK * j < n - 1})
+        at = [i for i in at if 0 <= i < n - 1]           # (n = 1: the quotient is empty)
         assert (q.reshape(-1, 32)[at] == pc.mont([pc.kate_of_last(c, bv, n, i) for i in at]).reshape(-1, 32)).all()
         assert (rem == pc.mont([pc.kate_of_last(c, bv, n, -1)])).all()
     return np.concatenate([q, np.zeros(32, dtype=np.uint8)]), rem
+
+
+def _kate_single_and_rem(O, n, name, points):
+    """sg_fr_kate_division_dev and sg_fr_kate_division_rem_dev on one input class at every point of `points`: quotient, zero
+    padding slot, remainder on the host and on the device; the input is unchanged"""
+    import torch
+    ffi, L = _L()
+    nblk = pc.kate_blocks(n)
+    d_a = _dev(_vec(O, name, n, 31))
+    for point in points:
+        b = pc.scalar(O, point, 32)
+        want_q, want_rem = _kate_want(O, name, n, b, 31)
+        q1, q2, rem_dev, rem = _garbage(32 * n), _garbage(32 * n), _garbage(32), np.zeros(32, dtype=np.uint8)
+        ffi.check(L.sg_fr_kate_division_dev(ffi.dev_ptr(d_a), C.c_size_t(n), ffi.ptr(b), ffi.dev_ptr(q1), ffi.ptr(rem), ffi.current_stream_ptr()))
+        ffi.check(L.sg_fr_kate_division_rem_dev(ffi.dev_ptr(d_a), C.c_size_t(n), ffi.ptr(b), ffi.dev_ptr(q2), ffi.dev_ptr(rem_dev),
+                                                ffi.current_stream_ptr()))
+        torch.cuda.synchronize()
+        what = f"Kate division n={n} ({nblk} blocks, scan of {pc.kate_scan_threads(nblk)}) {name} by {point if point == 'random' else point % R}"
+        d_want = _dev(want_q)
+        for entry, q in (("sg_fr_kate_division_dev", q1), ("sg_fr_kate_division_rem_dev", q2)):
+            if not torch.equal(q, d_want):
+                _same(q, want_q, f"{what}, {entry}")
+        _same(rem, want_rem, what + ", remainder on the host")
+        _same(rem_dev, want_rem, what + ", remainder on the device")
+    torch.cuda.synchronize()
+    assert (_host(d_a) == _vec(O, name, n, 31)).all(), f"Kate division n={n} {name}: the input changed"
 
 
 @pytest.mark.parametrize("n", pc.KATE_SIZES)
@@ -156,30 +183,20 @@ def test_kate_division(gpu, O, n):
     (n = 2048 b) and just entered (one coefficient in block b), by b = random, 0, 1 and r - 1: quotient, zero padding slot and
     remainder.  `last`: one coefficient at degree n - 1, so every quotient coefficient is that value times a power of b and a
     wrong weight in any block carry shows"""
-    import torch
-    ffi, L = _L()
     nblk = pc.kate_blocks(n)
     assert nblk in pc.KATE_BLOCK_COUNTS
     small = n <= pc.KATE_ALL_CLASSES_UP_TO
     for name in pc.kate_classes(n):
-        d_a = _dev(_vec(O, name, n, 31))
-        for point in (pc.SCALARS if small or name == "last" else ("random", R - 1)):
-            b = pc.scalar(O, point, 32)
-            want_q, want_rem = _kate_want(O, name, n, b, 31)
-            q1, q2, rem_dev, rem = _garbage(32 * n), _garbage(32 * n), _garbage(32), np.zeros(32, dtype=np.uint8)
-            ffi.check(L.sg_fr_kate_division_dev(ffi.dev_ptr(d_a), C.c_size_t(n), ffi.ptr(b), ffi.dev_ptr(q1), ffi.ptr(rem), ffi.current_stream_ptr()))
-            ffi.check(L.sg_fr_kate_division_rem_dev(ffi.dev_ptr(d_a), C.c_size_t(n), ffi.ptr(b), ffi.dev_ptr(q2), ffi.dev_ptr(rem_dev),
-                                                    ffi.current_stream_ptr()))
-            torch.cuda.synchronize()
-            what = f"Kate division n={n} ({nblk} blocks, scan of {pc.kate_scan_threads(nblk)}) {name} by {point if point == 'random' else point % R}"
-            d_want = _dev(want_q)
-            for entry, q in (("sg_fr_kate_division_dev", q1), ("sg_fr_kate_division_rem_dev", q2)):
-                if not torch.equal(q, d_want):
-                    _same(q, want_q, f"{what}, {entry}")
-            _same(rem, want_rem, what + ", remainder on the host")
-            _same(rem_dev, want_rem, what + ", remainder on the device")
-        torch.cuda.synchronize()
-        assert (_host(d_a) == _vec(O, name, n, 31)).all(), f"Kate division n={n} {name}: the input changed"
+        _kate_single_and_rem(O, n, name, pc.SCALARS if small or name == "last" else ("random", R - 1))
+
+
+@pytest.mark.parametrize("n", pc.KATE_SMALL_SIZES)
+def test_kate_division_of_one_block(gpu, O, n):
+    """the same two entry points where the division is one launch without carries: a constant (n = 1: no quotient coefficient,
+    only the padding slot and the remainder), n = 2, and 2047 and 2048 coefficients, the last sizes of one block"""
+    assert pc.kate_blocks(n) == 1
+    for name in pc.KATE_SMALL_CLASSES:
+        _kate_single_and_rem(O, n, name, pc.KATE_SMALL_POINTS)
 
 
 def test_kate_division_refuses_2_21_plus_1(gpu, O):
@@ -213,6 +230,32 @@ def test_kate_division_batch(gpu, O, blocks):
         for j, q in enumerate(outs):
             want_q, _ = _kate_want(O, name, n, pts[32 * j:32 * j + 32].copy(), 41)
             _same(q, want_q, f"Kate division batch n={n} {name}, division {j}")
+
+
+@pytest.mark.parametrize("m", pc.KATE_BATCH_M)
+@pytest.mark.parametrize("n", pc.KATE_BATCH_SMALL_SIZES)
+def test_kate_division_batch_of_one_and_two_blocks(gpu, O, n, m):
+    """sg_fr_kate_division_batch_dev where it runs the write step alone (one block: no carries) and where the first carry
+    appears (two blocks, full and with one coefficient in the second): one division, and sixteen divisions of ONE input at
+    sixteen different points, into outputs pre-filled with garbage; the input is unchanged"""
+    import torch
+    ffi, L = _L()
+    assert pc.kate_blocks(n) in (1, 2) and m <= pc.KATE_BATCH_MAX
+    for name in pc.KATE_SMALL_CLASSES:
+        d_a = _dev(_vec(O, name, n, 45))
+        drawn = O.random_fr(46, m)
+        pts = [drawn[32 * j:32 * j + 32].copy() for j in range(m)]
+        if name == "last":
+            pts[-1] = pc.scalar(O, R - 1, 0)
+        assert len({bytes(p) for p in pts}) == m
+        outs = [_garbage(32 * n) for _ in range(m)]
+        ffi.check(L.sg_fr_kate_division_batch_dev((C.c_void_p * m)(*[d_a.data_ptr()] * m), C.c_size_t(n), ffi.ptr(np.concatenate(pts)), C.c_uint32(m),
+                                                  (C.c_void_p * m)(*[o.data_ptr() for o in outs]), ffi.current_stream_ptr()))
+        torch.cuda.synchronize()
+        for j, q in enumerate(outs):
+            want_q, _ = _kate_want(O, name, n, pts[j], 45)
+            _same(q, want_q, f"Kate division batch n={n} m={m} {name}, division {j}")
+        assert (_host(d_a) == _vec(O, name, n, 45)).all(), f"Kate division batch n={n} m={m} {name}: the input changed"
 
 
 # ============================================================================= evaluation

@@ -1,10 +1,10 @@
 """CPU checks of tests/poly_cases.py, the geometry, generators and case list behind tests/test_gpu_poly_edges.py: the restated
-constants are the ones in csrc/poly.hip and csrc/poly.h, the case list reaches every class of launch (each width of the Kate scan
+constants and rules are the ones csrc/poly_plan.h compiles to, the case list reaches every class of launch (each width of the Kate scan
 exactly full and just entered, both instantiations of the batched evaluation, the first, last and refused block counts, every
 zero pattern of the batch inversion), the generators and closed forms agree with the oracle at small sizes, and the oracle leaves
 the inverse of a zero denominator at zero, as ff::BatchInvert does -- the GPU tests rely on that."""
 import os
-import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -21,30 +21,37 @@ def O():
     return oracle
 
 
-def _constants(text):
-    """`NAME = <integer>` wherever it follows `uint32_t` or a comma in a `static constexpr uint32_t` line"""
-    out = {}
-    for line in text.split("\n"):
-        if line.startswith("static constexpr uint32_t "):
-            for name, value in re.findall(r"\b([A-Z][A-Z0-9_]*) = (\d+)\b", line):
-                out[name] = int(value)
-    return out
-
-
-def test_restated_constants_are_the_ones_in_the_source():
+def test_restated_rules_are_the_compiled_ones(tmp_path):
+    """tests/cpp/poly_plan_check.cpp runs the host geometry the launch functions and the C ABI use (csrc/poly_plan.h, no HIP);
+    the restatement in poly_cases.py must print the same: every constant, and every rule at every size of the case lists, at
+    the refused sizes, at n and n +- 1 for n = 2048 b, and around 2^24 and 2^26 for the evaluations.  The C++ rules are the
+    reference: a difference is fixed in poly_cases.py."""
     from oracle import pyref
-    hip = open(os.path.join(CSRC, "poly.hip")).read()
-    got = dict(_constants(open(os.path.join(CSRC, "poly.h")).read()), **_constants(hip))
-    want = dict(PP_CH=pc.PP_CH, PP_THREADS=pc.PP_THREADS, KD_CH=pc.KD_CH, KD_THREADS=pc.KD_THREADS, BI_CH=pc.BI_CH, EV_THREADS=pc.EV_THREADS,
-                EV_CH=pc.EV_CH, EVAL_BATCH_MAX=pc.EVAL_BATCH_MAX, LINCOMB_MAX=pc.LINCOMB_MAX, LINCOMB_LOW_MAX=pc.LINCOMB_LOW_MAX)
-    assert {k: got.get(k) for k in want} == want
-    assert "PP_BLOCK = PP_CH * PP_THREADS" in hip and "KD_BLOCK = KD_CH * KD_THREADS" in hip
+    exe = str(tmp_path / "poly_plan_check")
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + CSRC, os.path.join(ROOT, "tests", "cpp", "poly_plan_check.cpp"),
+                           "-o", exe])
+    sizes = {(n, 1) for n in pc.PREFIX_SIZES + pc.KATE_SIZES + pc.EVAL_SIZES + pc.EVAL_BATCH_TILED + pc.KATE_SMALL_SIZES + pc.KATE_BATCH_SMALL_SIZES}
+    sizes |= {(n, 1) for n in (pc.PREFIX_REFUSED, pc.KATE_REFUSED, pc.EVAL_BATCH_REFUSED) + pc.PLAN_EVAL_EDGES}
+    sizes |= set(pc.EVAL_BATCH_SHAPES) | {(pc.KD_BLOCK * b + d, m) for b in pc.PLAN_EDGE_BLOCKS for d in (-1, 0, 1) for m in (1, 3, pc.KATE_BATCH_MAX)}
+    sizes |= {(1 << 26, 41), (4097, 80), (4097, 81)}
+    sizes = sorted(sizes)
+    prefixes = sorted({(n, c) for n, _ in sizes for c in (0, n, n + 1, n + 2)} | {((1 << 21) + 1, 0)})
+    terms = list(range(0, 2 * pc.LINCOMB_MAX + 1))
+    text = "".join(f"size {n} {m}\n" for n, m in sizes) + "".join(f"prefix {n} {c}\n" for n, c in prefixes) + "".join(f"lincomb {m}\n" for m in terms)
+    got = subprocess.run([exe], input=text, capture_output=True, text=True, check=True).stdout.split("\n")[:-1]
+    want = [pc.plan_constants()] + [pc.plan_line(n, m) for n, m in sizes]
+    want += [f"prefix n={n} count_out={c} blocks={'none' if pc.prefix_blocks(n, c) is None else pc.prefix_blocks(n, c)}" for n, c in prefixes]
+    want += [f"lincomb m={m} mid={','.join(map(str, pc.lincomb_mid_reductions(m))) or '-'}" for m in terms]
+    assert len(got) == len(want)
+    for g, w in zip(got, want):
+        assert g == w
+    # requests as arguments give the same answers
+    by_args = subprocess.run([exe, "size 2049 16", "lincomb 32"], capture_output=True, text=True, check=True).stdout.split("\n")[:-1]
+    assert by_args == [pc.plan_constants(), pc.plan_line(2049, 16), "lincomb m=32 mid=31"]
     assert pc.PP_BLOCK == pc.KD_BLOCK == 2048 and (pc.R, pc.MONT) == (pyref.R, pyref.MONT)
-    # the rules the restatement copies, as the host code states them
-    assert "(n <= ((size_t)1 << 24) ? 16 : 32) * EV_THREADS" in hip and "blocks > (small ? 16u : 32u) * EV_THREADS" in hip
-    assert "uint32_t scan_threads = 64;" in hip and "while (scan_threads < nblk) scan_threads <<= 1;" in hip
-    assert "if ((j & 31) == 30)" in hip and "(span + PP_BLOCK - 1) / PP_BLOCK" in hip and "(n + KD_BLOCK - 1) / KD_BLOCK" in hip
-    assert "__launch_bounds__(1024) prefix_product_scan_blocks" in hip and "__launch_bounds__(1024) kate_scan_blocks" in hip
+    # the kernels take the same rules: the scans are one workgroup of at most POLY_SCAN_MAX threads
+    scan = open(os.path.join(CSRC, "poly_scan.cuh")).read()
+    assert "__launch_bounds__(1024) prefix_product_scan_blocks_batch" in scan and "__launch_bounds__(1024) kate_scan_blocks" in scan
 
 
 def test_geometry_at_the_edges():
