@@ -285,13 +285,33 @@ hipError_t build_window_table(const g1_affine_mem* d_bases, size_t n, uint32_t c
   return hipSuccess;
 }
 
-// points[i] on y^2 = x^3 + 3 (or the identity, 64 zero bytes)?  *bad counts the points that are not
+// is the 256-bit value of 8 LE words below the modulus?  (borrow chain of w - p over exactly normalised limbs)
+template <class P>
+__device__ __forceinline__ bool words_below_p(const uint32_t w[8]) {
+  const f29 a = f29_from_words<0>(w);
+  uint32_t borrow = 0;
+#pragma unroll
+  for (int i = 0; i < 9; i++) borrow = (a.l[i] - P::p[i] - borrow) >> 31;
+  return borrow != 0;
+}
+// points[i] on y^2 = x^3 + 3 (or the identity, 64 zero bytes)?  *bad counts the points that are not.  A coordinate whose
+// words are not below q is bad whatever its residue (halo2curves' from_raw_bytes refuses it, and so does sg_pairing_check)
 __global__ void __launch_bounds__(256) g1_on_curve_kernel(const g1_affine_mem* __restrict__ points, uint32_t n, uint32_t* bad) {
   typedef Fq29 P;
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const affine29 p = affine29_load(points + i);
+  uint32_t w[16];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const uint4 v = points[i].q[k];
+    w[4 * k] = v.x; w[4 * k + 1] = v.y; w[4 * k + 2] = v.z; w[4 * k + 3] = v.w;
+  }
+  const affine29 p = affine29_from_words(w);
   if (p.inf) return;
+  if (!words_below_p<P>(w) || !words_below_p<P>(w + 8)) {
+    atomicAdd(bad, 1u);
+    return;
+  }
   const f29 one = f29_one<P>();
   const f29 x = f29_mul<P>(p.x, one), y = f29_mul<P>(p.y, one);       // bound 32 -> < 2
   const f29 x3 = f29_mul<P>(f29_sqr<P>(x), x), y2 = f29_sqr<P>(y);

@@ -86,8 +86,12 @@ __global__ void kzg_setup_scalars(uint32_t k, words8 tau_w, fp_words* pw, fp_wor
   f29 n = f29_one<P>();
   for (uint32_t q = 0; q < k; q++) n = f29_cond_sub_p<P>(f29_normalize(f29_dbl(n)));
   const f29 wi = f29_pow_u64<P>(omega, i);
-  f29 den = f29_mul<P>(n, f29_sub<P, 0>(tau, wi));             // n (tau - omega^i)
+  const f29 diff = f29_sub<P, 0>(tau, wi);
+  f29 den = f29_mul<P>(n, diff);                               // n (tau - omega^i)
   f29 l = f29_mul<P>(f29_mul<P>(wi, num), f29_inv<P>(den));
+  // tau is the domain point omega^i: 0 / 0 above (the inverse of 0 is 0), and L_i(omega^i) = 1 by definition; num is zero
+  // for the whole domain then, so every other row is 0 already
+  if (f29_is_zero_mod_p<P>(diff)) l = f29_one<P>();
   f29_to_words(f29_reduce_with<P>(l, P::r256), o);
   fp_words_store(lg + i, o);
 }
