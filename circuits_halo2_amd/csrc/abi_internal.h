@@ -76,9 +76,7 @@ struct Context {
   hipEvent_t ev_in = nullptr;
   DevBuf<uint8_t> stage_a, stage_b, scratch;
   std::vector<uint8_t> gate_blob_host;
-  std::map<uint64_t, GateProgram> gate_cache;  // lowered gate programs by structure hash
-  uint64_t gate_recent[4] = {0, 0, 0, 0};      // keys of the programs used last (tried first, by comparison)
-  uint32_t gate_recent_next = 0;
+  GateProgramCache gate_programs;   // lowered gate programs by structure (gates_compile.h)
   // in-place multi-pass transforms need a scratch vector; one per caller stream, so that transforms
   // enqueued on a side stream never share it with work in flight on another stream
   std::map<hipStream_t, DevBuf<uint8_t>> ntt_scratch;

@@ -134,80 +134,14 @@ int sg_quotient_lookup_cosets_dev(void* d_values, const void* d_z, const void* d
 }
 
 // the lowered program of a graph, from the lane's cache (compiled on first sight), with its constant table refreshed for this
-// call: constants ++ challenges ++ beta, gamma, theta, y (compile_gates' order).  The caller holds the lane.
+// call.  The caller holds the lane.
 static int gate_program_for(const sg_graph* graph, uint32_t n_fixed, uint32_t n_advice, uint32_t n_instance, const uint8_t* challenges,
                             uint32_t n_challenges, const uint8_t beta[32], const uint8_t gamma[32], const uint8_t theta[32],
                             const uint8_t y[32], GateProgram** out) {
-  // the lowered program depends on the graph's structure only (constants / challenges are a table refreshed per call):
-  // cached under the structure itself.  A prover sends the same two programs proof after proof, so the lane's most recent
-  // hits are tried first with one memcmp each (the structure of the reference circuit's gate program is 100+ KB: hashing
-  // it byte by byte cost 0.3 ms of host time per proof, with the device idle behind it)
-  std::vector<uint8_t> sig;
-  {
-    const uint32_t hdr[8] = {graph->n_constants, graph->n_rotations, graph->n_calculations, graph->n_horner_parts, n_fixed,
-                             n_advice, n_instance, n_challenges};
-    const size_t parts[4] = {sizeof hdr, graph->rotations ? sizeof(int32_t) * graph->n_rotations : 0,
-                             graph->calculations ? sizeof(sg_calculation) * graph->n_calculations : 0,
-                             graph->horner_parts ? sizeof(sg_value_source) * graph->n_horner_parts : 0};
-    const void* src[4] = {hdr, graph->rotations, graph->calculations, graph->horner_parts};
-    sig.resize(parts[0] + parts[1] + parts[2] + parts[3]);
-    size_t at = 0;
-    for (int i = 0; i < 4; i++) {
-      if (parts[i]) std::memcpy(sig.data() + at, src[i], parts[i]);
-      at += parts[i];
-    }
-  }
-  auto hit = g_ctx->gate_cache.end();
-  for (uint64_t recent : g_ctx->gate_recent) {
-    auto it = g_ctx->gate_cache.find(recent);
-    if (it != g_ctx->gate_cache.end() && it->second.signature == sig) {
-      hit = it;
-      break;
-    }
-  }
-  uint64_t key = 1469598103934665603ull;
-  if (hit == g_ctx->gate_cache.end()) {
-    size_t i = 0;
-    for (; i + 8 <= sig.size(); i += 8) {
-      uint64_t w;
-      std::memcpy(&w, sig.data() + i, 8);
-      key = (key ^ w) * 1099511628211ull;
-    }
-    for (; i < sig.size(); i++) key = (key ^ sig[i]) * 1099511628211ull;
-    hit = g_ctx->gate_cache.find(key);
-    if (hit != g_ctx->gate_cache.end() && hit->second.signature != sig) {  // 64-bit collision: recompile
-      g_ctx->gate_cache.erase(hit);
-      hit = g_ctx->gate_cache.end();
-    }
-  }
-  std::string err = "";
-  if (hit == g_ctx->gate_cache.end()) {
-    GateProgram fresh;
-    err = compile_gates(*graph, n_fixed, n_advice, n_instance, challenges, n_challenges, beta, gamma, theta, y, &fresh);
-    if (!err.empty()) return fail(SG_ERR_INVALID, ("sg_quotient_gates: " + err).c_str());
-    fresh.signature = std::move(sig);
-    if (g_ctx->gate_cache.size() >= 64) g_ctx->gate_cache.clear();
-    hit = g_ctx->gate_cache.emplace(key, std::move(fresh)).first;
-  }
-  {
-    bool listed = false;
-    for (uint64_t recent : g_ctx->gate_recent) listed = listed || recent == hit->first;
-    if (!listed) g_ctx->gate_recent[g_ctx->gate_recent_next++ % 4] = hit->first;
-  }
-  GateProgram& prog = hit->second;
+  const std::string err = g_ctx->gate_programs.lookup_or_compile(*graph, n_fixed, n_advice, n_instance, n_challenges, gates_env().lowering, out);
+  if (!err.empty()) return fail(SG_ERR_INVALID, ("sg_quotient_gates: " + err).c_str());
   if ((graph->n_constants && !graph->constants)) return fail(SG_ERR_INVALID, "sg_quotient_gates: null constants");
-  {  // constant table of this call: constants ++ challenges ++ beta, gamma, theta, y (compile_gates' order)
-    prog.const_words.clear();
-    auto push = [&](const uint8_t* p) {
-      uint32_t w[8];
-      std::memcpy(w, p, 32);
-      prog.const_words.insert(prog.const_words.end(), w, w + 8);
-    };
-    for (uint32_t i = 0; i < graph->n_constants; i++) push(graph->constants + 32 * (size_t)i);
-    for (uint32_t i = 0; i < n_challenges; i++) push(challenges + 32 * (size_t)i);
-    push(beta); push(gamma); push(theta); push(y);
-  }
-  *out = &prog;
+  gate_const_table(*graph, challenges, n_challenges, beta, gamma, theta, y, &(*out)->const_words);
   return SG_OK;
 }
 static int quotient_gates_impl(void* d_values, const sg_graph* graph, const void* const* d_fixed, uint32_t n_fixed,
@@ -223,7 +157,8 @@ static int quotient_gates_impl(void* d_values, const sg_graph* graph, const void
   GateProgram* prog_p = nullptr;
   TRY(gate_program_for(graph, n_fixed, n_advice, n_instance, challenges, n_challenges, beta, gamma, theta, y, &prog_p));
   GateProgram& prog = *prog_p;
-  if (prog.n_slots > 64) return fail(SG_ERR_INVALID, "sg_quotient_gates: more than 64 simultaneously live values");
+  static_assert(GATES_MAX_SLOTS == 64, "the message below names the limit");
+  if (prog.n_slots > GATES_MAX_SLOTS) return fail(SG_ERR_INVALID, "sg_quotient_gates: more than 64 simultaneously live values");
   std::vector<const void*> cols;
   for (uint32_t i = 0; i < n_fixed; i++) cols.push_back(d_fixed[i]);
   for (uint32_t i = 0; i < n_advice; i++) cols.push_back(d_advice[i]);
@@ -301,7 +236,7 @@ int sg_quotient_numerator_cosets_dev(void* d_values, const sg_graph* gates, cons
   bool fused = false;
   if (g_sh.param[kRowFusedNumerator].load() && n_fixed + n_advice + n_instance <= NUM_MAX_COLS) {
     LOCKED_CTX();
-    if (g_ctx->gate_cache.size() >= 62) g_ctx->gate_cache.clear();   // neither look-up below may evict the other's program
+    g_ctx->gate_programs.reserve(2);   // neither look-up below may evict the other's program
     GateProgram *pg = nullptr, *pi = nullptr;
     const uint8_t none[32] = {0};
     TRY(gate_program_for(gates, n_fixed, n_advice, n_instance, challenges, n_challenges, beta, gamma, theta, y, &pg));
@@ -351,32 +286,32 @@ int sg_quotient_numerator_cosets_dev(void* d_values, const sg_graph* gates, cons
                                        beta, gamma, y, k, n_cosets, stream);
 }
 
+// the lowered program itself, for tooling (tools/gen_gates_programs.py writes the ahead-of-time instantiations of the reference
+// circuit's programs from it) and tests.  Host-only: no device is touched, no cache either.
+static int lowered_program(const char* who, const sg_graph* graph, uint32_t n_fixed, uint32_t n_advice, uint32_t n_instance,
+                           uint32_t n_challenges, GateProgram* prog) {
+  const std::string err = compile_gates(*graph, n_fixed, n_advice, n_instance, n_challenges, gates_env().lowering, prog);
+  if (!err.empty()) return fail(SG_ERR_INVALID, (std::string(who) + ": " + err).c_str());
+  return SG_OK;
+}
 // how the interpreter would run a program: instructions and simultaneously live values (LDS slots per row; 8 or fewer keep
-// two workgroups of 256 rows per CU).  Host-only: no device is touched.
+// two workgroups of 256 rows per CU)
 int sg_gates_program_info(const sg_graph* graph, uint32_t n_fixed, uint32_t n_advice, uint32_t n_instance, uint32_t n_challenges,
                           uint32_t* n_ops_out, uint32_t* n_slots_out) {
   if (!graph || !n_ops_out || !n_slots_out) return fail(SG_ERR_INVALID, "sg_gates_program_info: null argument");
-  std::vector<uint8_t> zeros(32 * (size_t)std::max<uint32_t>(1, n_challenges), 0);
   GateProgram prog;
-  const std::string err = compile_gates(*graph, n_fixed, n_advice, n_instance, zeros.data(), n_challenges, zeros.data(), zeros.data(),
-                                        zeros.data(), zeros.data(), &prog);
-  if (!err.empty()) return fail(SG_ERR_INVALID, ("sg_gates_program_info: " + err).c_str());
+  TRY(lowered_program("sg_gates_program_info", graph, n_fixed, n_advice, n_instance, n_challenges, &prog));
   *n_ops_out = (uint32_t)prog.ops.size();
   *n_slots_out = prog.n_slots;
   return SG_OK;
 }
-
-// the lowered program itself, for tooling (tools/gen_gates_programs.py writes the ahead-of-time instantiations of the reference
-// circuit's programs from it) and tests: words_out = [n_slots, result_kind, result_index, n_ops, then (w0, dst, a, b) per
-// instruction].  *n_words_out is the size needed; nothing is written beyond cap_words.  Host only.
+// words_out = [n_slots, result_kind, result_index, n_ops, then (w0, dst, a, b) per instruction].  *n_words_out is the size
+// needed; nothing is written beyond cap_words.
 int sg_gates_program_words(const sg_graph* graph, uint32_t n_fixed, uint32_t n_advice, uint32_t n_instance, uint32_t n_challenges,
                            uint32_t* words_out, uint32_t cap_words, uint32_t* n_words_out) {
   if (!graph || !n_words_out || (cap_words && !words_out)) return fail(SG_ERR_INVALID, "sg_gates_program_words: null argument");
-  std::vector<uint8_t> zeros(32 * (size_t)std::max<uint32_t>(1, n_challenges), 0);
   GateProgram prog;
-  const std::string err = compile_gates(*graph, n_fixed, n_advice, n_instance, zeros.data(), n_challenges, zeros.data(), zeros.data(),
-                                        zeros.data(), zeros.data(), &prog);
-  if (!err.empty()) return fail(SG_ERR_INVALID, ("sg_gates_program_words: " + err).c_str());
+  TRY(lowered_program("sg_gates_program_words", graph, n_fixed, n_advice, n_instance, n_challenges, &prog));
   std::vector<uint32_t> w = {prog.n_slots, prog.result_kind, prog.result_index, (uint32_t)prog.ops.size()};
   for (const GateOp& o : prog.ops) { w.push_back(o.w0); w.push_back(o.dst); w.push_back(o.a); w.push_back(o.b); }
   *n_words_out = (uint32_t)w.size();

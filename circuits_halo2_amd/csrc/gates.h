@@ -1,37 +1,30 @@
-// Custom-gate block of halo2's evaluate_h: an interpreter for GraphEvaluator programs (see gates.hip).
+// Custom-gate block of halo2's evaluate_h: an interpreter for GraphEvaluator programs (see gates.hip) and the straight-line
+// kernels of the programs known ahead of time.  The host side -- the lowering, the tile rule, the program cache -- is
+// gates_compile.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <string>
 #include <vector>
 
-#include "../../include/summa_gpu.h"
+#include "gates_compile.h"
 #include "msm.h"
 
 namespace sg {
 
-struct GateOp {  // one instruction of the compiled program (4 words, read with scalar loads)
-  uint32_t w0;   // opcode | kidx << 8 | a_kind << 16 | b_kind << 24   (MULADD: the kidx byte holds the kind of c)
-  uint32_t dst;  // LDS slot (low 16 bits); MULADD: the third operand c in the high 16 bits
-  uint32_t a, b; // slot / constant index / (LOADCOL: column index, rotation)
-};
-// G_RED: the same residue below 2p (f29_reduce_small); G_MULADD: a * b + c under one reduction (f29_mul_add)
-enum GateOpcode : uint32_t { G_LOADCOL, G_LOADPREV, G_ADD, G_SUB, G_MUL, G_SQR, G_DBL, G_NEG, G_RED, G_MULADD };
-enum GateOperandKind : uint32_t { GK_SLOT = 0, GK_CONST = 1 };
+// what a program known ahead of time may have for its columns and constants to travel as kernel arguments (GateArgsV in
+// gates.hip, NumeratorArgs in numerator.h)
+static constexpr uint32_t GATES_V_COLS = 24, GATES_V_CONSTS = 40;
 
-struct GateProgram {
-  std::vector<GateOp> ops;
-  std::vector<uint32_t> const_words;  // 8 words per constant (memory-domain Fr)
-  uint32_t n_slots = 0, result_kind = GK_SLOT, result_index = 0;
-  uint32_t n_columns = 0;             // fixed ++ advice ++ instance
-  std::vector<uint8_t> signature;     // structure bytes this program was lowered from (cache confirmation)
+// The development aids, read from the environment at every call (tests switch them between calls):
+//   SG_GATES_GENERIC   every program runs in the interpreter          SG_GATES_DEBUG    one line per launch on stderr
+//   SG_GATES_ROWS      the interpreter's rows per workgroup           SG_GATES_RELOAD, SG_GATES_CONVERT   GateLowering
+struct GateEnv {
+  bool generic, debug;
+  uint32_t rows;
+  GateLowering lowering;
 };
-
-// halo2-shaped graph -> compiled program (bound tracking, lazy reductions, slot allocation).
-// Returns an empty string on success, a message otherwise.
-std::string compile_gates(const sg_graph& g, uint32_t n_fixed, uint32_t n_advice, uint32_t n_instance,
-                          const uint8_t* challenges, uint32_t n_challenges, const uint8_t beta[32],
-                          const uint8_t gamma[32], const uint8_t theta[32], const uint8_t y[32], GateProgram* out);
+GateEnv gates_env();
 
 // a program the library has straight-line code for (the reference circuit's gate programs and its lookup input): launched with
 // columns and constants as kernel arguments -- no blob; returns false (nothing launched) for any other program

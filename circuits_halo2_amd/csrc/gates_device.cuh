@@ -2,6 +2,7 @@
 // quotient numerator): kernel arguments, the ahead-of-time program tables and their straight-line evaluation.
 #pragma once
 #include <cstring>
+#include <type_traits>
 
 #include "gates.h"
 
@@ -27,7 +28,7 @@ struct GateSrc {
 };
 
 // ---- the same, for a program known at compile time (gates_mst_programs.inc: the reference circuit's own gate programs as
-// lowered by compile_gates below; tools/gen_gates_programs.py).  Every instruction is a template instantiation: the
+// lowered by compile_gates, gates_compile.h; tools/gen_gates_programs.py).  Every instruction is a template instantiation: the
 // operands are registers (slot[] is indexed by constants only), there is no instruction fetch or decode and no LDS round
 // trip per instruction -- what remains of the interpreter's ~50 instructions of overhead per op is the constants' LDS
 // reads.  gates_run uses it when the program it is given is word for word one of the tables; SG_GATES_GENERIC=1 keeps
@@ -99,4 +100,19 @@ static bool is_program(const GateProgram& p) {
   return p.ops.size() == PROG::n_ops && p.n_slots == PROG::n_slots && p.result_kind == PROG::result_kind &&
          p.result_index == PROG::result_index && std::memcmp(p.ops.data(), PROG::ops, sizeof(GateOp) * PROG::n_ops) == 0;
 }
+// THE list of the programs known ahead of time: f(table type{}, its name) for the one `p` is, word for word (the tables differ,
+// so at most one is); returns whether there was one
+template <class F>
+static bool for_known_gate_program(const GateProgram& p, F&& f) {
+  if (is_program<MstLookupInput>(p)) return f(MstLookupInput{}, "MstLookupInput"), true;
+  if (is_program<MstGatesNc2>(p)) return f(MstGatesNc2{}, "MstGatesNc2"), true;
+  if (is_program<MstGatesNc1>(p)) return f(MstGatesNc1{}, "MstGatesNc1"), true;
+  if (is_program<MstGatesNc3>(p)) return f(MstGatesNc3{}, "MstGatesNc3"), true;
+  if (is_program<MstGatesNc4>(p)) return f(MstGatesNc4{}, "MstGatesNc4"), true;
+  return false;
+}
+// the lookup input is known by value only (gates_run_by_value) and as the fused numerator's second program: the blob-form
+// kernel and the numerator's first program are instantiated for the circuit's gate programs alone
+template <class PROG>
+constexpr bool is_circuit_gate_program = !std::is_same<PROG, MstLookupInput>::value;
 }  // namespace sg

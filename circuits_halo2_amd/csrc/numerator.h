@@ -6,7 +6,8 @@
 #include "quotient.h"
 
 namespace sg {
-static constexpr uint32_t NUM_MAX_CONSTS = 40, NUM_MAX_INPUT_CONSTS = 8, NUM_MAX_COLS = 24;
+// (the gate program's columns and constants travel as in gates_run_by_value: the same limits)
+static constexpr uint32_t NUM_MAX_CONSTS = GATES_V_CONSTS, NUM_MAX_INPUT_CONSTS = 8, NUM_MAX_COLS = GATES_V_COLS;
 struct NumeratorArgs {   // kernel argument (by value: no blob upload, nothing to keep alive)
   fp_words* values;                               // out: cosets * 2^k rows, every row written
   const fp_words* cols[NUM_MAX_COLS];             // fixed ++ advice ++ instance, coset-major, as the gate programs index them

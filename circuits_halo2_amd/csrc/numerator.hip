@@ -14,7 +14,6 @@
 #include "numerator.h"
 
 #include <cstdio>
-#include <cstdlib>
 
 #include "gates_device.cuh"
 #include "quotient_device.cuh"
@@ -70,17 +69,20 @@ __global__ void __launch_bounds__(256) numerator_fused_kernel(NumeratorArgs a) {
 
 template <class F>
 static bool for_known_pair(const GateProgram& g, const GateProgram& in, F&& f) {
-  if (!is_program<MstLookupInput>(in)) return false;
-  if (is_program<MstGatesNc2>(g)) return f(MstGatesNc2{}, 2), true;
-  if (is_program<MstGatesNc1>(g)) return f(MstGatesNc1{}, 1), true;
-  if (is_program<MstGatesNc3>(g)) return f(MstGatesNc3{}, 3), true;
-  if (is_program<MstGatesNc4>(g)) return f(MstGatesNc4{}, 4), true;
-  return false;
+  bool found = false;
+  if (is_program<MstLookupInput>(in))
+    for_known_gate_program(g, [&](auto tag, const char* name) {
+      if constexpr (is_circuit_gate_program<decltype(tag)>) {
+        found = true;
+        f(tag, name);
+      }
+    });
+  return found;
 }
 bool numerator_fused_available(const GateProgram& gates, const GateProgram& lookup_input) {
   if (gates.const_words.size() / 8 > NUM_MAX_CONSTS || lookup_input.const_words.size() / 8 > NUM_MAX_INPUT_CONSTS) return false;
   if (gates.n_columns > NUM_MAX_COLS || lookup_input.n_columns != gates.n_columns) return false;
-  return for_known_pair(gates, lookup_input, [](auto, int) {});
+  return for_known_pair(gates, lookup_input, [](auto, const char*) {});
 }
 hipError_t numerator_fused(const GateProgram& gates, const GateProgram& lookup_input, NumeratorArgs& a, hipStream_t stream) {
   // one program object in both roles would be one constant table serving two programs
@@ -92,10 +94,10 @@ hipError_t numerator_fused(const GateProgram& gates, const GateProgram& lookup_i
   std::memcpy(a.input_consts, lookup_input.const_words.data(), lookup_input.const_words.size() * sizeof(uint32_t));
   const size_t n_ext = (size_t)a.perm.cosets << a.perm.k;
   const unsigned blocks = (unsigned)((n_ext + 255) / 256);
-  for_known_pair(gates, lookup_input, [&](auto tag, int nc) {
+  const GateEnv env = gates_env();
+  for_known_pair(gates, lookup_input, [&](auto tag, const char* name) {
     using G = decltype(tag);
-    if (std::getenv("SG_GATES_DEBUG"))
-      std::fprintf(stderr, "gates: ahead-of-time program MstGatesNc%d inside the one-pass numerator, %u blocks\n", nc, blocks);
+    if (env.debug) std::fprintf(stderr, "gates: ahead-of-time program %s inside the one-pass numerator, %u blocks\n", name, blocks);
     numerator_fused_kernel<G, MstLookupInput><<<blocks, 256, 0, stream>>>(a);
   });
   return hipGetLastError();

@@ -166,7 +166,7 @@ def lookup_expressions():
 #   * no fold is in gate order any more, so the needed powers of y come in as challenges (gate_challenge_exponents);
 #     every term is added to the running value as soon as it is complete and its operands die.
 # 53 products per row instead of 73, and 8 simultaneously live values instead of 13 under the interpreter's allocator
-# (csrc/gates.hip; `arithmetic.gates_program_info`): the kernel's occupancy is set by that number (LDS slots per row).
+# (csrc/gates_compile.h; `arithmetic.gates_program_info`): the kernel's occupancy is set by that number (LDS slots per row).
 # tests: the value against `gates()` folded with y on the CPU (test_verifier_cpu.py) and row by row on the GPU
 # (test_gpu_parity.py), the proofs against the verifier.
 @lru_cache(maxsize=None)

@@ -431,7 +431,7 @@ int sg_quotient_lookup_cosets_dev(void* d_values, const void* d_z, const void* d
  * values[row] being available as SG_VS_PREVIOUS_VALUE (upstream ends its program with
  * Horner(PreviousValue, gate polynomials, Y)).  Column sources name (column index, index into
  * rotations[]); a rotation r reads row + r * 2^(ext_k - k).  The program is compiled per call into a
- * straight-line LDS-slot program (csrc/gates.hip); at most 64 simultaneously live values. */
+ * straight-line LDS-slot program (csrc/gates_compile.h); at most 64 simultaneously live values. */
 enum { SG_VS_CONSTANT = 0, SG_VS_INTERMEDIATE = 1, SG_VS_FIXED = 2, SG_VS_ADVICE = 3, SG_VS_INSTANCE = 4,
        SG_VS_CHALLENGE = 5, SG_VS_BETA = 6, SG_VS_GAMMA = 7, SG_VS_THETA = 8, SG_VS_Y = 9, SG_VS_PREVIOUS_VALUE = 10 };
 enum { SG_OP_ADD = 0, SG_OP_SUB = 1, SG_OP_MUL = 2, SG_OP_SQUARE = 3, SG_OP_DOUBLE = 4, SG_OP_NEGATE = 5,

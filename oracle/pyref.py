@@ -348,6 +348,45 @@ def random_fr(seed: int, n: int):
     return out
 
 
+def eval_graph(graph, column, challenges, beta, gamma, theta, y, previous):
+    """halo2's GraphEvaluator::evaluate (plonk/evaluation.rs) for one row over integers mod r: the value of the last calculation.
+    graph: {"constants": [int], "rotations": [int], "calculations": [(op, a, b[, parts])]} with value sources (kind, index,
+    rotation index), numbered as in include/summa_gpu.h; column(kind, index, rotation) -> the column's value at row + rotation.
+    Only the calculations the result depends on are evaluated."""
+    calcs = graph["calculations"]
+    operands = lambda cal: [cal[1]] + ([cal[2]] if cal[0] <= 2 or cal[0] == 6 else []) + (list(cal[3]) if cal[0] == 6 else [])
+    reached, todo = set(), [len(calcs) - 1]
+    while todo:
+        q = todo.pop()
+        if q not in reached:
+            reached.add(q)
+            todo += [s[1] for s in operands(calcs[q]) if s[0] == 1]
+    fixed = {6: beta, 7: gamma, 8: theta, 9: y, 10: previous}
+    inter = {}
+
+    def value(s):
+        kind, index, rot = s
+        if kind == 0:
+            return graph["constants"][index] % R
+        if kind == 1:
+            return inter[index]
+        if kind in (2, 3, 4):
+            return column(kind, index, graph["rotations"][rot]) % R
+        return (challenges[index] if kind == 5 else fixed[kind]) % R
+
+    for q in sorted(reached):
+        op, a = calcs[q][0], value(calcs[q][1])
+        if op == 6:   # Horner(start, parts, factor)
+            f = value(calcs[q][2])
+            for part in calcs[q][3]:
+                a = (a * f + value(part)) % R
+            inter[q] = a
+        else:
+            b = value(calcs[q][2]) if op <= 2 else 0
+            inter[q] = [a + b, a - b, a * b, a * a, 2 * a, -a, None, a][op] % R
+    return inter[len(calcs) - 1]
+
+
 # --- witness side (SURVEY.md §8a row W, §8f-4): Poseidon Merkle sum tree ---------------------
 # zk_prover/src/merkle_sum_tree/{entry.rs:15-27, node.rs:16-84, utils/build_tree.rs:5-78,
 # utils/operation_helpers.rs:10-12, mst.rs:74-134}; Poseidon = halo2_gadgets' Pow5 sponge with

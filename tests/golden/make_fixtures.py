@@ -11,6 +11,11 @@ Fixtures are DATA:
                      big-integer twin oracle/pyref.py (NTT 2^4, coeff_to_extended 2^4->2^7,
                      MSM answers as f(tau)*G).
   ntt_k11_{in,out}.bin, msm_tau_k10_{scalars,bases}.bin   pyref-generated vectors.
+  gates_lowering.json   what the gate compiler (csrc/gates_compile.h) makes of every graph of tests/gates_cases.py: the
+                     SHA-256 of the lowered words [n_slots, result_kind, result_index, n_ops, ops...] or the error message,
+                     through the built library.  Recorded before the compiler moved out of gates.hip; `make_fixtures.py
+                     gates_lowering` rewrites this file alone (needs no reference tree) -- only after a deliberate change
+                     of the lowering, together with csrc/gates_mst_programs.inc.
   entry_*.csv        byte copies of the reference's CSV data fixtures csv/*.csv (the inputs of its Merkle-sum-tree and
                      circuit tests: 13 / 16 / 17 entries, switched order, one modified entry, big integers, an overflowing balance).
 """
@@ -37,6 +42,20 @@ def copy_csvs():
     for name in CSVS:
         shutil.copyfile(os.path.join(REF, "csv", name), os.path.join(HERE, name))
         os.chmod(os.path.join(HERE, name), 0o644)
+
+
+def gates_lowering():
+    sys.path.insert(0, os.path.join(HERE, ".."))
+    import gates_cases
+    from oracle import oracle
+    out = {c.name: gates_cases.library_lowering(c) for c in gates_cases.corpus(oracle)}
+    path = os.path.join(HERE, "gates_lowering.json")
+    was = json.load(open(path)) if os.path.exists(path) else {}
+    moved = sorted(n for n in set(was) | set(out) if was.get(n) != out.get(n))
+    if was and moved:
+        print("gates_lowering.json: RE-RECORDED, the built library lowers", len(moved), "graphs differently from the committed file:", ", ".join(moved[:8]))
+    json.dump(out, open(path, "w"), indent=0)
+    print("gates_lowering.json:", len(out), "graphs,", sum("error" in v for v in out.values()), "refused")
 
 
 def main():
@@ -112,8 +131,9 @@ def main():
     import hashlib
     kat["poseidon_t2_sha256"] = hashlib.sha256(repr((rcs, mds)).encode()).hexdigest()
     json.dump(kat, open(os.path.join(HERE, "kat.json"), "w"), indent=1)
+    gates_lowering()
     print("fixtures written to", HERE)
 
 
 if __name__ == "__main__":
-    main()
+    gates_lowering() if sys.argv[1:] == ["gates_lowering"] else main()

@@ -1300,41 +1300,7 @@ def test_lincomb(gpu, O):
 
 
 # ----------------------------------------------------------------------------- §8f-1: custom gates (GraphEvaluator)
-def _random_graph(rng, n_fixed, n_advice, n_instance, n_chal, n_calc, O):
-    """a random, valid GraphEvaluator program that exercises every calculation and value source"""
-    from circuits_halo2_amd import arithmetic as A
-    g = A.GraphEvaluator()
-    consts = [g.add_constant(O.random_fr(int(rng.integers(1 << 30)), 1)) for _ in range(3)]
-    consts.append(g.add_constant(fr_np([0])))
-    consts.append(g.add_constant(fr_np([1])))
-    rots = [0, 1, -1, 2, -5]
-
-    def src(upto):
-        kind = int(rng.integers(0, 8))
-        if kind == 0:
-            return consts[int(rng.integers(len(consts)))]
-        if kind in (1, 2) and upto:
-            return (A.INTERMEDIATE, int(rng.integers(max(0, upto - 6), upto)), 0)   # mostly recent values
-        if kind == 3 and n_fixed:
-            return g.query(A.FIXED, int(rng.integers(n_fixed)), rots[int(rng.integers(len(rots)))])
-        if kind == 4 and n_instance:
-            return g.query(A.INSTANCE, int(rng.integers(n_instance)), rots[int(rng.integers(2))])
-        if kind == 5 and n_chal:
-            return (A.CHALLENGE, int(rng.integers(n_chal)), 0)
-        if kind == 6:
-            return (int(rng.choice([A.BETA, A.GAMMA, A.THETA, A.Y, A.PREVIOUS_VALUE])), 0, 0)
-        return g.query(A.ADVICE, int(rng.integers(n_advice)), rots[int(rng.integers(len(rots)))])
-
-    while len(g.calculations) < n_calc:
-        q = len(g.calculations)
-        op = int(rng.choice([A.ADD, A.ADD, A.SUB, A.SUB, A.MUL, A.MUL, A.SQUARE, A.DOUBLE, A.NEGATE, A.HORNER, A.STORE]))
-        if op == A.HORNER:
-            g.add_calculation(op, src(q), src(q), [src(q) for _ in range(int(rng.integers(0, 5)))])
-        elif op in (A.SQUARE, A.DOUBLE, A.NEGATE, A.STORE):
-            g.add_calculation(op, src(q))
-        else:
-            g.add_calculation(op, src(q), src(q))
-    return g
+from gates_cases import random_graph as _random_graph  # noqa: E402  (the CPU corpus of the gate compiler draws from it too)
 
 
 @pytest.mark.parametrize("seed,k,ext_k,n_calc", [(1, 4, 6, 8), (2, 5, 7, 40), (3, 9, 12, 120), (4, 10, 13, 300),
@@ -1357,8 +1323,9 @@ def test_quotient_gates_random_programs(gpu, O, seed, k, ext_k, n_calc):
 
 
 def test_quotient_gates_bounds_and_slots(gpu, O):
-    """long lazy chains (sums of 200 terms, alternating subtractions / negations / doublings) and many live
-    values (40 loads consumed in reverse order: the 64-rows-per-workgroup layout)"""
+    """long lazy chains (sums of 200 terms, alternating subtractions / negations / doublings) and 40 loads consumed in
+    reverse order (emission is on demand, so the chain needs 2 slots: test_interpreter_at_every_tile_size is the one
+    that reaches the 64-rows-per-workgroup layout)"""
     from circuits_halo2_amd import arithmetic as A
     k, ext_k = 6, 8
     ne = 1 << ext_k
@@ -1380,7 +1347,7 @@ def test_quotient_gates_bounds_and_slots(gpu, O):
     want = O.quotient_gates(start, g.as_dict(), *args)
     got = A.quotient_gates(dev(start), g, [], [dev(c) for c in adv], [], *args[3:])
     assert (got.cpu().numpy() == want).all()
-    # 40 values loaded first, consumed last-in-first-out
+    # 40 squared loads, consumed last-in-first-out
     g = A.GraphEvaluator()
     loads = [g.add_calculation(A.SQUARE, g.query(A.ADVICE, i, 0)) for i in range(40)]
     acc = loads[-1]
@@ -1420,6 +1387,64 @@ def test_quotient_gates_errors(gpu, O):
         run(g, [col])
     with pytest.raises(ValueError):
         run(g, [col[:64]])
+
+
+def _gates_on_both_layouts(O, capfd, graph, n_fixed, n_advice, chal, seed, generic=False):
+    """a gate program at k = 5 over the extended domain (ext_k = 7) and over 5 cosets of 2^5 rows, against the oracle (coset-major:
+    every block is a domain of its own, rotations wrap inside it).  Returns [(stderr of the call under SG_GATES_DEBUG, rows)]."""
+    import os
+    from circuits_halo2_amd import arithmetic as A
+    k, ext_k, d = 5, 7, 5
+    beta, gamma, theta, y = (O.random_fr(seed + 90 + i, 1) for i in range(4))
+    out = []
+    for rows, cosets in ((1 << ext_k, 0), (d << k, d)):
+        fixed = [O.random_fr(seed + i, rows) for i in range(n_fixed)]
+        advice = [O.random_fr(seed + 40 + i, rows) for i in range(n_advice)]
+        start = O.random_fr(seed + 80, rows)
+        if cosets:
+            blk = lambda a, b: a[32 * (b << k):32 * ((b + 1) << k)]
+            want = np.concatenate([O.quotient_gates(blk(start, b), graph.as_dict(), [blk(c, b) for c in fixed], [blk(c, b) for c in advice], [],
+                                                    chal, beta, gamma, theta, y, k, k) for b in range(d)])
+        else:
+            want = O.quotient_gates(start, graph.as_dict(), fixed, advice, [], chal, beta, gamma, theta, y, k, ext_k)
+        os.environ["SG_GATES_DEBUG"] = "1"
+        if generic:
+            os.environ["SG_GATES_GENERIC"] = "1"
+        try:
+            args = (dev(start), graph, [dev(c) for c in fixed], [dev(c) for c in advice], [], chal, beta, gamma, theta, y, k)
+            got = A.quotient_gates_cosets(*args, cosets) if cosets else A.quotient_gates(*args, ext_k)
+            got = got.cpu().numpy()
+        finally:
+            os.environ.pop("SG_GATES_DEBUG", None)
+            os.environ.pop("SG_GATES_GENERIC", None)
+        assert (got == want).all(), (rows, cosets)
+        out.append((capfd.readouterr().err, got))
+    return out
+
+
+@pytest.mark.parametrize("nc", [2, 4])
+def test_ahead_of_time_gate_program_with_its_arguments_in_the_blob(gpu, O, capfd, nc):
+    """25 columns (11 fixed, 14 advice of which the program reads the first 3) are one more than travel as kernel arguments: the
+    lowering is the same, the ahead-of-time kernel takes columns and constants from the blob.  Same rows as the oracle and as the
+    interpreter."""
+    from circuits_halo2_amd import mst_inclusion as M
+    graph, chal = M.gate_graph(nc), M.gate_challenges(0x7654321 + nc, nc)
+    fast = _gates_on_both_layouts(O, capfd, graph, M.NUM_FIXED, 14, chal, 5100 + 200 * nc)
+    slow = _gates_on_both_layouts(O, capfd, graph, M.NUM_FIXED, 14, chal, 5100 + 200 * nc, generic=True)
+    for (err, rows), (err_generic, rows_generic) in zip(fast, slow):
+        assert "ahead-of-time program MstGatesNc%d," % nc in err and "(arguments by value)" not in err, err
+        assert "ahead-of-time" not in err_generic and "rows per workgroup" in err_generic, err_generic
+        assert (rows == rows_generic).all()
+
+
+@pytest.mark.parametrize("rows_per_workgroup", [256, 128, 64])
+def test_interpreter_at_every_tile_size(gpu, O, capfd, rows_per_workgroup):
+    """a program of 8, 20 and 40 simultaneously live values: 256, 128 and 64 rows per workgroup (tests/gates_cases.py restates
+    the rule; tests/test_gates_cases_cpu.py checks these programs against it)"""
+    import gates_cases as gc
+    n = gc.INTERPRETER_TILE_PROGRAMS[rows_per_workgroup]
+    for err, _ in _gates_on_both_layouts(O, capfd, gc.many_live_values(n), 0, 1, np.zeros(0, dtype=np.uint8), 5900 + n):
+        assert "%d slots, 4 constants -> %d rows per workgroup" % (n + 1, rows_per_workgroup) in err, err
 
 
 # ----------------------------------------------------------------------------- §8f-1: quotient numerator
