@@ -142,6 +142,116 @@ SG_HD void xyzz29_madd(xyzz29& acc, const affine29& q) {
   acc.y = y3;
 }
 
+// affine -> XYZZ with X, Y < 2 and ZZ = ZZZ = 1^: the coordinates come below 2p by f29_reduce_small (same domain, ~45
+// instructions each) instead of a product by 1^
+SG_HD xyzz29 xyzz29_from_affine(const affine29& q) {
+  typedef Fq29 P;
+  if (q.inf) return xyzz29_identity();
+  xyzz29 r;
+  r.x = f29_reduce_small<P>(q.x);                              // 33 -> < 2
+  // (normalised exactly first: the single carry step of affine29_negate leaves the top limb of a value below 2^232 one
+  // short when limb 7 keeps an excess, and f29_reduce_small takes its quotient from the top limb)
+  r.y = f29_reduce_small<P>(f29_normalize(q.y));               // 33 -> < 2
+  r.zz = f29_one<P>();
+  r.zzz = f29_one<P>();
+  return r;
+}
+
+// The ORDINARY case of acc += (neg ? -q : q), all of it straight-line code that updates acc in place: for the loops that
+// keep one accumulator in registers (msm_accumulate).  Neither acc nor q may be the identity.  Returns 0, or, where
+// P = 0 (mod p), 1 for acc = -(+-q) and 2 for acc = +-q; acc is then without meaning and the caller adds by xyzz29_madd.
+// The sign costs no negation of q.y: r = +-s2 - Y1 + K p is formed limb by limb from (s2 ^ mask) and one of two raised
+// constants, 4p for +s2 (r < 6) and 8p + 1 for ~s2 = -s2 - 1 (r < 8); s2 is exactly normalised and Y1 normalised, so
+// every limb of 8p's row (>= 2^30 + 2^25) stays above s2 + Y1 and no limb but the top one wraps.
+SG_HD int xyzz29_madd_ordinary(xyzz29& acc, const affine29& q, bool neg) {
+  typedef Fq29 P;
+  f29 u2 = f29_mul<P>(q.x, acc.zz);                            // 32*2 = 64
+  f29 s2 = f29_mul<P>(q.y, acc.zzz);                           // 64
+  f29 p = f29_sub<P, 2>(u2, acc.x);                            // < 2 + 8 = 10
+  // limb i of 4p - Y1 before its carry step (shared with the y3 product's operand) + s2, or + ~s2 + (8p - 4p + 1)
+  const uint32_t mask = neg ? 0xffffffffu : 0u;
+  f29 r;
+#pragma unroll
+  for (int i = 0; i < 9; i++)
+    r.l[i] = ((s2.l[i] ^ mask) + (P::subc[1][i] - acc.y.l[i])) + (mask & (P::subc[2][i] - P::subc[1][i] + 1u));
+  r = f29_carry(r);                                            // < 2 + 4 = 6, or < 8 - (s2 + Y1) <= 8
+  int special = 0;
+  if (f29_is_zero_mod_p<P>(p)) special = f29_is_zero_mod_p<P>(r) ? 2 : 1;
+  f29 pp = f29_sqr<P>(p);                                      // 100
+  f29 ppp = f29_mul<P>(p, pp);                                 // 20
+  f29 qq = f29_mul<P>(acc.x, pp);                              // 16
+  f29 rr = f29_sqr<P>(r);                                      // 64 (< 1.38 p)
+  // x3 and t as in xyzz29_madd: rr is the minuend, so its wider bound changes nothing in the shared carry step; x3 < rr + 6p
+  // < 7.38 p keeps x3 < 8 and t = qq + 8p - x3 above 0.62 p
+  f29 x3 = f29_carry(f29_sub_nc<P, 1>(f29_sub_nc<P, 0>(rr, ppp), f29_add_nc(qq, qq)));
+  f29 t = f29_carry_top(f29_sub_nc<P, 2>(qq, x3));             // < 10
+#if SG_FUSED_Y3
+  f29 y3 = f29_mul2<P>(t, r, f29_sub<P, 1>(f29_zero(), acc.y), ppp);  // t r + (4p - Y1) ppp: 80 + 8 -> < 2
+#else
+  f29 y3 = f29_sub<P, 0>(f29_mul<P>(t, r), f29_mul<P>(acc.y, ppp));   // 80, 8 => < 4
+#endif
+  acc.zz = f29_mul<P>(acc.zz, pp);                             // 4
+  acc.zzz = f29_mul<P>(acc.zzz, ppp);                          // 4
+  acc.x = x3;
+  acc.y = y3;
+  return special;
+}
+// acc += (neg ? -q : q): xyzz29_madd with the sign as an argument; the cold paths apply it to q.y themselves
+SG_HD void xyzz29_madd(xyzz29& acc, const affine29& q, bool neg) {
+  if (q.inf) return;
+  affine29 s = q;
+  if (neg) affine29_negate(s);
+  if (xyzz29_is_identity(acc)) {
+    acc = xyzz29_from_affine(s);
+    return;
+  }
+  xyzz29 sum = acc;
+  const int special = xyzz29_madd_ordinary(sum, q, neg);
+  if (special == 0) acc = sum;
+  else if (special == 2) acc = xyzz29_double_affine(s);
+  else acc = xyzz29_identity();
+}
+
+// The ORDINARY case of a + b for two affine points (mmadd-2008-s, 4M + 2S): the first two points of a bucket, with no
+// product by 1^ and none by ZZ = ZZZ = 1^.  Coordinates arrive with bound 32 (33 after negation); only the two differences
+// are brought below 2p (f29_reduce_small), x1 and y1 enter their one product each as they are.  Neither point may be the
+// identity.  Returns 0, or, where P = 0 (mod p), 1 for a = -b and 2 for a = b; out is then without meaning.
+SG_HD int xyzz29_mmadd_ordinary(xyzz29& out, const affine29& a, const affine29& b) {
+  typedef Fq29 P;
+  f29 p = f29_reduce_small<P>(f29_sub<P, 5>(b.x, a.x));        // 33 + 64 = 97 -> < 2
+  f29 r = f29_reduce_small<P>(f29_sub<P, 5>(b.y, a.y));        // 97 -> < 2
+  int special = 0;
+  if (f29_is_zero_mod_p<P>(p)) special = f29_is_zero_mod_p<P>(r) ? 2 : 1;
+  f29 pp = f29_sqr<P>(p);                                      // 4
+  f29 ppp = f29_mul<P>(p, pp);                                 // 4 (< 1.03 p)
+  f29 qq = f29_mul<P>(a.x, pp);                                // 33*2 = 66 (< 1.39 p)
+  f29 rr = f29_sqr<P>(r);                                      // 4
+  // x3 = rr + 2p - ppp + 4p - 2 qq in one carry step (xyzz29_madd): ppp < 2p, 2 qq < 2.78 p < 4p, subtrahend limbs < 2^30;
+  // the value lies in (2.19 p, 8p), so the carried top limb is the true one and X3 < 8
+  f29 x3 = f29_carry(f29_sub_nc<P, 1>(f29_sub_nc<P, 0>(rr, ppp), f29_add_nc(qq, qq)));
+  // t = qq + 8p - x3 in (0, 9.39 p): a product's first operand, only the top limb carried
+  f29 t = f29_carry_top(f29_sub_nc<P, 2>(qq, x3));             // < 10
+#if SG_FUSED_Y3
+  out.y = f29_mul2<P>(t, r, f29_sub<P, 5>(f29_zero(), a.y), ppp);     // t r + (64p - y1) ppp: 20 + 128 = 148 -> < 2
+#else
+  out.y = f29_sub<P, 0>(f29_mul<P>(t, r), f29_mul<P>(a.y, ppp));      // 20, 66 => < 4
+#endif
+  out.x = x3;
+  out.zz = pp;
+  out.zzz = ppp;
+  return special;
+}
+// a + b for two affine points, every case decided exactly
+SG_HD xyzz29 xyzz29_mmadd(const affine29& a, const affine29& b) {
+  if (a.inf) return xyzz29_from_affine(b);
+  if (b.inf) return xyzz29_from_affine(a);
+  xyzz29 r;
+  const int special = xyzz29_mmadd_ordinary(r, a, b);
+  if (special == 2) return xyzz29_double_affine(a);
+  if (special == 1) return xyzz29_identity();
+  return r;
+}
+
 // acc += q   (both XYZZ; add-2008-s)
 SG_HD void xyzz29_add(xyzz29& acc, const xyzz29& q) {
   typedef Fq29 P;

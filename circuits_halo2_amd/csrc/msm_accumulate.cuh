@@ -15,7 +15,20 @@ __device__ __forceinline__ uint32_t find_owner(const uint32_t* __restrict__ toff
   return lo;
 }
 
-// Persistent: the grid is a fixed number of waves per SIMD (MsmConfig::acc_waves; three fill the register file at 161
+// A prefetched point out of its buffer, in limbs -- and pinned there, so that the loads that refill the buffer, issued
+// behind this, land in the buffer's own registers instead of a second buffer that is copied back at the end of the trip
+// (2 x 8 v_mov_b64 per addition).  A point at infinity raises `redo`.
+__device__ __forceinline__ affine29 affine29_take(const g1_affine_mem& raw, bool& redo) {
+  affine29 p = affine29_load(&raw);
+  uint32_t inf = p.inf;
+#pragma unroll
+  for (int i = 0; i < 9; i++) asm volatile("" : "+v"(p.x.l[i]), "+v"(p.y.l[i]));
+  asm volatile("" : "+v"(inf) : : "memory");
+  redo |= inf != 0;
+  return p;
+}
+
+// Persistent: the grid is a fixed number of waves per SIMD (MsmConfig::acc_waves; three fit the register file at 138
 // registers), and every wave takes tickets of 64 consecutive tasks from a counter until the task list (longest first, so
 // the 64 lanes of a ticket have equal work) is used up: the end of the launch is balanced by construction instead of by
 // the order in which the hardware happens to retire workgroups (2^20: 1.16 -> 1.12 ms; profiles/r03_sweeps/persistent_accumulate.txt).
@@ -46,21 +59,44 @@ __global__ void __launch_bounds__(256) msm_accumulate(const uint32_t* __restrict
       const g1_affine_mem* __restrict__ bases = bp.bases[b / buckets_per_msm];
       uint32_t start = off[b] + (seg << log_L);
       uint32_t end = min(off[b] + cnt[b], start + (1u << log_L));
-      xyzz29 acc = xyzz29_identity();
-      uint32_t e = sorted[start];
-      g1_affine_mem raw = bases[e & 0x7fffffffu];
-      for (uint32_t k = start; k < end; k++) {
-        uint32_t e_next = 0;
-        g1_affine_mem raw_next = raw;
-        if (k + 1 < end) {  // prefetch the next point while this one is being added
-          e_next = sorted[k + 1];
-          raw_next = bases[e_next & 0x7fffffffu];
+      // Task head: the first point alone, or the sum of the first two by the affine + affine addition, without the products
+      // that an accumulator of ZZ = ZZZ = 1 does not need.  Whatever is not the ordinary case of an addition -- a point at
+      // infinity, P = +-Q, an empty task -- only raises `redo`: the lane goes on with a meaningless accumulator, and the
+      // task is added again below by the additions that decide every case.  Reads past the end of the task fetch its last
+      // entry again and are not used.
+      const uint32_t last = max(end, start + 1) - 1;
+      uint32_t e = sorted[start], e1 = sorted[min(start + 1, last)];
+      g1_affine_mem raw = bases[e & 0x7fffffffu], raw1 = bases[e1 & 0x7fffffffu];
+      bool redo = end <= start;
+      affine29 p0 = affine29_take(raw, redo);
+      if (e >> 31) affine29_negate(p0);
+      xyzz29 acc;
+      uint32_t k = start + 2;
+      if (end - start == 1) {
+        acc = xyzz29_from_affine(p0);
+      } else {
+        affine29 p1 = affine29_take(raw1, redo);
+        if (e1 >> 31) affine29_negate(p1);
+        e = sorted[min(k, last)];
+        raw = bases[e & 0x7fffffffu];
+        redo |= xyzz29_mmadd_ordinary(acc, p0, p1) != 0;
+      }
+      // Steady state: the ordinary addition, in place, is the only definition of the accumulator that the loop carries, and
+      // the prefetch buffer is refilled where it stands as soon as its point is in limbs (affine29_take)
+      for (; k < end; k++) {
+        const affine29 p = affine29_take(raw, redo);
+        const bool neg = e >> 31;
+        e = sorted[min(k + 1, last)];
+        raw = bases[e & 0x7fffffffu];
+        redo |= xyzz29_madd_ordinary(acc, p, neg) != 0;
+      }
+      if (redo) {  // cold: the whole task by the additions that decide every case
+        acc = xyzz29_identity();
+        for (uint32_t i = start; i < end; i++) {
+          const uint32_t ei = sorted[i];
+          const g1_affine_mem q = bases[ei & 0x7fffffffu];
+          xyzz29_madd(acc, affine29_load(&q), ei >> 31);
         }
-        affine29 p = affine29_load(&raw);
-        if (e >> 31) affine29_negate(p);
-        xyzz29_madd(acc, p);
-        e = e_next;
-        raw = raw_next;
       }
       xyzz29_store(partial + toff[b] + seg, acc);
     }
