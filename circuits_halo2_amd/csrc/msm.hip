@@ -156,6 +156,8 @@ hipError_t MsmEngine::init() {
                              96 * 1024));
   SG_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(msm_fine_sort), hipFuncAttributeMaxDynamicSharedMemorySize,
                              128 * 1024));
+  SG_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(msm_fine_sort_fused), hipFuncAttributeMaxDynamicSharedMemorySize,
+                             128 * 1024));
   return hipSuccess;
 }
 
@@ -244,8 +246,8 @@ hipError_t MsmEngine::reserve_front(const FrontPlan& f, hipStream_t stream) {
   }
   {
     const uint32_t* before = meta_.p;
-    SG_TRY(meta_.reserve(16));
-    if (meta_.p != before) SG_TRY(hipMemsetAsync(meta_.p, 0, 16 * sizeof(uint32_t), stream));   // SCAN_DONE starts at zero (msm_scan_sums keeps it there)
+    SG_TRY(meta_.reserve(META_WORDS));
+    if (meta_.p != before) SG_TRY(hipMemsetAsync(meta_.p, 0, META_WORDS * sizeof(uint32_t), stream));   // SCAN_DONE starts at zero (msm_scan_sums keeps it there)
   }
   if (f.fe) {
     const uint32_t* before = fe_.p;
@@ -256,7 +258,7 @@ hipError_t MsmEngine::reserve_front(const FrontPlan& f, hipStream_t stream) {
   // the counters and the window sums reach the host through page-locked memory the kernels write directly (mapped,
   // coherent): no copy kernels between the producing kernel and the event the host waits for
   if (!h_meta_) {
-    SG_TRY(hipHostMalloc(&h_meta_, 16 * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
+    SG_TRY(hipHostMalloc(&h_meta_, META_WORDS * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
     SG_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&d_hmeta_), h_meta_, 0));
   }
   if (h_win_cap_ < f.hwin_words) {
@@ -276,7 +278,7 @@ hipError_t MsmEngine::launch_sort_two_pass(Job& j) {
   hipStream_t stream = j.stream;
   const uint32_t n = (uint32_t)f.n, B = f.B, NBc = f.NBc, collapse_W = f.fixed ? f.W1 : 0u;
   FrontEndScan fe_scan{nullptr, nullptr, nullptr, 0u, 0u};
-  if (f.fe) fe_scan = FrontEndScan{fe_.p + 3, coff_.p, tbase_.p, 1u << f.shift, f.log_L};
+  if (f.fe) fe_scan = FrontEndScan{fe_.p + FE_HP_DONE, coff_.p, tbase_.p, 1u << f.shift, f.log_L};
   msm_hist<<<dim3(f.W, f.P), 1024, B * sizeof(uint32_t), stream>>>(dig_.p, n, f.chunk, B, f.shift, hist_.p);
   msm_hist_prefix<<<(NBc + HP_BUCKETS - 1) / HP_BUCKETS, HP_BUCKETS * HP_GROUPS, 0, stream>>>(
       hist_.p, f.fixed ? f.W1 * f.P : f.P, B, NBc, ccnt_.p, fe_scan);

@@ -1,11 +1,117 @@
-// MSM engine, part 1 of 3 (included once by msm.hip): signed digits, the counting sort in its single-pass and two-pass
+// MSM engine, the front end (included once by msm.hip): signed digits, the counting sort in its single-pass and two-pass
 // forms, the scans that close it, and the ordering of the accumulation tasks.  The limits these kernels share with the host's
 // planning (SORT_TILE, FE_MAX_BINS, TASK_BINS, SCAN_BLOCK, SCAN_SMALL_PER) are defined in msm_plan.h.
 #pragma once
+#include <type_traits>
 #include "msm.h"
 #include "side_prio.cuh"
 
 namespace sg {
+
+// ------------------------------------------------------------------ the engine's two small device tables, word by word
+// meta_ (META_WORDS, zero when allocated): [0] entries, [1] tasks, [2] largest bucket count of the job (write_job_totals; the
+// same three go to the host's mapped copy), [ACC_TICKET] msm_accumulate's task counter, [SCAN_DONE] the finished workgroups of
+// msm_scan_sums (zero between launches).
+static constexpr uint32_t ACC_TICKET = 8, SCAN_DONE = 12, META_WORDS = 16;
+// fe_ (FE_WORDS, zero when allocated; the fused front end): [FE_HP_DONE] the finished workgroups of msm_hist_prefix (zero
+// between launches), [FE_CURSOR + k] the task scatter's running position inside the tasks of length k (zero at its start), and
+// two SETS of replicas, used by alternate jobs of the engine (a job's sort zeroes the other set for the next job): per replica
+// r of set p at FE_SET + p * FE_SET_WORDS + r * FE_ROW: [0] tasks, [1] largest count, [2 + k] tasks of (clamped) length k
+static constexpr uint32_t FE_HP_DONE = 3, FE_REPL = 64;
+static constexpr uint32_t FE_CURSOR = 8, FE_ROW = TASK_BINS + 2, FE_SET_WORDS = FE_REPL * FE_ROW, FE_SET = FE_CURSOR + TASK_BINS,
+                          FE_WORDS = FE_SET + 2 * FE_SET_WORDS;
+
+// ------------------------------------------------------------------ shared bodies
+// digit d != 0 lands in bucket |d| - 1 (d == 0 wraps to a huge value: msm_scatter's range test drops it) ...
+__device__ __forceinline__ uint32_t digit_bucket(int32_t d) { return (uint32_t)(d < 0 ? -d : d) - 1u; }
+// ... as the entry (row of the bases or of the window table, sign of the digit)
+__device__ __forceinline__ uint32_t entry_word(uint32_t index, int32_t d) { return index | (d < 0 ? 0x80000000u : 0u); }
+
+// Inclusive Hillis-Steele scan over the first n threads' words of NV separate LDS arrays (sums; MAX_LAST: the last array is a
+// running maximum).  Every thread of the workgroup calls it, having stored its own words: one barrier, then two per step.
+// `live` = false keeps a thread beyond the scanned range (msm_partition: B of 1024) out of the arrays but in the barriers.
+template <uint32_t NV, bool MAX_LAST = false, typename T>
+__device__ __forceinline__ void block_scan(uint32_t tid, uint32_t n, bool live, T* s0, T* s1 = nullptr, T* s2 = nullptr) {
+  static_assert(NV >= 1 && NV <= 3, "one to three arrays");
+  T* const s[3] = {s0, s1, s2};
+  __syncthreads();
+  for (uint32_t d = 1; d < n; d <<= 1) {
+    T x[NV] = {};
+    if (live && tid >= d) {
+#pragma unroll
+      for (uint32_t k = 0; k < NV; k++) x[k] = s[k][tid - d];
+    }
+    __syncthreads();
+    if (live) {
+#pragma unroll
+      for (uint32_t k = 0; k < NV; k++) s[k][tid] = (MAX_LAST && k == NV - 1) ? max(s[k][tid], x[k]) : s[k][tid] + x[k];
+    }
+    __syncthreads();
+  }
+}
+
+// The job's totals, by ONE thread: into off[NB] (optional), toff[NB], meta[0..2] and, when `host_meta` is given, straight into
+// page-locked host memory the device can write (the host reads them after an event, no copy kernel in between).  `task_slots`
+// is `tasks` but in the fused front end, whose task index space has gaps.
+__device__ __forceinline__ void write_job_totals(uint32_t* off, uint32_t* toff, uint32_t NB, uint32_t* meta,
+                                                 volatile uint32_t* host_meta, uint32_t entries, uint32_t task_slots,
+                                                 uint32_t tasks, uint32_t largest) {
+  if (off) off[NB] = entries;
+  toff[NB] = task_slots;
+  meta[0] = entries;
+  meta[1] = tasks;
+  meta[2] = largest;
+  if (host_meta) {
+    host_meta[0] = entries;
+    host_meta[1] = tasks;
+    host_meta[2] = largest;
+    __threadfence_system();
+  }
+}
+
+// A bucket of cv entries is nfull tasks of exactly L = 2^log_L entries plus at most one shorter task of rem; task lengths are
+// histogrammed clamped to TASK_BINS - 1.
+__device__ __forceinline__ uint32_t task_full_bin(uint32_t log_L) { return min(1u << log_L, TASK_BINS - 1); }
+struct BucketTasks {
+  uint32_t nfull, rem, full_bin, rem_bin;
+};
+__device__ __forceinline__ BucketTasks bucket_tasks(uint32_t cv, uint32_t log_L) {
+  const uint32_t nfull = cv >> log_L, rem = cv - (nfull << log_L);
+  return BucketTasks{nfull, rem, task_full_bin(log_L), min(rem, TASK_BINS - 1)};
+}
+// s_h[length] += the tasks of one bucket
+__device__ __forceinline__ void count_bucket_tasks(uint32_t* s_h, uint32_t cv, uint32_t log_L) {
+  const BucketTasks bt = bucket_tasks(cv, log_L);
+  if (bt.nfull) atomicAdd(&s_h[bt.full_bin], bt.nfull);
+  if (bt.rem) atomicAdd(&s_h[bt.rem_bin], 1u);
+}
+// ... of the task_block buckets of this workgroup
+__device__ __forceinline__ void count_block_tasks(uint32_t* s_h, const uint32_t* __restrict__ cnt, uint32_t NB, uint32_t log_L,
+                                                  uint32_t task_block) {
+  for (uint32_t q = threadIdx.x; q < task_block; q += blockDim.x) {
+    const uint32_t b = blockIdx.x * task_block + q;
+    if (b < NB) count_bucket_tasks(s_h, cnt[b], log_L);
+  }
+}
+// order[pos] = (bucket, segment) for every task of this workgroup's buckets, s_c[length] being the next free position among the
+// tasks of that length
+__device__ __forceinline__ void place_bucket_tasks(uint32_t* s_c, const uint32_t* __restrict__ cnt, uint32_t NB, uint32_t log_L,
+                                                   uint32_t task_block, uint2* __restrict__ order) {
+  for (uint32_t q = threadIdx.x; q < task_block; q += blockDim.x) {
+    const uint32_t b = blockIdx.x * task_block + q;
+    if (b < NB) {
+      const BucketTasks bt = bucket_tasks(cnt[b], log_L);
+      if (bt.nfull) {
+        const uint32_t pos = atomicAdd(&s_c[bt.full_bin], bt.nfull);
+        for (uint32_t seg = 0; seg < bt.nfull; seg++) order[pos + seg] = make_uint2(b, seg);
+      }
+      if (bt.rem) {
+        const uint32_t pos = atomicAdd(&s_c[bt.rem_bin], 1u);
+        order[pos] = make_uint2(b, bt.nfull);
+      }
+    }
+  }
+}
 
 // ------------------------------------------------------------------ 1: signed digits
 // Windows have individual widths (WindowPlan): W-1 signed windows of c or c-1 bits and an
@@ -85,7 +191,7 @@ __global__ void __launch_bounds__(1024) msm_hist(const int16_t* __restrict__ dig
   const int16_t* row = dig + (size_t)j * n;
   for (uint32_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
     int32_t d = row[i];
-    if (d) atomicAdd(&s_cnt[((uint32_t)(d < 0 ? -d : d) - 1u) >> shift], 1u);
+    if (d) atomicAdd(&s_cnt[digit_bucket(d) >> shift], 1u);
   }
   __syncthreads();
   uint32_t* out = hist + ((size_t)j * P + p) * nbw;
@@ -96,10 +202,10 @@ __global__ void __launch_bounds__(1024) msm_hist(const int16_t* __restrict__ dig
 // bases come from LDS, then a second sweep writes the prefixes (a column is P strided loads;
 // one thread per bucket made this the slowest kernel of a small MSM).
 static constexpr uint32_t HP_BUCKETS = 32, HP_GROUPS = 8;
-// Round 5 (`fe` != nullptr, coarse bins of the two-pass sort, NB <= FE_MAX_BINS): the workgroup that finishes LAST (a counter in
-// device memory, as msm_scan_sums does for its block sums) also scans the bin totals -- coff[g] = entries before bin g and
-// tbase[g] = task slots before bin g, a bin of F buckets and E entries owning F + (E >> log_L) slots (an upper bound of its
-// sum_f ceil(c_f / L) tasks) -- which used to be a launch of its own (msm_scan_small / msm_scan_sums + msm_scan_write).
+// Fused front end (`fe.done` != nullptr, coarse bins of the two-pass sort, NB <= FE_MAX_BINS): the workgroup that finishes LAST
+// (a counter in device memory, as msm_scan_sums does for its block sums) also scans the bin totals -- coff[g] = entries before
+// bin g and tbase[g] = task slots before bin g, a bin of F buckets and E entries owning F + (E >> log_L) slots (an upper bound
+// of its sum_f ceil(c_f / L) tasks) -- in place of a launch of its own (msm_scan_small / msm_scan_sums + msm_scan_write).
 struct FrontEndScan {
   uint32_t* done;    // counter of finished workgroups (zero between launches), nullptr: no scan here
   uint32_t* coff;    // [NB + 1]
@@ -161,14 +267,7 @@ __global__ void __launch_bounds__(256) msm_hist_prefix(uint32_t* __restrict__ hi
     }
   }
   s_a[tid] = a; s_t[tid] = t;
-  __syncthreads();
-  for (uint32_t d = 1; d < 256; d <<= 1) {
-    uint32_t xa = 0, xt = 0;
-    if (tid >= d) { xa = s_a[tid - d]; xt = s_t[tid - d]; }
-    __syncthreads();
-    s_a[tid] += xa; s_t[tid] += xt;
-    __syncthreads();
-  }
+  block_scan<2>(tid, 256, true, s_a, s_t);
   uint32_t ra = s_a[tid] - a, rt = s_t[tid] - t;
 #pragma unroll
   for (uint32_t q = 0; q < FE_MAX_BINS / 256; q++) {
@@ -186,16 +285,13 @@ __global__ void __launch_bounds__(256) msm_hist_prefix(uint32_t* __restrict__ hi
   }
 }
 
-// ------------------------------------------------------------------ 3: scans (multi-block)
+// ------------------------------------------------------------------ 3: scans over the buckets (multi-block)
 // cnt[NB] -> off[NB+1] (exclusive scan, optional), ntask[b] = ceil(cnt[b]/L), toff[NB+1]
 // (exclusive scan of ntask), meta = {sum cnt, sum ntask, max cnt}.  2048 buckets per block.
 
-// Round 4: the scan of the (<= 1024) block sums is done by whichever workgroup of this launch finishes LAST (a counter in
-// device memory, zero between launches: the last arrival resets it; no workgroup ever waits for another) -- the separate
-// one-workgroup launch of rounds 1-3 is gone, one ~5.5 us launch less per scan, two scans per MSM job.
-// The totals land in off[NB] (optional), toff[NB], meta[0..2] and, when `host_meta` is given, straight in page-locked host
-// memory the device can write (the host reads them after an event, no copy kernel in between).
-static constexpr uint32_t SCAN_DONE = 12;         // word of meta_ that counts the finished workgroups of msm_scan_sums
+// The scan of the (<= 1024) block sums is done by whichever workgroup of this launch finishes LAST (a counter in device
+// memory, zero between launches: the last arrival resets it; no workgroup ever waits for another): one ~5.5 us launch less per
+// scan than with a one-workgroup launch of its own, two scans per MSM job.  The totals: write_job_totals.
 __global__ void __launch_bounds__(256) msm_scan_sums(const uint32_t* __restrict__ cnt, uint32_t NB, uint32_t log_L,
                                                      uint32_t* __restrict__ bsum, uint32_t* __restrict__ meta,
                                                      uint32_t* __restrict__ off, uint32_t* __restrict__ toff,
@@ -249,14 +345,7 @@ __global__ void __launch_bounds__(256) msm_scan_sums(const uint32_t* __restrict_
   }
   __syncthreads();
   s_a[tid] = a; s_t[tid] = t; s_m[tid] = vm;
-  __syncthreads();
-  for (uint32_t d = 1; d < SCAN_THREADS; d <<= 1) {
-    uint32_t xa = 0, xt = 0, xm = 0;
-    if (tid >= d) { xa = s_a[tid - d]; xt = s_t[tid - d]; xm = s_m[tid - d]; }
-    __syncthreads();
-    s_a[tid] += xa; s_t[tid] += xt; s_m[tid] = max(s_m[tid], xm);
-    __syncthreads();
-  }
+  block_scan<3, true>(tid, SCAN_THREADS, true, s_a, s_t, s_m);
   uint32_t ra = s_a[tid] - a, rt = s_t[tid] - t;
 #pragma unroll
   for (uint32_t k = 0; k < 4; k++) {
@@ -269,18 +358,8 @@ __global__ void __launch_bounds__(256) msm_scan_sums(const uint32_t* __restrict_
     rt += vt[k];
   }
   if (tid == SCAN_THREADS - 1) {
-    if (off) off[NB] = s_a[tid];
-    toff[NB] = s_t[tid];
-    meta[0] = s_a[tid];
-    meta[1] = s_t[tid];
-    meta[2] = s_m[tid];
     meta[SCAN_DONE] = 0;                 // ready for the next launch on this stream
-    if (host_meta) {
-      host_meta[0] = s_a[tid];
-      host_meta[1] = s_t[tid];
-      host_meta[2] = s_m[tid];
-      __threadfence_system();
-    }
+    write_job_totals(off, toff, NB, meta, host_meta, s_a[tid], s_t[tid], s_t[tid], s_m[tid]);
   }
 }
 __global__ void __launch_bounds__(256) msm_scan_write(const uint32_t* __restrict__ cnt, uint32_t NB, uint32_t log_L,
@@ -299,14 +378,7 @@ __global__ void __launch_bounds__(256) msm_scan_write(const uint32_t* __restrict
     t += (v[k] + Lm1) >> log_L;
   }
   s_a[tid] = a; s_t[tid] = t;
-  __syncthreads();
-  for (uint32_t d = 1; d < SCAN_THREADS; d <<= 1) {
-    uint32_t va = 0, vt = 0;
-    if (tid >= d) { va = s_a[tid - d]; vt = s_t[tid - d]; }
-    __syncthreads();
-    s_a[tid] += va; s_t[tid] += vt;
-    __syncthreads();
-  }
+  block_scan<2>(tid, SCAN_THREADS, true, s_a, s_t);
   uint32_t ra = bsum[3 * blockIdx.x] + s_a[tid] - a, rt = bsum[3 * blockIdx.x + 1] + s_t[tid] - t;
 #pragma unroll
   for (uint32_t k = 0; k < SCAN_ITEMS; k++) {
@@ -321,7 +393,7 @@ __global__ void __launch_bounds__(256) msm_scan_write(const uint32_t* __restrict
   }
 }
 
-// ------------------------------------------------------------------ 3b: LDS-cursor scatter
+// ------------------------------------------------------------------ 4: single-pass sort, LDS-cursor scatter
 // workgroup (p, j): cursors = bucket offset + this chunk's prefix, kept in LDS; every point
 // of the chunk takes the next slot of its bucket with an LDS atomic.
 __global__ void __launch_bounds__(1024) msm_scatter(const int16_t* __restrict__ dig, uint32_t n, uint32_t chunk,
@@ -346,15 +418,15 @@ __global__ void __launch_bounds__(1024) msm_scatter(const int16_t* __restrict__ 
   const int16_t* row = dig + (size_t)j * n;
   for (uint32_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
     int32_t d = row[i];
-    uint32_t b = (uint32_t)(d < 0 ? -d : d) - 1u - b_lo;   // d == 0 wraps to a huge value
+    uint32_t b = digit_bucket(d) - b_lo;   // d == 0 wraps to a huge value
     if (b < span) {
       uint32_t pos = atomicAdd(&s_cur[b], 1u);
-      sorted[pos] = (base_idx + i) | (d < 0 ? 0x80000000u : 0u);
+      sorted[pos] = entry_word(base_idx + i, d);
     }
   }
 }
 
-// ------------------------------------------------------------------ 3c: two-pass sort
+// ------------------------------------------------------------------ 5: two-pass sort
 // msm_scatter's 4-byte stores land all over the output (a workgroup holds chunk / nbw entries per
 // bucket), and every one of them costs a 32-byte write to HBM.  The two-pass sort only ever writes
 // runs: pass 1 partitions the digits into B coarse bins per bucket set (bin = bucket >> shift) through
@@ -392,29 +464,23 @@ __global__ void __launch_bounds__(1024) msm_partition(const int16_t* __restrict_
     for (uint32_t k = 0; k < PER; k++) {
       const uint32_t i = t0 + k * 1024 + tid;
       d[k] = i < hi ? (int32_t)row[i] : 0;
-      if (d[k]) rank[k] = atomicAdd(&s_cnt[((uint32_t)(d[k] < 0 ? -d[k] : d[k]) - 1u) >> shift], 1u);
+      if (d[k]) rank[k] = atomicAdd(&s_cnt[digit_bucket(d[k]) >> shift], 1u);
     }
     __syncthreads();
     // exclusive scan of the B tile counts (B <= 1024): s_base
     {
       uint32_t v = tid < B ? s_cnt[tid] : 0;
       if (tid < B) s_base[tid] = v;
-      __syncthreads();
-      for (uint32_t dd = 1; dd < B; dd <<= 1) {
-        uint32_t u = (tid < B && tid >= dd) ? s_base[tid - dd] : 0;
-        __syncthreads();
-        if (tid < B) s_base[tid] += u;
-        __syncthreads();
-      }
+      block_scan<1>(tid, B, tid < B, s_base);
       if (tid < B) s_base[tid] -= v;
       __syncthreads();
     }
 #pragma unroll
     for (uint32_t k = 0; k < PER; k++) {
       if (d[k]) {
-        const uint32_t fine = (uint32_t)(d[k] < 0 ? -d[k] : d[k]) - 1u;
+        const uint32_t fine = digit_bucket(d[k]);
         const uint32_t slot = s_base[fine >> shift] + rank[k];
-        s_entry[slot] = (base_idx + t0 + k * 1024 + tid) | (d[k] < 0 ? 0x80000000u : 0u);
+        s_entry[slot] = entry_word(base_idx + t0 + k * 1024 + tid, d[k]);
         s_fine[slot] = (uint16_t)fine;
       }
     }
@@ -434,82 +500,18 @@ __global__ void __launch_bounds__(1024) msm_partition(const int16_t* __restrict_
 
 // pass 2: one workgroup per (set, coarse bin): F = 2^shift buckets.  counts[set*nbw + bin*F + f] and
 // the bin's slice of `sorted` in bucket order.
-__global__ void __launch_bounds__(512) msm_fine_sort(const uint32_t* __restrict__ part_entry,
-                                                     const uint16_t* __restrict__ part_fine,
-                                                     const uint32_t* __restrict__ coff,
-                                                     const uint32_t* __restrict__ ccnt, uint32_t B, uint32_t shift,
-                                                     uint32_t nbw, uint32_t* __restrict__ counts,
-                                                     uint32_t* __restrict__ sorted) {
-  side_kernel_prio();
-  extern __shared__ uint32_t s_mem[];
-  const uint32_t F = 1u << shift, tid = threadIdx.x, nthr = blockDim.x;
-  uint32_t* s_cnt = s_mem;        // [F] counts, then cursors
-  uint32_t* s_ofs = s_cnt + F;    // [F] exclusive offsets
-  uint32_t* s_part = s_ofs + F;   // [nthr] scan scratch
-  uint32_t* s_out = s_part + nthr;  // [SORT_TILE]
-  const uint32_t start = coff[blockIdx.x], E = ccnt[blockIdx.x];
-  const uint32_t set = blockIdx.x / B, bin = blockIdx.x - set * B;
-  for (uint32_t f = tid; f < F; f += nthr) s_cnt[f] = 0;
-  __syncthreads();
-  for (uint32_t i = tid; i < E; i += nthr) atomicAdd(&s_cnt[part_fine[start + i] & (F - 1)], 1u);
-  __syncthreads();
-  // exclusive scan over F: contiguous share per thread + Hillis-Steele over the shares
-  const uint32_t per = (F + nthr - 1) / nthr, f0 = min(tid * per, F), f1 = min(f0 + per, F);
-  uint32_t a = 0;
-  for (uint32_t f = f0; f < f1; f++) a += s_cnt[f];
-  s_part[tid] = a;
-  __syncthreads();
-  for (uint32_t dd = 1; dd < nthr; dd <<= 1) {
-    uint32_t u = tid >= dd ? s_part[tid - dd] : 0;
-    __syncthreads();
-    s_part[tid] += u;
-    __syncthreads();
-  }
-  uint32_t run = s_part[tid] - a;
-  uint32_t* cout = counts + (size_t)set * nbw + (size_t)bin * F;
-  for (uint32_t f = f0; f < f1; f++) {
-    const uint32_t c = s_cnt[f];
-    cout[f] = c;
-    s_ofs[f] = run;
-    run += c;
-  }
-  __syncthreads();
-  for (uint32_t f = tid; f < F; f += nthr) s_cnt[f] = s_ofs[f];   // cursors
-  __syncthreads();
-  if (E <= SORT_TILE) {
-    for (uint32_t i = tid; i < E; i += nthr) {
-      const uint32_t pos = atomicAdd(&s_cnt[part_fine[start + i] & (F - 1)], 1u);
-      s_out[pos] = part_entry[start + i];
-    }
-    __syncthreads();
-    for (uint32_t i = tid; i < E; i += nthr) sorted[start + i] = s_out[i];
-  } else {  // oversized bin (skewed scalars): place directly; the region belongs to this workgroup alone
-    for (uint32_t i = tid; i < E; i += nthr) {
-      const uint32_t pos = atomicAdd(&s_cnt[part_fine[start + i] & (F - 1)], 1u);
-      sorted[start + pos] = part_entry[start + i];
-    }
-  }
-}
-
-// Round 5: pass 2 that also closes the front end.  A workgroup owns a coarse bin whose entry offset (coff) and task-slot base
-// (tbase) are known from the coarse scan, so everything the bucket-level scans produced is local to it: off[b] = start +
-// exclusive count prefix, ntask[b] = ceil(c / L), toff[b] = tbase + exclusive task prefix (the task index space has gaps at
-// the end of every bin: consumers only ever index partial[toff[b] + seg]).  What is global -- the number of tasks, the
-// largest bucket, the histogram of task lengths that orders the tasks longest first -- leaves the workgroup as fire-and-forget
-// atomics into one of FE_REPL replicas (thousands of workgroups adding to ONE word per length cost a millisecond of serialised
-// atomics) and is summed by the NEXT kernel of the job (msm_task_scatter_reserve), where the kernel boundary has made it
-// complete: no workgroup waits for a return value or for another workgroup, and there is no release fence -- in this kernel a
-// fence writes back an L2 that has just been filled with sorted entries, once per workgroup: a millisecond
+//
+// FE, the pass that also closes the front end (msm_fine_sort_fused).  A workgroup owns a coarse bin whose entry offset (coff)
+// and task-slot base (tbase) are known from the coarse scan, so everything the bucket-level scans produce is local to it:
+// off[b] = start + exclusive count prefix, ntask[b] = ceil(c / L), toff[b] = tbase + exclusive task prefix (the task index space
+// has gaps at the end of every bin: consumers only ever index partial[toff[b] + seg]).  What is global -- the number of tasks,
+// the largest bucket, the histogram of task lengths that orders the tasks longest first -- leaves the workgroup as
+// fire-and-forget atomics into one of FE_REPL replicas (thousands of workgroups adding to ONE word per length cost a millisecond
+// of serialised atomics) and is summed by the NEXT kernel of the job (msm_task_scatter_reserve), where the kernel boundary has
+// made it complete: no workgroup waits for a return value or for another workgroup, and there is no release fence -- in this
+// kernel a fence writes back an L2 that has just been filled with sorted entries, once per workgroup: a millisecond
 // (profiles/r05_sweeps/frontend.txt has all three measurements).  msm_scan_sums, msm_scan_write, msm_task_hist and msm_task_scan
-// are gone from the job's chain.
-//   fe words: [3] finished workgroups of msm_hist_prefix, [FE_CURSOR + k] the scatter's running position inside the tasks of
-//   length k (zero at its start), and two SETS of replicas, used by alternate jobs of the engine (a job's sort zeroes the other
-//   set for the next job): per replica r of set p at FE_SET + p * FE_SET_WORDS + r * FE_ROW: [0] tasks, [1] largest count,
-//   [2 + k] tasks of (clamped) length k
-static constexpr uint32_t TASK_BINS_FE = 257;     // = TASK_BINS (defined with the task ordering below)
-static constexpr uint32_t FE_REPL = 64;
-static constexpr uint32_t FE_CURSOR = 8, FE_ROW = TASK_BINS_FE + 2, FE_SET_WORDS = FE_REPL * FE_ROW, FE_SET = FE_CURSOR + TASK_BINS_FE,
-                          FE_WORDS = FE_SET + 2 * FE_SET_WORDS;
+// are not in that job's chain.
 struct FrontEndOut {
   uint32_t* off;
   uint32_t* ntask;
@@ -518,83 +520,84 @@ struct FrontEndOut {
   uint32_t* fe;
   uint32_t log_L, parity;
 };
-__global__ void __launch_bounds__(512) msm_fine_sort_fused(const uint32_t* __restrict__ part_entry,
-                                                           const uint16_t* __restrict__ part_fine,
-                                                           const uint32_t* __restrict__ coff,
-                                                           const uint32_t* __restrict__ ccnt, uint32_t B, uint32_t shift,
-                                                           uint32_t nbw, uint32_t* __restrict__ counts,
-                                                           uint32_t* __restrict__ sorted, FrontEndOut o) {
-  side_kernel_prio();
+// dynamic LDS: (2F + nthr + SORT_TILE) words, FE (2F + 2 nthr + SORT_TILE); s_th [TASK_BINS] and s_red [2] (tasks of the bin,
+// largest count) are the fused kernel's own static LDS
+template <bool FE>
+__device__ __forceinline__ void fine_sort_body(const uint32_t* __restrict__ part_entry, const uint16_t* __restrict__ part_fine,
+                                               const uint32_t* __restrict__ coff, const uint32_t* __restrict__ ccnt, uint32_t B,
+                                               uint32_t shift, uint32_t nbw, uint32_t* __restrict__ counts,
+                                               uint32_t* __restrict__ sorted, const FrontEndOut& o, uint32_t* s_th,
+                                               uint32_t* s_red) {
   extern __shared__ uint32_t s_mem[];
-  __shared__ uint32_t s_th[TASK_BINS_FE];
-  __shared__ uint32_t s_red[2];   // tasks of the bin, largest count
   const uint32_t F = 1u << shift, tid = threadIdx.x, nthr = blockDim.x;
   uint32_t* s_cnt = s_mem;        // [F] counts, then cursors
   uint32_t* s_ofs = s_cnt + F;    // [F] exclusive offsets
-  uint32_t* s_part = s_ofs + F;   // [nthr] scan scratch
+  uint32_t* s_part = s_ofs + F;   // [nthr] scan scratch (FE: 64-bit words, over the start of s_out, which is not in use yet)
   uint32_t* s_out = s_part + nthr;  // [SORT_TILE]
   const uint32_t start = coff[blockIdx.x], E = ccnt[blockIdx.x];
   const uint32_t set = blockIdx.x / B, bin = blockIdx.x - set * B;
-  const uint32_t Lm1 = (1u << o.log_L) - 1, full_bin = min(1u << o.log_L, TASK_BINS_FE - 1);
-  // housekeeping for the jobs to come: the other replica set and the scatter's cursors back to zero (whoever used them last
-  // has finished: same stream)
-  {
+  if constexpr (FE) {
+    // housekeeping for the jobs to come: the other replica set and the scatter's cursors back to zero (whoever used them last
+    // has finished: same stream)
     uint32_t* other = o.fe + FE_SET + (o.parity ^ 1u) * FE_SET_WORDS;
     for (uint32_t row = blockIdx.x; row < FE_REPL; row += gridDim.x)
       for (uint32_t k = tid; k < FE_ROW; k += nthr) other[row * FE_ROW + k] = 0;
     if (blockIdx.x == 0)
-      for (uint32_t k = tid; k < TASK_BINS_FE; k += nthr) o.fe[FE_CURSOR + k] = 0;
+      for (uint32_t k = tid; k < TASK_BINS; k += nthr) o.fe[FE_CURSOR + k] = 0;
   }
   for (uint32_t f = tid; f < F; f += nthr) s_cnt[f] = 0;
-  for (uint32_t k = tid; k < TASK_BINS_FE; k += nthr) s_th[k] = 0;
-  if (tid < 2) s_red[tid] = 0;
+  if constexpr (FE) {
+    for (uint32_t k = tid; k < TASK_BINS; k += nthr) s_th[k] = 0;
+    if (tid < 2) s_red[tid] = 0;
+  }
   __syncthreads();
   for (uint32_t i = tid; i < E; i += nthr) atomicAdd(&s_cnt[part_fine[start + i] & (F - 1)], 1u);
   __syncthreads();
-  // exclusive scans over F (entries and tasks): contiguous share per thread + ONE Hillis-Steele over the shares, the two sums
-  // packed in a 64-bit word
+  // exclusive scan over F (FE: of entries and tasks, the two sums packed in a 64-bit word): contiguous share per thread + ONE
+  // Hillis-Steele over the shares
   const uint32_t per = (F + nthr - 1) / nthr, f0 = min(tid * per, F), f1 = min(f0 + per, F);
+  const uint32_t Lm1 = (1u << o.log_L) - 1;
   uint32_t a = 0, t = 0, mx = 0;
   for (uint32_t f = f0; f < f1; f++) {
     const uint32_t c = s_cnt[f];
     a += c;
-    t += (c + Lm1) >> o.log_L;
-    mx = max(mx, c);
-    // task lengths: nfull tasks of exactly L entries and at most one shorter one
-    const uint32_t nfull = c >> o.log_L, rem = c - (nfull << o.log_L);
-    if (nfull) atomicAdd(&s_th[full_bin], nfull);
-    if (rem) atomicAdd(&s_th[min(rem, TASK_BINS_FE - 1)], 1u);
+    if constexpr (FE) {
+      t += (c + Lm1) >> o.log_L;
+      mx = max(mx, c);
+      count_bucket_tasks(s_th, c, o.log_L);
+    }
   }
-  uint64_t* s_part64 = reinterpret_cast<uint64_t*>(s_part);   // [nthr] 64-bit: the scratch area is followed by s_out, which is not in use yet
-  s_part64[tid] = ((uint64_t)t << 32) | a;
-  __syncthreads();
-  for (uint32_t dd = 1; dd < nthr; dd <<= 1) {
-    uint64_t u = tid >= dd ? s_part64[tid - dd] : 0;
-    __syncthreads();
-    s_part64[tid] += u;
-    __syncthreads();
-  }
-  uint32_t run = (uint32_t)s_part64[tid] - a;
-  uint32_t trun = o.tbase[blockIdx.x] + (uint32_t)(s_part64[tid] >> 32) - t;
-  if (t) atomicAdd(&s_red[0], t);
-  if (mx) atomicMax(&s_red[1], mx);
+  using scan_t = std::conditional_t<FE, uint64_t, uint32_t>;
+  scan_t* s_scan = reinterpret_cast<scan_t*>(s_part);
+  if constexpr (FE) s_scan[tid] = ((uint64_t)t << 32) | a;
+  else s_scan[tid] = a;
+  block_scan<1>(tid, nthr, true, s_scan);
+  uint32_t run = (uint32_t)s_scan[tid] - a, trun = 0;
   const size_t b_first = (size_t)set * nbw + (size_t)bin * F;
+  if constexpr (FE) {
+    trun = o.tbase[blockIdx.x] + (uint32_t)(s_scan[tid] >> 32) - t;
+    if (t) atomicAdd(&s_red[0], t);
+    if (mx) atomicMax(&s_red[1], mx);
+  }
   uint32_t* cout = counts + b_first;
   for (uint32_t f = f0; f < f1; f++) {
-    const uint32_t c = s_cnt[f], nt = (c + Lm1) >> o.log_L;
+    const uint32_t c = s_cnt[f];
     cout[f] = c;
     s_ofs[f] = run;
-    o.off[b_first + f] = start + run;
-    o.ntask[b_first + f] = nt;
-    o.toff[b_first + f] = trun;
+    if constexpr (FE) {
+      const uint32_t nt = (c + Lm1) >> o.log_L;
+      o.off[b_first + f] = start + run;
+      o.ntask[b_first + f] = nt;
+      o.toff[b_first + f] = trun;
+      trun += nt;
+    }
     run += c;
-    trun += nt;
   }
   __syncthreads();
-  // the bin's share of the global figures: fire and forget
-  {
+  if constexpr (FE) {
+    // the bin's share of the global figures: fire and forget
     uint32_t* mine = o.fe + FE_SET + o.parity * FE_SET_WORDS + (blockIdx.x % FE_REPL) * FE_ROW;
-    for (uint32_t k = tid; k <= full_bin; k += nthr)
+    for (uint32_t k = tid; k <= task_full_bin(o.log_L); k += nthr)
       if (s_th[k]) atomicAdd(mine + 2 + k, s_th[k]);
     if (tid == 0) {
       if (s_red[0]) atomicAdd(mine, s_red[0]);
@@ -617,12 +620,30 @@ __global__ void __launch_bounds__(512) msm_fine_sort_fused(const uint32_t* __res
     }
   }
 }
+__global__ void __launch_bounds__(512) msm_fine_sort(const uint32_t* __restrict__ part_entry,
+                                                     const uint16_t* __restrict__ part_fine,
+                                                     const uint32_t* __restrict__ coff,
+                                                     const uint32_t* __restrict__ ccnt, uint32_t B, uint32_t shift,
+                                                     uint32_t nbw, uint32_t* __restrict__ counts,
+                                                     uint32_t* __restrict__ sorted) {
+  side_kernel_prio();
+  fine_sort_body<false>(part_entry, part_fine, coff, ccnt, B, shift, nbw, counts, sorted, FrontEndOut{}, nullptr, nullptr);
+}
+__global__ void __launch_bounds__(512) msm_fine_sort_fused(const uint32_t* __restrict__ part_entry,
+                                                           const uint16_t* __restrict__ part_fine,
+                                                           const uint32_t* __restrict__ coff,
+                                                           const uint32_t* __restrict__ ccnt, uint32_t B, uint32_t shift,
+                                                           uint32_t nbw, uint32_t* __restrict__ counts,
+                                                           uint32_t* __restrict__ sorted, FrontEndOut o) {
+  side_kernel_prio();
+  __shared__ uint32_t s_th[TASK_BINS];
+  __shared__ uint32_t s_red[2];
+  fine_sort_body<true>(part_entry, part_fine, coff, ccnt, B, shift, nbw, counts, sorted, o, s_th, s_red);
+}
 
-// ---- task ordering: longest tasks first, equal lengths side by side, so the 64 lanes of a
-// wave run the same number of additions (bucket sizes are Poisson-distributed: without this
-// a wave waits for its largest bucket, ~30 % of the lanes' time idle).
-static constexpr uint32_t ACC_TICKET = 8;          // word of meta_ that holds msm_accumulate's task counter
-static_assert(TASK_BINS == TASK_BINS_FE, "one histogram of task lengths");
+// ------------------------------------------------------------------ 6: task ordering
+// Longest tasks first, equal lengths side by side, so the 64 lanes of a wave run the same number of additions (bucket sizes
+// are Poisson-distributed: without this a wave waits for its largest bucket, ~30 % of the lanes' time idle).
 
 // thist[bin * nblk + blk] = number of tasks of (clamped) length `bin` in block blk
 __global__ void __launch_bounds__(256) msm_task_hist(const uint32_t* __restrict__ cnt, uint32_t NB,
@@ -632,16 +653,7 @@ __global__ void __launch_bounds__(256) msm_task_hist(const uint32_t* __restrict_
   __shared__ uint32_t s_h[TASK_BINS];
   for (uint32_t k = threadIdx.x; k < TASK_BINS; k += blockDim.x) s_h[k] = 0;
   __syncthreads();
-  const uint32_t full_bin = min(1u << log_L, TASK_BINS - 1);
-  for (uint32_t q = threadIdx.x; q < task_block; q += blockDim.x) {
-    uint32_t b = blockIdx.x * task_block + q;
-    if (b < NB) {
-      // a bucket is nfull tasks of exactly L entries plus at most one shorter task
-      uint32_t cv = cnt[b], nfull = cv >> log_L, rem = cv - (nfull << log_L);
-      if (nfull) atomicAdd(&s_h[full_bin], nfull);
-      if (rem) atomicAdd(&s_h[min(rem, TASK_BINS - 1)], 1u);
-    }
-  }
+  count_block_tasks(s_h, cnt, NB, log_L, task_block);
   __syncthreads();
   for (uint32_t k = threadIdx.x; k < TASK_BINS; k += blockDim.x) thist[k * gridDim.x + blockIdx.x] = s_h[k];
 }
@@ -669,13 +681,7 @@ __global__ void __launch_bounds__(256) msm_task_scan(uint32_t* __restrict__ this
     }
   }
   s_sum[tid] = a;
-  __syncthreads();
-  for (uint32_t d = 1; d < 256; d <<= 1) {
-    uint32_t u = tid >= d ? s_sum[tid - d] : 0;
-    __syncthreads();
-    s_sum[tid] += u;
-    __syncthreads();
-  }
+  block_scan<1>(tid, 256, true, s_sum);
   uint32_t run = s_sum[tid] - a;
   {
     uint32_t row = row0, col = col0;
@@ -697,21 +703,7 @@ __global__ void __launch_bounds__(256) msm_task_scatter(const uint32_t* __restri
   __shared__ uint32_t s_c[TASK_BINS];
   for (uint32_t k = threadIdx.x; k < TASK_BINS; k += blockDim.x) s_c[k] = thist[k * gridDim.x + blockIdx.x];
   __syncthreads();
-  const uint32_t full_bin = min(1u << log_L, TASK_BINS - 1);
-  for (uint32_t q = threadIdx.x; q < task_block; q += blockDim.x) {
-    uint32_t b = blockIdx.x * task_block + q;
-    if (b < NB) {
-      uint32_t cv = cnt[b], nfull = cv >> log_L, rem = cv - (nfull << log_L);
-      if (nfull) {
-        uint32_t pos = atomicAdd(&s_c[full_bin], nfull);
-        for (uint32_t seg = 0; seg < nfull; seg++) order[pos + seg] = make_uint2(b, seg);
-      }
-      if (rem) {
-        uint32_t pos = atomicAdd(&s_c[min(rem, TASK_BINS - 1)], 1u);
-        order[pos] = make_uint2(b, nfull);
-      }
-    }
-  }
+  place_bucket_tasks(s_c, cnt, NB, log_L, task_block, order);
 }
 
 // the same after msm_fine_sort_fused: every workgroup first sums the replicas of the task-length histogram the sort left (the
@@ -736,7 +728,7 @@ __global__ void __launch_bounds__(256) msm_task_scatter_reserve(const uint32_t* 
   side_kernel_prio();
   __shared__ uint32_t s_c[TASK_BINS], s_tot[TASK_BINS], s_red[2];
   const uint32_t tid = threadIdx.x;
-  const uint32_t full_bin = min(1u << log_L, TASK_BINS - 1), nbins = full_bin + 1;
+  const uint32_t nbins = task_full_bin(log_L) + 1;
   const uint32_t* set = ft.fe + FE_SET + ft.parity * FE_SET_WORDS;
   for (uint32_t k = tid; k < TASK_BINS; k += blockDim.x) { s_c[k] = 0; s_tot[k] = 0; }
   if (tid < 2) s_red[tid] = 0;
@@ -751,29 +743,11 @@ __global__ void __launch_bounds__(256) msm_task_scatter_reserve(const uint32_t* 
     if (tk) atomicAdd(&s_red[0], tk);
     if (mxr) atomicMax(&s_red[1], mxr);
   }
-  for (uint32_t q = tid; q < task_block; q += blockDim.x) {
-    uint32_t b = blockIdx.x * task_block + q;
-    if (b < NB) {
-      uint32_t cv = cnt[b], nfull = cv >> log_L, rem = cv - (nfull << log_L);
-      if (nfull) atomicAdd(&s_c[full_bin], nfull);
-      if (rem) atomicAdd(&s_c[min(rem, TASK_BINS - 1)], 1u);
-    }
-  }
+  count_block_tasks(s_c, cnt, NB, log_L, task_block);
   __syncthreads();
   if (blockIdx.x == 0 && tid == 0) {
-    const uint32_t entries = ft.coff[ft.NBc], tasks = s_red[0], largest = s_red[1];
-    ft.off[NB] = entries;
-    ft.toff[NB] = ft.tbase[ft.NBc];
-    ft.meta[0] = entries;
-    ft.meta[1] = tasks;
-    ft.meta[2] = largest;
     ft.meta[ft.ticket_word] = 0;          // msm_accumulate's task counter (the next launch on this stream)
-    if (ft.host_meta) {
-      ft.host_meta[0] = entries;
-      ft.host_meta[1] = tasks;
-      ft.host_meta[2] = largest;
-      __threadfence_system();
-    }
+    write_job_totals(ft.off, ft.toff, NB, ft.meta, ft.host_meta, ft.coff[ft.NBc], ft.tbase[ft.NBc], s_red[0], s_red[1]);
   }
   // position of this workgroup's tasks of length k: every longer task first, then what other workgroups reserved before
   for (uint32_t k = tid; k < nbins; k += blockDim.x) {
@@ -783,20 +757,7 @@ __global__ void __launch_bounds__(256) msm_task_scatter_reserve(const uint32_t* 
     s_c[k] = base + (mine ? atomicAdd(ft.fe + FE_CURSOR + k, mine) : 0u);
   }
   __syncthreads();
-  for (uint32_t q = tid; q < task_block; q += blockDim.x) {
-    uint32_t b = blockIdx.x * task_block + q;
-    if (b < NB) {
-      uint32_t cv = cnt[b], nfull = cv >> log_L, rem = cv - (nfull << log_L);
-      if (nfull) {
-        uint32_t pos = atomicAdd(&s_c[full_bin], nfull);
-        for (uint32_t seg = 0; seg < nfull; seg++) order[pos + seg] = make_uint2(b, seg);
-      }
-      if (rem) {
-        uint32_t pos = atomicAdd(&s_c[min(rem, TASK_BINS - 1)], 1u);
-        order[pos] = make_uint2(b, nfull);
-      }
-    }
-  }
+  place_bucket_tasks(s_c, cnt, NB, log_L, task_block, order);
 }
 
 // the same three scans for NB <= 4 Ki buckets in ONE workgroup (a small MSM is a chain of ~25 launches with
@@ -821,14 +782,7 @@ __global__ void __launch_bounds__(1024) msm_scan_small(const uint32_t* __restric
     m = max(m, v[k]);
   }
   s_a[tid] = a; s_t[tid] = t; s_m[tid] = m;
-  __syncthreads();
-  for (uint32_t d = 1; d < 1024; d <<= 1) {
-    uint32_t va = 0, vt = 0, vm = 0;
-    if (tid >= d) { va = s_a[tid - d]; vt = s_t[tid - d]; vm = s_m[tid - d]; }
-    __syncthreads();
-    s_a[tid] += va; s_t[tid] += vt; s_m[tid] = max(s_m[tid], vm);
-    __syncthreads();
-  }
+  block_scan<3, true>(tid, 1024, true, s_a, s_t, s_m);
   uint32_t ra = s_a[tid] - a, rt = s_t[tid] - t;
 #pragma unroll
   for (uint32_t k = 0; k < SCAN_SMALL_PER; k++) {
@@ -841,22 +795,10 @@ __global__ void __launch_bounds__(1024) msm_scan_small(const uint32_t* __restric
       rt += nt;
     }
   }
-  if (tid == 1023) {
-    if (off) off[NB] = s_a[tid];
-    toff[NB] = s_t[tid];
-    meta[0] = s_a[tid];
-    meta[1] = s_t[tid];
-    meta[2] = s_m[tid];
-    if (host_meta) {
-      host_meta[0] = s_a[tid];
-      host_meta[1] = s_t[tid];
-      host_meta[2] = s_m[tid];
-      __threadfence_system();
-    }
-  }
+  if (tid == 1023) write_job_totals(off, toff, NB, meta, host_meta, s_a[tid], s_t[tid], s_t[tid], s_m[tid]);
 }
 
-// exclusive scans over NB buckets (one launch for small NB, else two); host_meta: see msm_scan_sums
+// exclusive scans over NB buckets (one launch for small NB, else two); host_meta: see write_job_totals
 static hipError_t launch_scan(const uint32_t* cnt, uint32_t NB, uint32_t log_L, uint32_t* off, uint32_t* ntask,
                               uint32_t* toff, uint32_t* bsum, uint32_t* meta, hipStream_t stream, uint32_t* host_meta = nullptr) {
   if (NB <= SCAN_SMALL_PER * 1024) {

@@ -48,7 +48,9 @@ _U = [(n, "uniform", {}, MODES) for n in (1 << 15, 1 << 18, 1 << 19, 1 << 20, (1
 _SINGLE_PASS = [(1 << 12, "uniform", {}, MODES), (1 << 14, "uniform", {}, MODES),
                 (1 << 12, "equal", {}, MODES), (1 << 14, "byte", {}, MODES)]
 _SMALL_TWO_PASS = [(1 << 12, "uniform", {"msm.two_pass": 2}, MODES), (1 << 14, "uniform", {"msm.two_pass": 2}, MODES),
-                   (1 << 12, "equal", {"msm.two_pass": 2}, MODES), (1 << 14, "byte", {"msm.two_pass": 2}, MODES)]
+                   (1 << 12, "equal", {"msm.two_pass": 2}, MODES), (1 << 14, "byte", {"msm.two_pass": 2}, MODES),
+                   # c = 12, B = 4 bins of F = 512 buckets: a window's 2^14 equal digits share ONE bin, the smallest E > SORT_TILE
+                   (1 << 14, "equal", {"msm.two_pass": 2}, MODES)]
 _AT_2_20 = [(1 << 20, d, {}, MODES) for d in ("equal", "byte", "selector", "sparse", "tiled32", "pm_pairs", "s_neg_s")]
 _SIGNED = [(1 << 20, "signed16", {"msm.window_bits": 16}, MODES),    # NBc = 16 windows x 256 bins = 4096
            (1 << 19, "signed13", {"msm.window_bits": 13}, MODES),    # 20 x 128 = 2560
