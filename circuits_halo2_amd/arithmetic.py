@@ -152,6 +152,22 @@ def lookup_permute_small(inp, table, rows: int):
     return a, s
 
 
+def lookup_permute(inp, table, rows: int):
+    """halo2's permute_expression_pair on the device for any table (sg_lookup_permute_dev): returns the permuted input / table
+    columns over `rows` usable rows (device tensors, Montgomery words).  A' is the input in increasing integer order; the table
+    values that no first occurrence takes fill the repeated rows in increasing integer order, as lookup_permute_small places
+    them.  Raises ValueError when an input value is not in the table."""
+    import torch
+    a = torch.empty(32 * rows, dtype=torch.uint8, device="cuda")
+    s = torch.empty(32 * rows, dtype=torch.uint8, device="cuda")
+    rc = ffi.lib().sg_lookup_permute_dev(ffi.dev_ptr(inp), ffi.dev_ptr(table), C.c_size_t(rows), ffi.dev_ptr(a), ffi.dev_ptr(s),
+                                         ffi.current_stream_ptr())
+    if rc == -6:        # SG_ERR_WITNESS
+        raise ValueError("lookup input value not in the table")
+    ffi.check(rc)
+    return a, s
+
+
 def fr_random(key: bytes, stream_id: int, n: int):
     """n uniform field elements on the device from ChaCha20(key) (sg_fr_random_dev): blinding values of a proof"""
     import torch

@@ -229,6 +229,48 @@ int sg_lookup_permute_small_async_dev(const void* d_input, const void* d_table, 
   if (e != hipSuccess) return hip_fail("lookup permutation", e);
   return SG_OK;
 }
+// The general path: one launch sequence for both forms.  The work space is the stream's own (scratch_for, slot 9): calls on one
+// stream are ordered, so each may reuse what the one before it used, and a larger `rows` grows the buffer by DevBuf::reserve's rule
+// -- the outgrown block is retired, not freed (devmem.h), so launches already queued on the stream keep reading valid memory.  A
+// call with the same or fewer rows allocates nothing.
+static int lookup_permute_launch(const char* who, const void* d_input, const void* d_table, size_t rows, void* d_permuted_input,
+                                 void* d_permuted_table, void* d_status, hipStream_t s, uint32_t** work_out) {
+  if (rows > LS_MAX_ROWS) return fail(SG_ERR_INVALID, "sg_lookup_permute: at most 2^31 - 1 rows");
+  uint8_t* wb = nullptr;
+  hipError_t e = scratch_for(s, 9, lookup_sort_work_bytes(rows), &wb);
+  if (e != hipSuccess) return hip_fail("lookup permutation work space", e);
+  uint32_t* work = reinterpret_cast<uint32_t*>(wb);
+  e = poly_lookup_permute(static_cast<const fp_words*>(d_input), static_cast<const fp_words*>(d_table), rows, work,
+                          static_cast<fp_words*>(d_permuted_input), static_cast<fp_words*>(d_permuted_table),
+                          static_cast<uint32_t*>(d_status), s);
+  if (e != hipSuccess) return hip_fail(who, e);
+  *work_out = work;
+  return SG_OK;
+}
+int sg_lookup_permute_dev(const void* d_input, const void* d_table, size_t rows, void* d_permuted_input, void* d_permuted_table,
+                          void* stream) {
+  if (rows && (!d_input || !d_table || !d_permuted_input || !d_permuted_table)) return fail(SG_ERR_INVALID, "sg_lookup_permute: null argument");
+  if (rows == 0) return SG_OK;
+  LOCKED_CTX();
+  hipStream_t s = pick_stream(stream);
+  uint32_t* work = nullptr;
+  TRY(lookup_permute_launch("sg_lookup_permute", d_input, d_table, rows, d_permuted_input, d_permuted_table, nullptr, s, &work));
+  uint32_t h_flag = 0;
+  hipError_t e = host_copy_d2h(&h_flag, work + LS_FLAG, sizeof h_flag, s);
+  if (e != hipSuccess) return hip_fail("lookup permutation", e);
+  if (h_flag) return fail(SG_ERR_WITNESS, "sg_lookup_permute: an input value is not in the table");
+  return SG_OK;
+}
+int sg_lookup_permute_async_dev(const void* d_input, const void* d_table, size_t rows, void* d_permuted_input, void* d_permuted_table,
+                                void* d_status, void* stream) {
+  if (!d_status || (rows && (!d_input || !d_table || !d_permuted_input || !d_permuted_table)))
+    return fail(SG_ERR_INVALID, "sg_lookup_permute_async: null argument");
+  if (rows == 0) return SG_OK;
+  LOCKED_CTX();
+  uint32_t* work = nullptr;
+  return lookup_permute_launch("sg_lookup_permute_async", d_input, d_table, rows, d_permuted_input, d_permuted_table, d_status,
+                               pick_stream(stream), &work);
+}
 int sg_fr_flag_noncanonical_dev(const void* const* d_cols, uint32_t m, size_t n, void* d_flag, void* stream) {
   if (!d_flag || (m && !d_cols) || m > 16) return fail(SG_ERR_INVALID, "sg_fr_flag_noncanonical: bad argument");
   for (uint32_t j = 0; j < m; j++)

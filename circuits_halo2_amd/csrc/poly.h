@@ -87,6 +87,12 @@ hipError_t poly_lookup_permute_small(const fp_words* d_input, const fp_words* d_
 hipError_t poly_lookup_permute_small_chained(const fp_words* d_input, const fp_words* d_table, size_t rows, uint32_t* d_work,
                                              uint32_t* d_flag, uint32_t* d_next_work, uint32_t* d_next_flag, fp_words* d_permuted_input,
                                              fp_words* d_permuted_table, uint32_t* d_status, hipStream_t stream);
+// The same for any table (poly_lookup_sort.cuh): both columns are sorted as 254-bit integers and the table is placed by the rule
+// above.  d_work: lookup_sort_work_bytes(rows) bytes, 16-byte aligned; the verdict (0 ok, 1 an input value that is not in the
+// table) is left in d_work[LS_FLAG] and, if d_status is given, written there by the last launch; the outputs are Montgomery
+// words, written under verdict 0 only, and must not overlap the inputs.  LS_LAUNCHES launches, no host wait.
+hipError_t poly_lookup_permute(const fp_words* d_input, const fp_words* d_table, size_t rows, uint32_t* d_work,
+                               fp_words* d_permuted_input, fp_words* d_permuted_table, uint32_t* d_status, hipStream_t stream);
 // n uniform field elements from ChaCha20 (RFC 8439 block function) keyed by `key` (8 LE words): element i takes the
 // first 32 bytes of block (counter = i, nonce = (attempt, stream_lo, stream_hi)), top two bits cleared, and is
 // redrawn with attempt + 1 while >= r (~24 %); the accepted limbs are written as they are (a uniform value in any

@@ -9,12 +9,13 @@
 //
 // This file: evaluation, batch inversion, the element-wise product, the canonical-range check and the linear combinations, each
 // launch function under its kernels.  poly_scan.cuh: the shared device helpers, prefix product, grand products, Kate division;
-// poly_lookup_permute.cuh; poly_random.cuh.  The host geometry of all of them is in poly_plan.h.
+// poly_lookup_permute.cuh (range tables), poly_lookup_sort.cuh (any table); poly_random.cuh.  The host geometry of all of them is in poly_plan.h.
 #include "poly.h"
 #include "side_prio.cuh"
 
 #include "poly_scan.cuh"
 #include "poly_lookup_permute.cuh"
+#include "poly_lookup_sort.cuh"
 #include "poly_random.cuh"
 
 namespace sg {

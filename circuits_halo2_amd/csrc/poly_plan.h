@@ -75,6 +75,38 @@ inline size_t kate_tmp_elems() { return POLY_SCAN_MAX + 1; }
 inline size_t kate_batch_powers_bytes(uint32_t m) { return (size_t)m * KATE_POWERS_BYTES; }
 inline size_t kate_batch_tmp_elems(size_t n, uint32_t m) { return (size_t)m * ((n + KD_BLOCK - 1) / KD_BLOCK) + 1; }
 
+// ---- lookup permutation for any table (poly_lookup_sort.cuh): LSD radix sort of both columns' 254-bit keys, LS_DIGIT_BITS per
+// pass, a workgroup per LS_TILE keys in the histogram and scatter launches and in the two flag scans of the placement
+static constexpr uint32_t LS_DIGIT_BITS = 8, LS_BINS = 1u << LS_DIGIT_BITS, LS_PASSES = 256 / LS_DIGIT_BITS;
+static constexpr uint32_t LS_THREADS = 256, LS_ITEMS = 4, LS_TILE = LS_THREADS * LS_ITEMS;
+static constexpr uint32_t LS_HEAD_WORDS = 64;   // per column the OR of all keys and the OR of their complements (8 + 8 words), then the verdict
+static constexpr uint32_t LS_FLAG = 32;         // the verdict's word in the head
+static constexpr size_t LS_MAX_ROWS = ((size_t)1 << 31) - 1;
+inline size_t lookup_sort_tiles(size_t rows) { return (rows + LS_TILE - 1) / LS_TILE; }
+// work space in u32 words: head | keys[column][ping-pong][rows][8] | hist[column][digit][tile] | used[rows] | repeat[rows] |
+// rank[rows] | left[rows] | sums[2][tiles rounded up to 4] -- every part but repeat / rank / left starts on a 16-byte boundary
+struct LookupSortLayout {
+  size_t keys, hist, used, repeat, rank, left, sums, sums_stride, words;
+};
+inline LookupSortLayout lookup_sort_layout(size_t rows) {
+  const size_t tiles = lookup_sort_tiles(rows);
+  LookupSortLayout l;
+  l.keys = LS_HEAD_WORDS;
+  l.hist = l.keys + 4 * 8 * rows;
+  l.used = l.hist + 2 * (size_t)LS_BINS * tiles;
+  l.repeat = l.used + rows;
+  l.rank = l.repeat + rows;
+  l.left = l.rank + rows;
+  l.sums = l.left + rows;
+  l.sums_stride = (tiles + 3) & ~(size_t)3;
+  l.words = l.sums + 2 * l.sums_stride;
+  return l;
+}
+inline size_t lookup_sort_work_bytes(size_t rows) { return lookup_sort_layout(rows).words * sizeof(uint32_t); }
+// launches of one call whatever the keys hold (a pass over a digit on which a column is constant returns at once): the head's
+// memset, the keys, three per pass, then mark, tile sums, their scan, compaction, write
+static constexpr uint32_t LS_LAUNCHES = 2 + 3 * LS_PASSES + 5;
+
 // ---- linear combinations
 static constexpr uint32_t LINCOMB_MAX = 32;
 static constexpr uint32_t LINCOMB_LOW_MAX = 8;

@@ -277,7 +277,7 @@ int sg_fr_from_montgomery_dev(const void* d_in, void* d_out, size_t n, void* str
 /* halo2 lookup::prover::permute_expression_pair (§3.1 step 4) for range tables, on the device: rows = the usable
  * rows; A' (d_permuted_input) = the input rows in increasing order, S' (d_permuted_table) = the table rows
  * rearranged so that every row has A'[i] == S'[i] or A'[i] == A'[i-1].  Handles tables whose values are all below
- * 2^16 (SG_ERR_UNSUPPORTED otherwise: sort on the host as upstream does); SG_ERR_WITNESS if an input value is not
+ * 2^16 (SG_ERR_UNSUPPORTED otherwise: sg_lookup_permute_dev below takes any table); SG_ERR_WITNESS if an input value is not
  * in the table.  Synchronises the stream (the status is known on return). */
 int sg_lookup_permute_small_dev(const void* d_input, const void* d_table, size_t rows, void* d_permuted_input,
                                 void* d_permuted_table, void* stream);
@@ -288,6 +288,25 @@ int sg_lookup_permute_small_dev(const void* d_input, const void* d_table, size_t
  * table (a property of the proving key) issues this, goes on, and looks at the status where it waits anyway.  Asynchronous. */
 int sg_lookup_permute_small_async_dev(const void* d_input, const void* d_table, size_t rows, void* d_permuted_input,
                                       void* d_permuted_table, void* d_status, void* stream);
+/* The same for ANY table (full-width field elements: a theta-compressed multi-column lookup, a table of hashes): both columns are
+ * sorted on the device as 254-bit integers.  d_input / d_table: `rows` Montgomery Fr each (a word value at or above r counts as
+ * its residue); outputs: canonical Montgomery words.  A' = the input in increasing integer order; S' = the table rearranged so
+ * that every row has A'[i] == S'[i] or A'[i] == A'[i-1]: a first occurrence in A' takes the first table row of its value, and the
+ * table values left over go IN INCREASING INTEGER ORDER INTO THE REPEATED ROWS IN INCREASING ROW ORDER -- the rule of the range-table
+ * functions above (a range table gives the same words on either path) and of the compiled host prover.  Upstream fills the
+ * repeated rows from the last one backwards, another valid arrangement: S' differs from upstream's row by row, the lookup argument
+ * holds for both.  (The Python host twin, prover.permute_expression_pair, orders multi-limb leftovers low limb first, a third
+ * valid arrangement; aligning it with this rule is a behaviour change left to a later revision.)
+ * rows == 0: SG_OK, nothing done; rows >= 2^31 or a null pointer: SG_ERR_INVALID.  The outputs must not overlap the inputs (not
+ * detected).  SG_ERR_WITNESS if an input value is not in the table.  Synchronises the stream (the status is known on return). */
+int sg_lookup_permute_dev(const void* d_input, const void* d_table, size_t rows, void* d_permuted_input, void* d_permuted_table,
+                          void* stream);
+/* The same without the wait: *d_status (u32 in device-visible memory) receives 0 (done) or 1 (an input value is not in the table)
+ * when the kernels have run -- never 2: no table is unsupported; the outputs are valid only under status 0 (under 1 they are not
+ * written).  The work space is the stream's and grows to the largest `rows` seen: after the first call on a stream, a call with the
+ * same or fewer rows allocates nothing.  Asynchronous. */
+int sg_lookup_permute_async_dev(const void* d_input, const void* d_table, size_t rows, void* d_permuted_input, void* d_permuted_table,
+                                void* d_status, void* stream);
 /* n uniform field elements written to d_out (blinding rows, the random polynomial of create_proof -- upstream draws
  * them from `OsRng`; here the OS supplies a 32-byte key per proof and ChaCha20, RFC 8439's block function, expands it
  * on the device): element i = the first 32 bytes of block(key, counter = i, nonce = (attempt, stream_id)) with the top
@@ -604,6 +623,7 @@ int sg_msm_launch_log(uint32_t* out_words, size_t cap_records, size_t* n_records
  *     nothing removed or resized
  *   4: sg_get_param returns the value in effect of every parameter, its default until it is set (revision 3: 0 for a per-lane one
  *     never set); sg_set_param and sg_get_param refuse the same names, and setting a per-lane parameter no longer binds a device
+ *     (still 4: sg_lookup_permute_dev and sg_lookup_permute_async_dev added; nothing changed meaning, nothing removed or resized)
  * A binding built against revision r must refuse a library whose sg_abi_version() < r. */
 #define SG_ABI_VERSION 4
 int sg_abi_version(void);

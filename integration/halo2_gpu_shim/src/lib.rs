@@ -102,6 +102,26 @@ extern "C" {
         d_permuted_table: *mut c_void,
         stream: *mut c_void,
     ) -> c_int;
+    // ... and for any table (full-width values): both columns sorted on the device as integers; the table values that no first
+    // occurrence takes fill the repeated rows in increasing integer order, top row first (upstream fills them from the last row)
+    pub fn sg_lookup_permute_dev(
+        d_input: *const c_void,
+        d_table: *const c_void,
+        rows: size_t,
+        d_permuted_input: *mut c_void,
+        d_permuted_table: *mut c_void,
+        stream: *mut c_void,
+    ) -> c_int;
+    // the same without the wait: *d_status = 0 (done) or 1 (an input value is not in the table) when the kernels have run
+    pub fn sg_lookup_permute_async_dev(
+        d_input: *const c_void,
+        d_table: *const c_void,
+        rows: size_t,
+        d_permuted_input: *mut c_void,
+        d_permuted_table: *mut c_void,
+        d_status: *mut c_void,
+        stream: *mut c_void,
+    ) -> c_int;
 }
 
 /// `sg_graph` of include/summa_gpu.h: the plain-struct image of halo2's `GraphEvaluator` (what `pk.ev` holds)
