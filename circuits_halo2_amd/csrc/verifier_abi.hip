@@ -177,9 +177,7 @@ Fr expected_h_eval(const std::map<EvalKey, Fr>& evals, const Fr& beta, const Fr&
   };
   std::vector<Fr> terms;
   for (const ci::E& g : ci::gates(n_currencies)) terms.push_back(eval(g));
-  // permutation argument: columns (f2, a0, a1, f3, a2, instance) in chunks of CHUNK
-  const uint32_t perm_kind[NUM_SIGMA] = {SG_VS_FIXED, SG_VS_ADVICE, SG_VS_ADVICE, SG_VS_FIXED, SG_VS_ADVICE, SG_VS_INSTANCE};
-  const uint32_t perm_idx[NUM_SIGMA] = {2, 0, 1, 3, 2, 0};
+  // permutation argument: columns (f2, a0, a1, f3, a2, instance) in chunks of CHUNK (perm_kind / perm_idx)
   const uint32_t chunks = (NUM_SIGMA + CHUNK - 1) / CHUNK, last = chunks - 1;
   auto z = [&](uint32_t j, int rot = 0) -> const Fr& { return ev(Z_, j, rot); };
   terms.push_back(l_0 * (one - z(0)));
@@ -281,23 +279,12 @@ bool verify(const VerifyingKeyView& vk, const uint8_t* proof, size_t len, const 
   // SHPLONK: per rotation set, the zeta-combination of its polynomials, interpolated through the claimed values and evaluated
   // at mu; sets weighted by nu^i Z_{T \ S_i}(mu) / Z_{T \ S_0}(mu)
   const std::vector<RotationSet> sets = rotation_sets();
-  std::map<int, Fr> point, mu_minus;
-  for (const RotationSet& s : sets)
-    for (int r : s.rots)
-      if (!point.count(r)) {
-        point[r] = x * omega_pow(r);
-        mu_minus[r] = mu - point[r];
-      }
-  std::vector<Fr> outside;
-  for (const RotationSet& s : sets) {
-    Fr d = one;
-    for (auto& kv : mu_minus)
-      if (std::find(s.rots.begin(), s.rots.end(), kv.first) == s.rots.end()) d = d * kv.second;
-    outside.push_back(d);
-  }
+  const RotationPoints point{x, omega, omega_pow(-1)};
+  const OutsideProducts op = outside_products(sets, point, mu);   // (nothing inverted yet: a zero is the proof's fault)
+  const std::map<int, Fr>& mu_minus = op.mu_minus;
+  const std::vector<Fr>& outside = op.outside;
   const Fr norm0 = inv_or_reject(outside[0]);
-  Fr z_s0 = one;
-  for (int r : sets[0].rots) z_s0 = z_s0 * mu_minus[r];
+  const Fr& z_s0 = op.z_s0;
   std::map<Key, Fr> coeff;   // commitment -> its scalar in the final multi-scalar multiplication
   Fr r_eval = Fr::zero(), nu_pow = one;
   for (size_t si = 0; si < sets.size(); si++) {
@@ -305,9 +292,9 @@ bool verify(const VerifyingKeyView& vk, const uint8_t* proof, size_t len, const 
     std::vector<Fr> weights;   // barycentric weights of the set's points, evaluated at mu
     Fr wsum = Fr::zero();
     for (int r : s.rots) {
-      Fr den = mu_minus[r];
+      Fr den = mu_minus.at(r);
       for (int r2 : s.rots)
-        if (r2 != r) den = den * (point[r] - point[r2]);
+        if (r2 != r) den = den * (point(r) - point(r2));
       weights.push_back(inv_or_reject(den));
       wsum = wsum + weights.back();
     }

@@ -44,7 +44,7 @@ extern "C" {
  * What would break it (a change of `ConstraintSystem` that needs the C++ driver in include/summa_prover.hpp rebuilt, not data):
  * another number of advice / fixed / permutation columns (SP_NUM_* below are compile-time), a second lookup or a lookup with
  * several input expressions (theta would have to be squeezed BEFORE the permuted columns are committed: the driver commits them
- * with the advice columns, summa_prover.hpp phase 2), a second instance column or an instance rotation, a rotation beyond +-1
+ * with the advice columns, ProofRun::advice_and_lookup_columns in summa_prover.hpp), a second instance column or an instance rotation, a rotation beyond +-1
  * (the multi-open's rotation sets are {0}, {0, 1}, {-1, 0, 1, last}: fixed), a constraint degree above 6 (more quotient pieces), a
  * permutation chunk length other than degree - 2 = 4.  sp_key_create cannot see most of these from its arguments: it checks the
  * programs' column indices and rotations and refuses what it can (SG_ERR_INVALID); the rest is the caller's contract. */

@@ -1,7 +1,8 @@
 // Host-only exercise of the product's host arithmetic for the sanitizer leg (tests/test_sanitizers_cpu.py builds this
 // with -fsanitize=address,undefined): csrc/host_curve.h (Fq, Fq2, G1 / G2 group laws), csrc/host_pairing.h (Miller loop,
-// both final exponentiations), and the host parts of include/summa_prover.hpp / summa_circuit.hpp (Fr, Keccak-256,
-// Blake2b, both transcripts, the lookup permutation, the floor plan and the pinned verifying-key text).  Every check is
+// both final exponentiations), include/summa_fr.hpp (Fr), summa_transcript.hpp (Keccak-256, Blake2b, both transcripts),
+// summa_proof_host.hpp (the lookup permutation) and the host parts of summa_circuit.hpp (the floor plan and the pinned
+// verifying-key text; it includes summa_prover.hpp for the Graph type, hence the HIP include path).  Every check is
 // self-contained (algebraic identities, published test vectors); the program prints "host math ok" and exits 0.
 //   build: g++ -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -Icircuits_halo2_amd/csrc tests/cpp/host_math_check.cpp -L/opt/rocm/lib -lamdhip64
 #include <cstdio>

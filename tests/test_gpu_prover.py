@@ -210,6 +210,33 @@ def test_cpp_prover_proof_is_accepted(k, tmp_path):
     assert not SV.verify(bytes(p), s["asg"]["instances"], s["vk"])
 
 
+def test_cpp_prover_under_a_fixed_blinding_key_equals_the_python_driver(setup, tmp_path):
+    """the two drivers number their blinding draws alike (1-5 advice and permuted columns, 6-8 grand products, 9 the random
+    polynomial), so under one ChaCha20 key the compiled driver (Options::blinding_key, the tool's fourth argument) writes the
+    proof prover.create_proof(seed=key) returns, byte for byte; without a key it draws its own and the proof differs"""
+    import subprocess
+    from oracle import summa_verifier as SV
+    s = setup
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = os.path.join(root, "tools", "create_proof_cpp")
+    assert os.path.exists(exe), "tools/create_proof_cpp not built (python __graft_entry__.py)"
+    advice = [s["dev"](c) for c in s["asg"]["advice"]]
+    inst = s["asg"]["instances"]
+    bundle, out = str(tmp_path / "bundle.bin"), str(tmp_path / "proof.bin")
+    s["prover"].export_bundle(bundle, s["params"], s["pk"], advice, inst)
+    key = seeded_rng(77)
+    want = s["prover"].create_proof(s["params"], s["pk"], advice, inst, key)
+    r = subprocess.run([exe, bundle, out, "1", key.hex()], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    fixed = open(out, "rb").read()
+    assert len(fixed) == 2144 and fixed == want
+    r = subprocess.run([exe, bundle, out, "1"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    fresh = open(out, "rb").read()
+    assert len(fresh) == 2144 and fresh != want and SV.verify(fresh, inst, s["vk"])
+    assert subprocess.run([exe, bundle, out, "1", "abc"], capture_output=True).returncode == 2   # not 64 hex digits
+
+
 def test_fr_random_matches_the_chacha20_twin():
     """sg_fr_random_dev: bit-exact with the oracle's RFC 8439 ChaCha20 twin (pinned by the RFC's test vector in
     tests/test_verifier_cpu.py), for several keys / stream ids / lengths; rejection sampling included (~24 % redraws)"""

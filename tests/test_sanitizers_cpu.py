@@ -2,9 +2,10 @@
 this pool): the host arithmetic of the product and the C oracle rebuilt with -fsanitize=address,undefined and run over
 their own checks.
 
-* tests/cpp/host_math_check.cpp: csrc/host_curve.h, csrc/host_pairing.h, the host parts of include/summa_prover.hpp
-  (Fr, Keccak, Blake2b, both transcripts, the lookup permutation) and of include/summa_circuit.hpp (floor plan, gate
-  program, verifying-key digest);
+* tests/cpp/host_math_check.cpp: csrc/host_curve.h, csrc/host_pairing.h, the compiled prover's host headers
+  (include/summa_fr.hpp: Fr; summa_transcript.hpp: Keccak, Blake2b, both transcripts; summa_proof_host.hpp: the lookup
+  permutation) and the host parts of include/summa_circuit.hpp (floor plan, gate program, verifying-key digest); the
+  multi-open's scalars have their own sanitized check, tests/test_proof_host_cpu.py;
 * the 29-bit limb arithmetic of the kernels compiled for the host (tests/checks/limb_*_check.cpp) against Python integers;
 * tools/circuit_dump.cpp (the compiled floor plan and gate programs): same bytes as the unsanitized build;
 * oracle/bn254_oracle.c (`make asan`): MSM, NTT, domain operations, Poseidon tree and the quotient blocks against the

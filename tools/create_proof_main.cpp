@@ -2,7 +2,7 @@
 // proving-key columns, GraphEvaluator programs, an assignment), builds the proving key's device forms, runs
 // create_proof `reps` times, writes the last proof to <out> and prints one JSON line with the best wall time.
 //   build: hipcc -O2 -std=c++17 -Iinclude tools/create_proof_main.cpp -o tools/create_proof_cpp -Lcircuits_halo2_amd -lsumma_gpu
-//   usage: create_proof_cpp <bundle> <proof out> [reps = 5]
+//   usage: create_proof_cpp <bundle> <proof out> [reps = 5] [blinding key: 64 hex digits (tests; default: the OS entropy source)]
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -61,10 +61,21 @@ struct Reader {
 
 int main(int argc, char** argv) {
   if (argc < 3) {
-    std::fprintf(stderr, "usage: %s <bundle> <proof out> [reps]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s <bundle> <proof out> [reps] [blinding key, 64 hex digits]\n", argv[0]);
     return 2;
   }
   const int reps = argc > 3 ? std::atoi(argv[3]) : 5;
+  uint8_t blinding_key[32];
+  Options opt;
+  if (argc > 4) {
+    const std::string hex(argv[4]);
+    if (hex.size() != 64 || hex.find_first_not_of("0123456789abcdefABCDEF") != std::string::npos) {
+      std::fprintf(stderr, "%s: the blinding key is 64 hex digits\n", argv[0]);
+      return 2;
+    }
+    for (int i = 0; i < 32; i++) blinding_key[i] = (uint8_t)std::stoul(hex.substr(2 * i, 2), nullptr, 16);
+    opt.blinding_key = blinding_key;
+  }
   // the prover issues independent chains on side streams; with HIP's default of 4 hardware queues they end up sharing
   // a queue with the main stream (measured: the phase-1 transforms serialised with the commitments) -- ask for more
   // before the runtime initialises
@@ -122,13 +133,13 @@ int main(int argc, char** argv) {
     for (int r = 0; r < reps + 1; r++) {   // the first run warms work spaces, plans and the program cache
       hk(hipDeviceSynchronize(), "sync");
       t0 = clk::now();
-      proof = create_proof(pk, advice, instances);
+      proof = create_proof(pk, advice, instances, nullptr, opt);
       const double ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
       if (r) best = std::min(best, ms);
       if (std::getenv("SG_PROVER_VERBOSE")) std::fprintf(stderr, "run %d: %.3f ms\n", r, ms);
     }
     Timings tm;
-    create_proof(pk, advice, instances, &tm);
+    create_proof(pk, advice, instances, &tm, opt);
     std::ofstream out(argv[2], std::ios::binary);
     out.write(reinterpret_cast<const char*>(proof.data()), (std::streamsize)proof.size());
     std::printf("{\"k\": %u, \"driver\": \"c++\", \"create_proof_ms\": %.3f, \"keygen_transforms_ms\": %.3f, \"proof_bytes\": %zu", k,
