@@ -288,6 +288,17 @@ def full_verifier(params: ParamsKZG, vk: VerifyingKey, proof: bytes, public_inpu
     return V.verify_proof(params, vk, proof, [int(v) for v in public_inputs[0]], flavour="blake2b")
 
 
+def full_verifier_batch(params: ParamsKZG, vk: VerifyingKey, proofs, public_inputs_list, entropy: bytes | None = None) -> list:
+    """`full_verifier` for many proofs under one key, folded into one pairing check (halo2's `BatchVerifier`; verifier.verify_batch):
+    entry i is what full_verifier answers for proof i alone"""
+    from . import verifier as V
+    ok = [len(pi) == 1 for pi in public_inputs_list]
+    verdicts = V.verify_batch(params, vk, [bytes(p) if good else b"" for p, good in zip(proofs, ok)],
+                              [[int(v) for v in pi[0]] if good else [] for pi, good in zip(public_inputs_list, ok)],
+                              flavour="blake2b", entropy=entropy)
+    return [bool(v and good) for v, good in zip(verdicts, ok)]
+
+
 def create_proof_checked(params: ParamsKZG, pk, circuit: MstInclusionCircuit, instances) -> bytes:
     """[REF utils.rs:162-196]  the proof under the Keccak transcript of the Solidity verifier, verified right away"""
     from . import verifier as V

@@ -80,6 +80,55 @@ def best_multiexp_batch(pairs):
     return [out[64 * i:64 * i + 64].copy() for i in range(count)]
 
 
+class MultiexpMany:
+    """Many small MSMs in ONE launch, kept on the device, and sums over ranges of them (C ABI: sg_msm_g1_many_*).
+    jobs: [(coeffs, bases), ...] host buffers as best_multiexp takes them, at most 64 points each (an empty job is the identity).
+
+        with MultiexpMany(jobs) as many:
+            whole, first = many.sums([(0, len(jobs)), (0, 1)])     # 64-byte affine points; at most 8 ranges per call
+    """
+
+    def __init__(self, jobs):
+        first, s_all, b_all = [0], [], []
+        for s, b in jobs:
+            s, b = ffi.u8(s), ffi.u8(b)
+            if s.size % 32 or b.size != 64 * (s.size // 32):
+                raise ValueError("MultiexpMany: coeffs.len() != bases.len()")
+            first.append(first[-1] + s.size // 32)
+            s_all.append(s)
+            b_all.append(b)
+        cat = lambda parts: np.concatenate(parts) if first[-1] else np.zeros(1, dtype=np.uint8)
+        self.jobs = len(first) - 1
+        self._handle = None
+        handle = C.c_uint64(0)
+        ffi.check(ffi.lib().sg_msm_g1_many_begin(ffi.ptr(cat(s_all)), ffi.ptr(cat(b_all)), ffi.ptr(np.array(first, dtype=np.uint32)),
+                                                 C.c_uint32(self.jobs), C.byref(handle)))
+        self._handle = handle.value
+
+    def sums(self, ranges):
+        """[(a, b), ...] -> the sum of jobs a <= i < b for each range, as a list of 64-byte affine points"""
+        if self._handle is None:
+            raise ValueError("MultiexpMany: closed")
+        rg = np.array([int(v) for ab in ranges for v in ab], dtype=np.int64)
+        if rg.size != 2 * len(ranges) or (rg < 0).any() or (rg >= 1 << 32).any():
+            raise ValueError("MultiexpMany: ranges are pairs of job indices")
+        out = np.zeros(max(1, 64 * len(ranges)), dtype=np.uint8)
+        ffi.check(ffi.lib().sg_msm_g1_many_sums(C.c_uint64(self._handle), ffi.ptr(rg.astype(np.uint32)), C.c_uint32(len(ranges)),
+                                                ffi.ptr(out)))
+        return [out[64 * i:64 * i + 64].copy() for i in range(len(ranges))]
+
+    def close(self):
+        if self._handle is not None:
+            handle, self._handle = self._handle, None
+            ffi.check(ffi.lib().sg_msm_g1_many_end(C.c_uint64(handle)))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 def best_fft(a, omega, log_n: int):
     """Forward DFT of 2^log_n Fr values with generator `omega`, natural order in and out.
     Host input: returns a new numpy buffer.  Device tensor: transformed in place (like the

@@ -65,6 +65,11 @@ struct Srs {
   g1_affine_mem* lagrange_prefix = nullptr;   // made with tab[2]
 };
 
+struct ManyJobs {   // behind a handle of sg_msm_g1_many_begin: the window sums of `jobs` small MSMs, on the device
+  uint32_t jobs;
+  uint32_t* S;
+};
+
 struct Context {
   int device = -1;
   hipStream_t stream = nullptr;
@@ -113,6 +118,9 @@ struct Context {
   static constexpr size_t MAIL_BYTES = 4096;
   uint8_t* h_mail = nullptr;
   uint8_t* d_mail = nullptr;
+  // sg_msm_g1_many_sums: the window sums of up to MSM_MANY_MAX_RANGES ranges, mapped the same way (64 KB)
+  uint32_t* h_many = nullptr;
+  uint32_t* d_many = nullptr;
   // sg_lookup_permute_small_async_dev: two work spaces per caller stream; the write pass of one call zeroes the other's
   // histograms for the next call (no memset launches)
   struct LookupWork {
@@ -133,6 +141,7 @@ struct Shared {
   std::mutex mu;
   int device = -1;
   std::map<uint64_t, Srs> srs;
+  std::map<uint64_t, ManyJobs> many;   // live handles of sg_msm_g1_many_begin
   uint64_t next_handle = 1;
   std::atomic<int> param[kMaxParams];   // the value in effect of each row of kParams: written under mu, read anywhere
   Shared();

@@ -728,6 +728,93 @@ int sg_commit(uint64_t srs_handle, int basis, const uint8_t* scalars, size_t n, 
   return SG_OK;
 }
 
+// ------------------------------------------------------------------ many small MSMs in one launch, sums over ranges of them
+int sg_msm_g1_many_begin(const uint8_t* scalars, const uint8_t* bases, const uint32_t* first, uint32_t jobs, uint64_t* handle) {
+  if (!first || !handle) return fail(SG_ERR_INVALID, "sg_msm_g1_many_begin: null argument");
+  if (jobs > MSM_MANY_MAX_JOBS) return fail(SG_ERR_INVALID, "sg_msm_g1_many_begin: more than 2^14 jobs");
+  for (uint32_t i = 0; i < jobs; i++) {
+    if (first[i + 1] < first[i]) return fail(SG_ERR_INVALID, "sg_msm_g1_many_begin: `first` decreases");
+    if (first[i + 1] - first[i] > MSM_TINY_MAX) return fail(SG_ERR_INVALID, "sg_msm_g1_many_begin: a job of more than 64 points");
+  }
+  const size_t n = first[jobs];   // the jobs index scalars / bases from their start
+  if (n > first[0] && (!scalars || !bases)) return fail(SG_ERR_INVALID, "sg_msm_g1_many_begin: null argument");
+  LOCKED_CTX();
+  Context& c = *g_ctx;
+  TRY(upload(c.stage_a, scalars, n > first[0] ? n * 32 : 0, c.stream));
+  TRY(upload(c.stage_b, bases, n > first[0] ? n * 64 : 0, c.stream));
+  uint8_t* d_first = nullptr;
+  CHECK_HIP(scratch_for(c.stream, 10, ((size_t)jobs + 1) * sizeof(uint32_t), &d_first), "sg_msm_g1_many_begin: scratch");
+  CHECK_HIP(hipMemcpyAsync(d_first, first, ((size_t)jobs + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c.stream), "H2D copy");
+  ManyJobs m{jobs, nullptr};
+  const size_t bytes = std::max<size_t>(jobs, 1) * MSM_MANY_JOB_WORDS * sizeof(uint32_t);
+  hipError_t e = hipMalloc(&m.S, bytes);
+  if (e != hipSuccess) {   // out of memory: give the retired blocks back and try once more (DevBuf::reserve)
+    retired_device_memory_collect();
+    e = hipMalloc(&m.S, bytes);
+  }
+  if (e != hipSuccess) return hip_fail("sg_msm_g1_many_begin: window sums", e);
+  e = msm_many_launch(reinterpret_cast<const fp_words*>(c.stage_a.p), reinterpret_cast<const g1_affine_mem*>(c.stage_b.p),
+                      reinterpret_cast<const uint32_t*>(d_first), jobs, m.S, c.stream);
+  // the sums may be asked for from any lane: S is complete (and the staging buffers free again) on return
+  if (e == hipSuccess) e = host_wait_stream(c.stream);
+  if (e != hipSuccess) {
+    (void)hipFree(m.S);
+    return hip_fail("sg_msm_g1_many_begin", e);
+  }
+  std::lock_guard<std::mutex> lk(g_sh.mu);
+  *handle = g_sh.next_handle++;
+  g_sh.many[*handle] = m;
+  return SG_OK;
+}
+int sg_msm_g1_many_sums(uint64_t handle, const uint32_t* ranges, uint32_t count, uint8_t* out_affine) {
+  if (count > MSM_MANY_MAX_RANGES) return fail(SG_ERR_INVALID, "sg_msm_g1_many_sums: more than 8 ranges");
+  if (count && (!ranges || !out_affine)) return fail(SG_ERR_INVALID, "sg_msm_g1_many_sums: null argument");
+  for (uint32_t r = 0; r < count; r++)
+    if (ranges[2 * r] > ranges[2 * r + 1]) return fail(SG_ERR_INVALID, "sg_msm_g1_many_sums: a range that ends before it starts");
+  LOCKED_CTX();
+  ManyJobs m;
+  {
+    std::lock_guard<std::mutex> lk(g_sh.mu);
+    auto it = g_sh.many.find(handle);
+    if (it == g_sh.many.end()) return fail(SG_ERR_INVALID, "sg_msm_g1_many_sums: unknown handle");
+    m = it->second;
+  }
+  ManyRanges rg{};
+  for (uint32_t r = 0; r < count; r++) {
+    if (ranges[2 * r + 1] > m.jobs) return fail(SG_ERR_INVALID, "sg_msm_g1_many_sums: a range beyond the last job");
+    rg.v[2 * r] = ranges[2 * r];
+    rg.v[2 * r + 1] = ranges[2 * r + 1];
+  }
+  if (count == 0) return SG_OK;
+  Context& c = *g_ctx;
+  if (!c.h_many) {
+    CHECK_HIP(hipHostMalloc(reinterpret_cast<void**>(&c.h_many), MSM_MANY_MAX_RANGES * MSM_MANY_JOB_WORDS * sizeof(uint32_t),
+                            hipHostMallocMapped | hipHostMallocCoherent), "sg_msm_g1_many_sums: mapped host memory");
+    CHECK_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&c.d_many), c.h_many, 0), "sg_msm_g1_many_sums: mapped host memory");
+  }
+  // (the buffer is this lane's, and the previous call waited for its kernel: nothing reads it now)
+  CHECK_HIP(msm_many_sum_launch(m.S, rg, count, c.d_many, c.stream), "sg_msm_g1_many_sums");
+  CHECK_HIP(host_wait_stream(c.stream), "sg_msm_g1_many_sums");
+  const WindowPlan wp = make_window_plan(4);
+  for (uint32_t r = 0; r < count; r++) msm_window_sums_to_affine(wp, c.h_many + r * MSM_MANY_JOB_WORDS, out_affine + 64 * (size_t)r);
+  return SG_OK;
+}
+int sg_msm_g1_many_end(uint64_t handle) {
+  LOCKED_CTX();
+  ManyJobs gone;
+  {
+    std::lock_guard<std::mutex> lk(g_sh.mu);
+    auto it = g_sh.many.find(handle);
+    if (it == g_sh.many.end()) return fail(SG_ERR_INVALID, "sg_msm_g1_many_end: unknown handle");
+    gone = it->second;
+    g_sh.many.erase(it);
+  }
+  // freed, not retired (as sg_srs_free does): a verifier that runs for days would otherwise pile up 16 KB per proof; begin and every
+  // sums call waited for their kernels, so nothing reads S now
+  (void)hipFree(gone.S);
+  return SG_OK;
+}
+
 int sg_msm_launch_log(uint32_t* out_words, size_t cap_records, size_t* n_records) {
   if (!n_records || (cap_records && !out_words)) return fail(SG_ERR_INVALID, "sg_msm_launch_log: bad argument");
   static_assert(sizeof(AccLaunchRecord) == 8 * sizeof(uint32_t), "record layout is part of the ABI");

@@ -1,5 +1,6 @@
 // Host-side interface of the MSM engine (msm.hip; its decisions: msm_plan.h; its kernels: msm_sort.cuh, msm_accumulate.cuh,
-// msm_reduce.cuh).  The one-launch tiny MSM is in msm_tiny.hip, the set-up time G1 operations in g1_ops.h.
+// msm_reduce.cuh).  The one-launch tiny MSM is in msm_tiny.hip, many of them in one launch in msm_many.hip, the set-up time G1
+// operations in g1_ops.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -19,6 +20,13 @@
 namespace sg {
 
 static constexpr uint32_t MSM_TINY_MAX = 64;   // MSMs of at most this many points run as ONE launch (MsmEngine::run_tiny)
+
+// many MSMs of at most MSM_TINY_MAX points in one launch (msm_many.hip): S holds 64 window sums of 32 words per job
+static constexpr uint32_t MSM_MANY_WINDOWS = 64, MSM_MANY_MAX_JOBS = 1u << 14, MSM_MANY_MAX_RANGES = 8;
+static constexpr size_t MSM_MANY_JOB_WORDS = (size_t)MSM_MANY_WINDOWS * 32;
+struct ManyRanges {   // [v[2 r], v[2 r + 1]): the jobs of range r (kernel argument)
+  uint32_t v[2 * MSM_MANY_MAX_RANGES];
+};
 
 struct MsmTimings {
   float digits_ms = 0, sort_ms = 0, accumulate_ms = 0, reduce_ms = 0, total_ms = 0;
@@ -157,6 +165,15 @@ class MsmEngine {
   uint8_t* h_tiny_ = nullptr;    // run_tiny: scalars, points (read by the kernel) and the window sums (written by it), mapped
   uint8_t* d_tiny_ = nullptr;
 };
+
+// the host tail of the one-launch kernels: W window sums (32 canonical words each) -> the affine point (msm_tiny.hip)
+void msm_window_sums_to_affine(const WindowPlan& wp, const uint32_t* h_sums, uint8_t out_affine[64]);
+// msm_many.hip.  d_first: jobs + 1 offsets into d_scalars / d_bases, no job above MSM_TINY_MAX points; d_S: jobs x
+// MSM_MANY_JOB_WORDS words.  The sums of `count` ranges of jobs go to d_out (count x MSM_MANY_JOB_WORDS words; the device address of
+// mapped host memory), one host tail each.
+hipError_t msm_many_launch(const fp_words* d_scalars, const g1_affine_mem* d_bases, const uint32_t* d_first, uint32_t jobs,
+                           uint32_t* d_S, hipStream_t stream);
+hipError_t msm_many_sum_launch(const uint32_t* d_S, const ManyRanges& ranges, uint32_t count, uint32_t* d_out, hipStream_t stream);
 
 // one msm_accumulate launch as the engine issued it (parameter "msm.acc_log"; sg_msm_launch_log)
 struct AccLaunchRecord {

@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "host_curve.h"
+#include "msm_tiny.cuh"
 
 namespace sg {
 SG_DEFINE_SIDE_PRIO_SETTER(msm_tiny_set_side_prio)
@@ -24,50 +25,12 @@ __global__ void __launch_bounds__(64) msm_tiny_kernel(const fp_words* __restrict
   __shared__ int s_dig[MSM_TINY_MAX];
   __shared__ uint32_t s_pt[MSM_TINY_MAX][16];
   __shared__ xyzz29_mem s_x[8];
-  const uint32_t w = blockIdx.x, t = threadIdx.x, W = wp.W;
+  const uint32_t w = blockIdx.x, t = threadIdx.x;
   if (t < n) {
-    words8 s;
-    {
-      f29 k = f29_zero();   // canonical scalar = s~ * 2^5 * 2^-261 (msm_digits)
-      k.l[0] = 32;
-      f29_to_words(f29_cond_sub_p<Fr29>(f29_mul<Fr29>(f29_load_r256<Fr29>(scalars + t), k)), s.l);
-    }
     uint32_t off = 0;
-    {
-      // s += K = sum_{j < W-1} 2^(o_j + w_j - 1): every window's digit becomes independent of its neighbours
-      uint32_t kk[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      uint32_t o = 0;
-      for (uint32_t j = 0; j + 1 < W; j++) {
-        const uint32_t bit = o + wp.width[j] - 1;
-        const uint32_t m = 1u << (bit & 31), q = bit >> 5;
-#pragma unroll
-        for (int i = 0; i < 8; i++) kk[i] |= (q == (uint32_t)i) ? m : 0u;
-        if (j < w) off += wp.width[j];
-        o += wp.width[j];
-      }
-      uint32_t carry = 0;
-#pragma unroll
-      for (int q = 0; q < 8; q++) {
-        const uint64_t v = (uint64_t)s.l[q] + kk[q] + carry;
-        s.l[q] = (uint32_t)v;
-        carry = (uint32_t)(v >> 32);
-      }
-    }
-    const uint32_t width = wp.width[w], q = off >> 5, r = off & 31;
-    uint32_t lo = 0, hi = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-      lo = (q == (uint32_t)i) ? s.l[i] : lo;
-      hi = (q + 1 == (uint32_t)i) ? s.l[i] : hi;
-    }
-    const uint32_t v = (uint32_t)((((uint64_t)hi << 32) | lo) >> r) & ((1u << width) - 1);
-    s_dig[t] = (w + 1 < W) ? (int)v - (int)(1u << (width - 1)) : (int)v;
-    const uint4* src = bases[t].q;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const uint4 x = src[i];
-      s_pt[t][4 * i] = x.x; s_pt[t][4 * i + 1] = x.y; s_pt[t][4 * i + 2] = x.z; s_pt[t][4 * i + 3] = x.w;
-    }
+    for (uint32_t j = 0; j < w; j++) off += wp.width[j];
+    s_dig[t] = msm_tiny_digit(msm_tiny_scalar(scalars + t, wp), w, off, wp);
+    msm_tiny_point_to_lds(bases + t, s_pt[t]);
   }
   __syncthreads();
   xyzz29 acc = xyzz29_identity();
@@ -124,8 +87,14 @@ hipError_t MsmEngine::run_tiny(const uint8_t* h_scalars, const uint8_t* h_bases,
   SG_TRY(hipGetLastError());
   SG_TRY(hipEventRecord(ev_tiny_, stream));
   SG_TRY(host_wait_event(ev_tiny_));
+  msm_window_sums_to_affine(wp, h_out, out_affine);
+  return hipSuccess;
+}
+
+// The host tail of the one-launch kernels: a job's window sums (W x 32 canonical words: X, Y, ZZ, ZZZ) at their bit offsets, one
+// double-and-add sweep from the top bit (as finish() does), affine normalisation.
+void msm_window_sums_to_affine(const WindowPlan& wp, const uint32_t* h_out, uint8_t out_affine[64]) {
   using namespace host;
-  // window sums at their bit offsets, one double-and-add sweep from the top bit (as finish() does)
   int head[255], next[64];
   for (auto& h : head) h = -1;
   uint32_t o = 0, top = 0;
@@ -148,7 +117,6 @@ hipError_t MsmEngine::run_tiny(const uint8_t* h_scalars, const uint8_t* h_bases,
     }
   }
   jac_to_affine_bytes(total, out_affine);
-  return hipSuccess;
 }
 
 }  // namespace sg

@@ -19,6 +19,7 @@ static __device__ __forceinline__ void side_kernel_prio() {
 }
 hipError_t msm_set_side_prio(uint32_t on);
 hipError_t msm_tiny_set_side_prio(uint32_t on);
+hipError_t msm_many_set_side_prio(uint32_t on);
 hipError_t ntt_set_side_prio(uint32_t on);
 hipError_t poly_set_side_prio(uint32_t on);
 hipError_t quotient_set_side_prio(uint32_t on);

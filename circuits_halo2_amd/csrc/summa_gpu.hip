@@ -122,6 +122,7 @@ constexpr int kNoLimit = 0x7fffffff;
 int set_side_prio(int on) {
   hipError_t e = msm_set_side_prio(on);
   if (e == hipSuccess) e = msm_tiny_set_side_prio(on);
+  if (e == hipSuccess) e = msm_many_set_side_prio(on);
   if (e == hipSuccess) e = ntt_set_side_prio(on);
   if (e == hipSuccess) e = poly_set_side_prio(on);
   if (e == hipSuccess) e = quotient_set_side_prio(on);
@@ -334,6 +335,7 @@ void destroy_context(Context* c) {
   for (auto& kv : c->stream_scratch) kv.second.release();
   for (auto& kv : c->lookup_work) kv.second.buf.release();
   if (c->h_mail) (void)hipHostFree(c->h_mail);
+  if (c->h_many) (void)hipHostFree(c->h_many);
   if (c->d_consts) (void)hipFree(c->d_consts);
   c->stream = nullptr;   // one of g_lane_main: destroyed with the others at sg_shutdown
   delete c;
@@ -594,6 +596,8 @@ void sg_shutdown(void) {
         if (t.table) (void)hipFree(t.table);
     }
     g_sh.srs.clear();
+    for (auto& kv : g_sh.many) (void)hipFree(kv.second.S);
+    g_sh.many.clear();
     g_sh.device = -1;
     retired_device_memory_collect();
     summa::prover::release_orphans();   // what the prover sessions of ended threads left behind

@@ -9,19 +9,27 @@
 // the two-pairing check (sg_pairing_check):
 //     e( sum_i c_i C_i - r G - Z_{S_0}(mu) W + mu W', [1]_2 ) * e( -W', [s]_2 ) == 1
 // with the scaling by 1 / Z_{T \ S_0}(mu) of the reference's generated verifier [REF contracts/src/InclusionVerifier.sol:1025-1402].
+//
+// sv_verify_batch (include/summa_verifier.h) folds N such checks into one with random multipliers (verify_batch_plan.h): the host
+// part per proof as above, the group side as ONE launch of 2 N small MSMs kept on the device (sg_msm_g1_many_*) and one pairing
+// check per range of proofs asked about -- one for a batch without a bad proof.
 #include "../../include/summa_prover.h"
+#include "../../include/summa_verifier.h"
 
 #include <map>
 #include <tuple>
 
 #include "../../include/summa_circuit.hpp"
 #include "host_curve.h"
+#include "msm.h"
+#include "verify_batch_plan.h"
 
 using namespace summa::prover;
 using sg::host::Fq;
 
 namespace {
 thread_local char g_sv_err[256] = "";
+thread_local char g_svb_err[256] = "";   // sv_last_error
 
 struct Reject : std::runtime_error {   // the proof (not the call) is at fault: verification answers "no"
   using std::runtime_error::runtime_error;
@@ -216,10 +224,26 @@ struct VerifyingKeyView {
   const uint8_t *g2, *s_g2;           // 128 B each
 };
 
-bool verify(const VerifyingKeyView& vk, const uint8_t* proof, size_t len, const std::vector<Fr>& instances, bool evm) {
+// what a proof contributes to the final check: the points and scalars of its left-hand side, and W'
+struct Terms {
+  std::vector<uint8_t> points, scalars;   // 64 B / 32 B each, as the C ABI takes them
+  Point w2;
+  size_t count() const { return scalars.size() / 32; }
+};
+Point negated(const Point& p) {
+  Fq y;
+  std::memcpy(y.v, p.b + 32, 32);
+  const Fq neg = Fq::zero() - y;
+  Point out = p;
+  std::memcpy(out.b + 32, neg.v, 32);
+  return out;
+}
+
+// the host part: replays the transcript and returns the proof's terms; throws Reject where the proof is at fault
+Terms proof_terms(const VerifyingKeyView& vk, const uint8_t* proof, size_t len, const std::vector<Fr>& instances, bool evm) {
   const uint32_t k = vk.k;
   const size_t n = (size_t)1 << k;
-  if (instances.size() > n - (BLINDING + 1)) return false;      // halo2: Error::InstanceTooLarge
+  if (instances.size() > n - (BLINDING + 1)) throw Reject("too many instances");      // halo2: Error::InstanceTooLarge
   Reader rd{proof, len, 0, evm, {}, {}};
   rd.common_scalar(Fr::from_be_bytes_reduced(vk.digest_be));
   for (const Fr& v : instances) rd.common_scalar(v);
@@ -244,7 +268,7 @@ bool verify(const VerifyingKeyView& vk, const uint8_t* proof, size_t len, const 
   const Point w = rd.read_point();
   const Fr mu = rd.squeeze();
   const Point w2 = rd.read_point();
-  if (rd.pos != len) return false;
+  if (rd.pos != len) throw Reject("proof too long");
 
   // Lagrange evaluations: l_0, l_last, l_blind (the five blinding rows), the instance column at x
   uint8_t omega_b[32], n_inv_b[32];
@@ -314,10 +338,11 @@ bool verify(const VerifyingKeyView& vk, const uint8_t* proof, size_t len, const 
     }
     nu_pow = nu_pow * nu;
   }
-  std::vector<uint8_t> points, scalars;
+  Terms terms;
+  terms.w2 = w2;
   auto push = [&](const Point& p, const Fr& c) {
-    points.insert(points.end(), p.b, p.b + 64);
-    scalars.insert(scalars.end(), c.bytes(), c.bytes() + 32);
+    terms.points.insert(terms.points.end(), p.b, p.b + 64);
+    terms.scalars.insert(terms.scalars.end(), c.bytes(), c.bytes() + 32);
   };
   for (auto& kv : coeff) {
     if (kv.first.kind == H_) {   // h(X) = sum_j x^(n j) h_j(X)
@@ -334,16 +359,14 @@ bool verify(const VerifyingKeyView& vk, const uint8_t* proof, size_t len, const 
   push(make_point(gx, gy), -r_eval);
   push(w, -z_s0);
   push(w2, mu);
+  return terms;
+}
+
+// e(lhs, [1]_2) e(rhs, [s]_2) == 1; false where a point is at fault
+bool pairing_holds(const VerifyingKeyView& vk, const uint8_t lhs[64], const uint8_t rhs[64]) {
   uint8_t g1[128], g2[256];
-  const size_t count = scalars.size() / 32;
-  if (sg_msm_g1(scalars.data(), points.data(), count, g1) != SG_OK) throw std::runtime_error(std::string("verifier: msm: ") + sg_last_error());
-  {   // -W'
-    Fq w2y;
-    std::memcpy(w2y.v, w2.b + 32, 32);
-    const Fq neg = Fq::zero() - w2y;
-    std::memcpy(g1 + 64, w2.b, 32);
-    std::memcpy(g1 + 96, neg.v, 32);
-  }
+  std::memcpy(g1, lhs, 64);
+  std::memcpy(g1 + 64, rhs, 64);
   std::memcpy(g2, vk.g2, 128);
   std::memcpy(g2 + 128, vk.s_g2, 128);
   int ok = 0;
@@ -351,6 +374,23 @@ bool verify(const VerifyingKeyView& vk, const uint8_t* proof, size_t len, const 
   if (rc == SG_ERR_INVALID) return false;   // a coordinate not reduced / a point off the curve: the data's fault
   if (rc != SG_OK) throw std::runtime_error(std::string("verifier: pairing: ") + sg_last_error());
   return ok == 1;
+}
+
+// the group part of one proof: one MSM, one two-pairing check
+bool check_terms(const VerifyingKeyView& vk, const Terms& t) {
+  uint8_t lhs[64];
+  if (sg_msm_g1(t.scalars.data(), t.points.data(), t.count(), lhs) != SG_OK) throw std::runtime_error(std::string("verifier: msm: ") + sg_last_error());
+  return pairing_holds(vk, lhs, negated(t.w2).b);
+}
+
+// the instance column as the C ABI passes it; false where a word is not a field element
+bool read_instances(const uint8_t* instances, uint32_t n_instances, std::vector<Fr>* out) {
+  out->resize(n_instances);
+  for (uint32_t i = 0; i < n_instances; i++) {
+    std::memcpy((*out)[i].l, instances + 32 * (size_t)i, 32);
+    if (Fr::geq_p((*out)[i].l)) return false;
+  }
+  return true;
 }
 }  // namespace
 
@@ -373,13 +413,10 @@ int sp_verify_proof(uint32_t k, uint32_t n_currencies, const uint8_t vk_digest_b
   *accepted = 0;
   (void)sg_bind_thread();
   try {
-    std::vector<Fr> inst(n_instances);
-    for (uint32_t i = 0; i < n_instances; i++) {
-      std::memcpy(inst[i].l, instances + 32 * (size_t)i, 32);
-      if (Fr::geq_p(inst[i].l)) return SG_OK;          // not a field element: rejected
-    }
+    std::vector<Fr> inst;
+    if (!read_instances(instances, n_instances, &inst)) return SG_OK;          // not a field element: rejected
     const VerifyingKeyView vk{k, n_currencies, vk_digest_be, fixed_comms, permutation_comms, g2, s_g2};
-    *accepted = verify(vk, proof, proof_len, inst, transcript == SP_TRANSCRIPT_EVM) ? 1 : 0;
+    *accepted = check_terms(vk, proof_terms(vk, proof, proof_len, inst, transcript == SP_TRANSCRIPT_EVM)) ? 1 : 0;
     return SG_OK;
   } catch (const Reject&) {
     return SG_OK;                                         // *accepted stays 0
@@ -390,6 +427,122 @@ int sp_verify_proof(uint32_t k, uint32_t n_currencies, const uint8_t vk_digest_b
     std::snprintf(g_sv_err, sizeof g_sv_err, "%s", e.what());
     return SG_ERR_HIP;
   }
+}
+
+const char* sv_last_error(void) { return g_svb_err; }
+
+int sv_verify_batch(uint32_t k, uint32_t n_currencies, const uint8_t vk_digest_be[32], const uint8_t* fixed_comms,
+                    const uint8_t* permutation_comms, const uint8_t g2[128], const uint8_t s_g2[128],
+                    const uint8_t* const* proofs, const size_t* proof_lens, const uint8_t* const* instances,
+                    const uint32_t* n_instances, uint32_t n_proofs, int transcript, const uint8_t entropy[32],
+                    uint8_t* accepted, uint32_t* pairings) {
+  namespace vb = sg::verify_batch;
+  auto invalid = [](const char* what) {
+    std::snprintf(g_svb_err, sizeof g_svb_err, "sv_verify_batch: %s", what);
+    return (int)SG_ERR_INVALID;
+  };
+  if (n_proofs == 0) return SG_OK;
+  if (n_proofs > vb::MAX_PROOFS) return invalid("more than 8192 proofs");
+  if (!vk_digest_be || !fixed_comms || !permutation_comms || !g2 || !s_g2 || !proofs || !proof_lens || !instances || !n_instances ||
+      !accepted || k < 4 || k > 25 || n_currencies == 0 || n_currencies > 64)
+    return invalid("bad argument");
+  if (transcript != SP_TRANSCRIPT_EVM && transcript != SP_TRANSCRIPT_BLAKE2B) return invalid("unknown transcript");
+  for (uint32_t i = 0; i < n_proofs; i++)
+    if ((proof_lens[i] && !proofs[i]) || (n_instances[i] && !instances[i])) return invalid("bad argument");
+  std::memset(accepted, 0, n_proofs);
+  if (pairings) *pairings = 0;
+  if (sg_device() < 0 && sg_device_count() <= 0) {   // (asked first: the host part's domain constants would fail less clearly)
+    std::snprintf(g_svb_err, sizeof g_svb_err, "sv_verify_batch: no HIP device visible");
+    return SG_ERR_NO_DEVICE;
+  }
+  (void)sg_bind_thread();
+  uint64_t handle = 0;
+  bool open = false;
+  int rc = SG_OK;
+  try {
+    const VerifyingKeyView vk{k, n_currencies, vk_digest_be, fixed_comms, permutation_comms, g2, s_g2};
+    // the host part, proof by proof: a proof it rejects keeps verdict 0 and two empty jobs
+    std::vector<Terms> terms(n_proofs);
+    std::vector<uint32_t> live;
+    std::vector<vb::ProofView> views(n_proofs);
+    for (uint32_t i = 0; i < n_proofs; i++) {
+      views[i] = vb::ProofView{proofs[i], proof_lens[i], instances[i], n_instances[i]};
+      std::vector<Fr> inst;
+      if (!read_instances(instances[i], n_instances[i], &inst)) continue;
+      try {
+        terms[i] = proof_terms(vk, proofs[i], proof_lens[i], inst, transcript == SP_TRANSCRIPT_EVM);
+      } catch (const Reject&) {
+        continue;
+      }
+      if (terms[i].count() > sg::MSM_TINY_MAX) return invalid("a proof of more than 64 terms");
+      live.push_back(i);
+    }
+    // jobs 0 .. N-1: proof i's terms with scalars r_i c; jobs N .. 2N-1: r_i (-W'_i)
+    const vb::Digest sd = vb::seed(vk_digest_be, views.data(), n_proofs, entropy);
+    std::vector<uint8_t> scalars, bases;
+    std::vector<uint32_t> first(2 * (size_t)n_proofs + 1, 0);
+    std::vector<Fr> r(n_proofs);
+    for (uint32_t i = 0; i < n_proofs; i++) {
+      const auto m = vb::multiplier(sd, i);
+      uint64_t c[4] = {0, 0, 0, 0};
+      std::memcpy(c, m.data(), 16);
+      r[i] = Fr::from_canonical_limbs(c);
+      for (size_t j = 0; j < terms[i].count(); j++) {
+        Fr s;
+        std::memcpy(s.l, terms[i].scalars.data() + 32 * j, 32);
+        s = s * r[i];
+        scalars.insert(scalars.end(), s.bytes(), s.bytes() + 32);
+      }
+      bases.insert(bases.end(), terms[i].points.begin(), terms[i].points.end());
+      first[i + 1] = (uint32_t)(scalars.size() / 32);
+    }
+    for (uint32_t i = 0; i < n_proofs; i++) {
+      if (terms[i].count()) {
+        scalars.insert(scalars.end(), r[i].bytes(), r[i].bytes() + 32);
+        const Point neg = negated(terms[i].w2);
+        bases.insert(bases.end(), neg.b, neg.b + 64);
+      }
+      first[n_proofs + i + 1] = (uint32_t)(scalars.size() / 32);
+    }
+    rc = sg_msm_g1_many_begin(scalars.data(), bases.data(), first.data(), 2 * n_proofs, &handle);
+    if (rc != SG_OK) {
+      std::snprintf(g_svb_err, sizeof g_svb_err, "sv_verify_batch: %s", sg_last_error());
+      return rc;
+    }
+    open = true;
+    // one range, or the two halves of a rejected one: their left and right sides in ONE sums call; the second half's pairing only if
+    // the first half was rejected (verify_batch_plan.h)
+    auto accepts = [&](const std::vector<vb::Range>& ranges) {
+      uint32_t rg[8];
+      uint8_t sums[4 * 64];
+      const uint32_t m = (uint32_t)ranges.size();
+      for (uint32_t q = 0; q < m; q++) {
+        rg[2 * q] = ranges[q].a;
+        rg[2 * q + 1] = ranges[q].b;
+        rg[2 * (m + q)] = n_proofs + ranges[q].a;
+        rg[2 * (m + q) + 1] = n_proofs + ranges[q].b;
+      }
+      if (sg_msm_g1_many_sums(handle, rg, 2 * m, sums) != SG_OK) throw std::runtime_error(std::string("verifier: sums: ") + sg_last_error());
+      std::vector<uint8_t> verdicts(m, 0);
+      for (uint32_t q = 0; q < m; q++) {
+        if (q == 1 && verdicts[0]) break;
+        verdicts[q] = pairing_holds(vk, sums + 64 * q, sums + 64 * (m + q)) ? 1 : 0;
+      }
+      return verdicts;
+    };
+    const vb::Verdicts out = vb::bisect(live, n_proofs, accepts);
+    std::memcpy(accepted, out.accepted.data(), n_proofs);
+    if (pairings) *pairings = out.checks;
+  } catch (const std::bad_alloc&) {
+    std::snprintf(g_svb_err, sizeof g_svb_err, "out of host memory");
+    rc = SG_ERR_NOMEM;
+  } catch (const std::exception& e) {
+    std::snprintf(g_svb_err, sizeof g_svb_err, "%s", e.what());
+    rc = SG_ERR_HIP;
+  }
+  if (open) (void)sg_msm_g1_many_end(handle);
+  if (rc != SG_OK) std::memset(accepted, 0, n_proofs);
+  return rc;
 }
 
 }  // extern "C"

@@ -164,18 +164,7 @@ def verify_proof_native(params, vk, proof: bytes, instances, flavour: str = "evm
         raise ValueError("flavour: evm or blake2b")
     if any(not 0 <= int(v) < R for v in instances) or len(params.g2) != 128 or len(params.s_g2) != 128:
         return False
-    cached = getattr(vk, "_native_view", None)
-    if cached is None:
-        pts = lambda comms: np.frombuffer(b"".join(_g1_bytes(tuple(c)) for c in comms), dtype=np.uint8).copy()
-        cached = (np.frombuffer(int(vk.transcript_repr).to_bytes(32, "big"), dtype=np.uint8).copy(), pts(vk.fixed_comms),
-                  pts(vk.permutation_comms))
-        try:
-            vk._native_view = cached
-        except AttributeError:
-            pass
-    digest, fixed, perm = cached
-    g2 = np.frombuffer(bytes(params.g2), dtype=np.uint8).copy()
-    s_g2 = np.frombuffer(bytes(params.s_g2), dtype=np.uint8).copy()
+    digest, fixed, perm, g2, s_g2 = _native_key(params, vk)
     raw = np.frombuffer(bytes(proof), dtype=np.uint8).copy() if len(proof) else np.zeros(1, dtype=np.uint8)
     inst = np.frombuffer(b"".join(_fr_bytes(int(v)) for v in instances), dtype=np.uint8).copy() if len(instances) else np.zeros(1, dtype=np.uint8)
     ok = C.c_int(0)
@@ -186,6 +175,62 @@ def verify_proof_native(params, vk, proof: bytes, instances, flavour: str = "evm
     if rc != 0:
         raise ffi.SummaGpuError(rc, L.sp_verify_last_error().decode())
     return ok.value == 1
+
+
+def _native_key(params, vk):
+    """the verifying key as sp_verify_proof / sv_verify_batch take it: (digest, fixed, permutation, g2, s_g2) byte arrays"""
+    cached = getattr(vk, "_native_view", None)
+    if cached is None:
+        pts = lambda comms: np.frombuffer(b"".join(_g1_bytes(tuple(c)) for c in comms), dtype=np.uint8).copy()
+        cached = (np.frombuffer(int(vk.transcript_repr).to_bytes(32, "big"), dtype=np.uint8).copy(), pts(vk.fixed_comms),
+                  pts(vk.permutation_comms))
+        try:
+            vk._native_view = cached
+        except AttributeError:
+            pass
+    return cached + (np.frombuffer(bytes(params.g2), dtype=np.uint8).copy(), np.frombuffer(bytes(params.s_g2), dtype=np.uint8).copy())
+
+
+def verify_batch(params, vk, proofs, instances_list, flavour: str = "evm", entropy: bytes | None = None, stats: dict | None = None):
+    """`verify_proof` for many proofs under one verifying key, folded into ONE pairing check with random multipliers (include/
+    summa_verifier.h: sv_verify_batch; halo2's `BatchVerifier`) -> list[bool], entry i what verify_proof answers for proof i alone.
+    A rejected batch is bisected down to its bad proofs.  entropy: 32 bytes of the caller's randomness (the multipliers are
+    derived from the whole batch and from it); stats, if given, receives {"pairings": pairing checks made}."""
+    if flavour not in ("evm", "blake2b"):
+        raise ValueError("flavour: evm or blake2b")
+    if len(proofs) != len(instances_list):
+        raise ValueError("verify_batch: one instance column per proof")
+    if entropy is not None and len(entropy) != 32:
+        raise ValueError("verify_batch: entropy is 32 bytes")
+    n = len(proofs)
+    if stats is not None:
+        stats["pairings"] = 0
+    if n == 0:
+        return []
+    if len(params.g2) != 128 or len(params.s_g2) != 128:
+        return [False] * n
+    digest, fixed, perm, g2, s_g2 = _native_key(params, vk)
+    # an instance that is no field element has no Montgomery form: such a proof goes in with an unreduced word and is rejected there
+    word = lambda v: _fr_bytes(int(v)) if 0 <= int(v) < R else b"\xff" * 32
+    raws = [np.frombuffer(bytes(p), dtype=np.uint8).copy() if len(p) else np.zeros(1, dtype=np.uint8) for p in proofs]
+    insts = [np.frombuffer(b"".join(word(v) for v in inst), dtype=np.uint8).copy() if len(inst) else np.zeros(1, dtype=np.uint8)
+             for inst in instances_list]
+    p_ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in raws])
+    i_ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in insts])
+    lens = (C.c_size_t * n)(*[len(p) for p in proofs])
+    counts = (C.c_uint32 * n)(*[len(inst) for inst in instances_list])
+    ent = np.frombuffer(bytes(entropy), dtype=np.uint8).copy() if entropy is not None else None
+    accepted = np.zeros(n, dtype=np.uint8)
+    pairings = C.c_uint32(0)
+    L = ffi.verifier_lib()
+    rc = L.sv_verify_batch(C.c_uint32(vk.k), C.c_uint32(vk.n_currencies), ffi.ptr(digest), ffi.ptr(fixed), ffi.ptr(perm), ffi.ptr(g2),
+                           ffi.ptr(s_g2), p_ptrs, lens, i_ptrs, counts, C.c_uint32(n), C.c_int(0 if flavour == "evm" else 1),
+                           ffi.ptr(ent) if ent is not None else None, ffi.ptr(accepted), C.byref(pairings))
+    if rc != 0:
+        raise ffi.SummaGpuError(rc, L.sv_last_error().decode())
+    if stats is not None:
+        stats["pairings"] = pairings.value
+    return [bool(v) for v in accepted]
 
 
 def verify_proof(params, vk, proof: bytes, instances, flavour: str = "evm", driver: str | None = None) -> bool:
@@ -211,6 +256,24 @@ def verify_proof(params, vk, proof: bytes, instances, flavour: str = "evm", driv
 
 
 def _verify(params, vk, proof: bytes, instances, flavour: str) -> bool:
+    terms = proof_terms(vk, proof, instances, flavour)
+    if terms is None:
+        return False
+    points, scalars, w2 = terms
+    lhs = best_multiexp(np.frombuffer(b"".join(_fr_bytes(s) for s in scalars), dtype=np.uint8),
+                        np.frombuffer(b"".join(_g1_bytes(p) for p in points), dtype=np.uint8))
+    neg_w2 = _g1_bytes((w2[0], (-w2[1]) % Q))
+    g1 = np.concatenate([lhs, np.frombuffer(neg_w2, dtype=np.uint8)])
+    g2 = np.frombuffer(bytes(params.g2) + bytes(params.s_g2), dtype=np.uint8).copy()
+    ok = C.c_int(0)
+    ffi.check(ffi.lib().sg_pairing_check(ffi.ptr(g1), ffi.ptr(g2), C.c_size_t(2), C.byref(ok)))
+    return ok.value == 1
+
+
+def proof_terms(vk, proof: bytes, instances, flavour: str):
+    """the host part: replays the transcript and returns what the proof contributes to the final check -- (points, scalars, W') with
+    the left-hand side sum_i scalars[i] points[i] (integers; points as (x, y)) -- or None where the proof's bytes are at fault;
+    ValueError / ZeroDivisionError as `verify_proof` catches them"""
     k = vk.k
     try:
         rd = _Reader(bytes(proof), flavour)
@@ -235,9 +298,9 @@ def _verify(params, vk, proof: bytes, instances, flavour: str) -> bool:
         mu = tr.squeeze_challenge()
         w2 = rd.read_point()
         if rd.pos != len(rd.proof):
-            return False
+            return None
     except ValueError:
-        return False
+        return None
     x = ch["x"]
     lag = _lagrange(x, k, [int(v) for v in instances])
     h_eval = _expected_h_eval(evals, ch, lag, vk.n_currencies)
@@ -296,11 +359,4 @@ def _verify(params, vk, proof: bytes, instances, flavour: str) -> bool:
             scalars.append(c)
     points += [(1, 2), w, w2]
     scalars += [(-r_eval) % R, (-z_s0) % R, mu]
-    lhs = best_multiexp(np.frombuffer(b"".join(_fr_bytes(s) for s in scalars), dtype=np.uint8),
-                        np.frombuffer(b"".join(_g1_bytes(p) for p in points), dtype=np.uint8))
-    neg_w2 = _g1_bytes((w2[0], (-w2[1]) % Q))
-    g1 = np.concatenate([lhs, np.frombuffer(neg_w2, dtype=np.uint8)])
-    g2 = np.frombuffer(bytes(params.g2) + bytes(params.s_g2), dtype=np.uint8).copy()
-    ok = C.c_int(0)
-    ffi.check(ffi.lib().sg_pairing_check(ffi.ptr(g1), ffi.ptr(g2), C.c_size_t(2), C.byref(ok)))
-    return ok.value == 1
+    return points, scalars, w2

@@ -119,6 +119,21 @@ int sg_msm_g1_batch_dev(const void* const* d_scalars, const void* const* d_bases
  * per-GPU partial results of a point-sharded MSM; EC addition is not an RCCL reduction op). */
 int sg_g1_sum_affine(const uint8_t* points, size_t n, uint8_t out_affine[64]);
 
+/* Many small MSMs in ONE launch, kept on the device, and sums over ranges of them -- the group side of a batch verifier
+ * (include/summa_verifier.h): N proofs' left-hand sides are N MSMs of ~37 points, of which only sums over ranges of proofs are
+ * ever wanted (the whole batch; its halves when it is rejected, down to the bad proofs).
+ * sg_msm_g1_many_begin: host pointers.  Job i is the MSM of scalars / bases [first[i], first[i + 1]) (`first`: jobs + 1 entries,
+ *   non-decreasing; at most 64 points per job; jobs <= 2^14 -- 8 KB of device memory per job, 128 MB at most); a job of no
+ *   points is the identity.  Uploads, runs the launch, waits, and returns a handle.
+ * sg_msm_g1_many_sums: out_affine[64 r ..] = sum of MSM_i over a_r <= i < b_r for `count` <= 8 ranges (a_r <= b_r <= jobs; an
+ *   empty range is the identity: 64 zero bytes), one launch and one host wait for all of them.  Nothing is recomputed: any
+ *   number of calls may follow one begin, from any thread.
+ * sg_msm_g1_many_end: frees the handle (waits for the device, as sg_srs_free does); not while a call on the handle is in
+ *   flight.  Handles still live at sg_shutdown are freed there.  An unknown handle is SG_ERR_INVALID. */
+int sg_msm_g1_many_begin(const uint8_t* scalars, const uint8_t* bases, const uint32_t* first, uint32_t jobs, uint64_t* handle);
+int sg_msm_g1_many_sums(uint64_t handle, const uint32_t* ranges, uint32_t count, uint8_t* out_affine);
+int sg_msm_g1_many_end(uint64_t handle);
+
 /* SRS cache: keeps ParamsKZG's g[] / g_lagrange[] resident in HBM across proofs
  * (the reference re-reads the file per Snapshot: backend/src/apis/round.rs:136-145). */
 int sg_srs_upload(uint32_t k, const uint8_t* g, const uint8_t* g_lagrange, uint64_t* handle_out);

@@ -177,6 +177,30 @@ extern "C" {
         accepted: *mut c_int,
     ) -> c_int;
     pub fn sp_verify_last_error() -> *const c_char;
+    // many proofs under one key folded into ONE pairing check (include/summa_verifier.h; halo2's BatchVerifier), and the group side
+    // it runs on: many small MSMs in one launch, kept on the device, sums over ranges of them
+    pub fn sv_verify_batch(
+        k: u32,
+        n_currencies: u32,
+        vk_digest_be: *const u8,
+        fixed_comms: *const u8,
+        permutation_comms: *const u8,
+        g2: *const u8,
+        s_g2: *const u8,
+        proofs: *const *const u8,
+        proof_lens: *const size_t,
+        instances: *const *const u8,
+        n_instances: *const u32,
+        n_proofs: u32,
+        transcript: c_int,
+        entropy: *const u8,
+        accepted: *mut u8,
+        pairings: *mut u32,
+    ) -> c_int;
+    pub fn sv_last_error() -> *const c_char;
+    pub fn sg_msm_g1_many_begin(scalars: *const u8, bases: *const u8, first: *const u32, jobs: u32, handle: *mut u64) -> c_int;
+    pub fn sg_msm_g1_many_sums(handle: u64, ranges: *const u32, count: u32, out_affine: *mut u8) -> c_int;
+    pub fn sg_msm_g1_many_end(handle: u64) -> c_int;
     // a setup that arrives in device memory (RCCL broadcast), proofs in flight from several threads, memory hygiene
     pub fn sg_srs_upload_dev(k: u32, d_g: *const c_void, d_g_lagrange: *const c_void, stream: *mut c_void, handle_out: *mut u64) -> c_int;
     pub fn sg_srs_copy_dev(handle: u64, d_g_out: *mut c_void, d_g_lagrange_out: *mut c_void, stream: *mut c_void) -> c_int;
