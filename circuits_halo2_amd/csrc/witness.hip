@@ -158,7 +158,7 @@ __global__ void __launch_bounds__(128) mst_level_kernel(const fp_words* __restri
 // are what the circuit constrains); the digests they end in are the tree's own nodes.
 __device__ const uint32_t FR_ONE_M[8] = {0x4ffffffbu, 0xac96341cu, 0x9f60cd29u, 0x36fc7695u,
                                          0x7879462eu, 0x666ea36fu, 0x9a07df2fu, 0x0e0a77c1u};   // 2^256 mod r: Montgomery form of 1
-struct WitnessItem { uint32_t kind, col, row, sym, extra; };       // kind 0 cell, 1 range (extra = bytes), 2 hash (extra = first absorb | count << 20 | chip << 28)
+struct WitnessItem { uint32_t kind, col, row, sym, extra; };       // kind 0 cell, 1 range (extra = bytes: bytes + 1 rows), 2 hash (extra = first absorb | count << 20 | chip << 28)
 struct WitnessAbsorb { uint32_t add_row, permute_row, sym; };
 struct WitnessTree {
   const fp_words* users;      // 2^depth username field elements
@@ -223,14 +223,15 @@ __global__ void __launch_bounds__(64) mst_inclusion_witness_kernel(const Witness
     sym_words(tree, it.sym, idx, w);
     fp_words_store(out.col[it.col] + it.row, w);
   } else if (it.kind == 1) {
-    // running sum of the byte decomposition: row i holds value >> 8 i (the value is a balance < 2^(8 bytes))
+    // running sums of the byte decomposition, N_BYTES + 1 of them: row i holds value >> 8 i.  The last one is 0 for a balance
+    // < 2^(8 N_BYTES) and what is left of a larger one (the circuit's copy to the constant 0 then fails, as in the reference)
     sym_words(tree, it.sym, idx, w);
     f29 one_int = f29_zero();
     one_int.l[0] = 1;
     uint32_t v[9];
     f29_to_words(f29_cond_sub_p<P>(f29_mul<P>(f29_words_to_r261<P>(w), one_int)), v);   // the canonical integer
     v[8] = 0;
-    for (uint32_t b = 0; b < it.extra; b++) {
+    for (uint32_t b = 0; b <= it.extra; b++) {
       // integer -> memory (2^256) form: v * 2^517 * 2^-261, canonical
       uint32_t o[8];
       f29_to_words(f29_reduce_with<P>(f29_from_words<0>(v), P::r517), o);

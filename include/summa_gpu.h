@@ -548,7 +548,8 @@ int sg_mst_build_dev(const void* d_usernames, const void* d_leaf_balances, uint3
  * users of a tree built by sg_mst_build_dev: the three advice columns in the reference's own floor plan.  The floor plan
  * is a function of <LEVELS, N_CURRENCIES, N_BYTES> only and arrives as `d_program` (device memory): n_items x 5 u32
  * {kind, column, row, symbol, extra} followed by n_absorbs x 3 u32 {add-input row, permute row, symbol}; kind 0 copies one
- * value, 1 writes the running sum of a byte-wise range check (extra = N_BYTES), 2 lays out a whole Poseidon sponge
+ * value, 1 writes the N_BYTES + 1 running sums value >> 8 i of a byte-wise range check (extra = N_BYTES; the last one is 0
+ * unless the value has more than N_BYTES bytes), 2 lays out a whole Poseidon sponge
  * (initial state, add-input and 37-row permute regions; extra = first absorb | count << 20).  A symbol names a tree
  * node relative to the user's leaf index: bits 0-3 kind (0 username, 1 node hash, 2 node balance, 3 path bit), 4-9
  * level, 10-12 mode (0 path node, 1 sibling, 2 child of the sibling, 3 ordered child of the path's parent), 13-19

@@ -284,18 +284,23 @@ def _tree_value(symbol, idx, users, node_hash, node_bal, nc):
     return node_hash[lv][node] if kind == 1 else node_bal[lv][node][lane]
 
 
-@pytest.mark.parametrize("levels,nc,k,idx", [(4, 2, 11, 5), (3, 1, 10, 6), (5, 3, 12, 17)])
-def test_witness_program_covers_the_reference_assignment_cell_by_cell(levels, nc, k, idx):
+@pytest.mark.parametrize("levels,nc,k,idx,overflow", [(4, 2, 11, 5, False), (3, 1, 10, 6, False), (5, 3, 12, 17, False), (4, 2, 11, 5, True)],
+                         ids=["4-2-11-5", "3-1-10-6", "5-3-12-17", "4-2-11-5-overflow"])
+def test_witness_program_covers_the_reference_assignment_cell_by_cell(levels, nc, k, idx, overflow):
     """mst_inclusion.witness_program (what the device kernel executes) against mst_inclusion.reference_assignment (the
     replay of the reference's synthesize with integers, itself pinned by the reproduced verifying key): every cell the
     program writes holds the value the assignment has there, the sponge regions start from the sponge's initial state,
     absorb the right words and end in the tree's own nodes -- and the cells the program covers are ALL the non-zero
-    cells of the assignment"""
+    cells of the assignment.  A range check holds N_BYTES + 1 running sums, the last one non-zero for a balance of more than
+    N_BYTES bytes (`overflow`: the user's and the sibling's balance out of range, laid out by the lenient assignment, which is
+    what api.MstInclusionCircuit.synthesize uses)"""
     from circuits_halo2_amd import mst_inclusion as M
     rng = random.Random(levels * 100 + nc)
     size = 1 << levels
     users = [rng.randrange(PR.R) for _ in range(size)]
     bals = [[rng.randrange(1 << 40) for _ in range(nc)] for _ in range(size)]
+    if overflow:
+        bals[idx][0], bals[idx ^ 1][nc - 1] = (1 << 64) + 5, 1 << 64
     node_hash = [[PR.poseidon_hash([users[i]] + bals[i]) for i in range(size)]]
     node_bal = [bals]
     for level in range(1, levels + 1):
@@ -313,7 +318,7 @@ def test_witness_program_covers_the_reference_assignment_cell_by_cell(levels, nc
     for level in range(1, levels):
         s = (idx >> level) ^ 1
         pre_mid.append(node_bal[level][s] + [node_hash[level - 1][2 * s], node_hash[level - 1][2 * s + 1]])
-    asg = M.reference_assignment(k, users[idx], bals[idx], bits, pre_leaf, pre_mid)
+    asg = M.reference_assignment(k, users[idx], bals[idx], bits, pre_leaf, pre_mid, lenient=overflow)
     adv = asg["advice"]
     prog, n_items, n_absorbs, inst_syms, rows_used = M.witness_program(k, levels, nc, 8)
     assert rows_used == asg["rows_used"]
@@ -323,6 +328,7 @@ def test_witness_program_covers_the_reference_assignment_cell_by_cell(levels, nc
     val = lambda s: _tree_value(s, idx, users, node_hash, node_bal, nc) % PR.R
     assert [val(s) for s in inst_syms] == asg["instances"] == [node_hash[0][idx], node_hash[levels][0]] + node_bal[levels][0]
     covered = set()
+    last_sums = []
     seen_hash = False
     for kind, col, row, s, extra in items:
         if kind == 0:
@@ -330,10 +336,10 @@ def test_witness_program_covers_the_reference_assignment_cell_by_cell(levels, nc
             assert adv[col][row] == val(s), (col, row)
             covered.add((col, row))
         elif kind == 1:
-            for b in range(extra):
+            for b in range(extra + 1):
                 assert adv[0][row + b] == val(s) >> (8 * b)
                 covered.add((0, row + b))
-            assert adv[0][row + extra] == 0
+            last_sums.append(adv[0][row + extra])
         else:
             first, count = extra & 0xFFFFF, (extra >> 20) & 255
             assert (adv[0][row], adv[1][row]) == (0, (count << 64) % PR.R)
@@ -353,6 +359,7 @@ def test_witness_program_covers_the_reference_assignment_cell_by_cell(levels, nc
             assert state0 in {h for lv in node_hash for h in lv}
     nonzero = {(c, r) for c in range(3) for r in range(1 << k) if adv[c][r]}
     assert nonzero <= covered
+    assert sorted(v for v in last_sums if v) == ([1, 1] if overflow else [])
     assert [it[0] for it in items] == sorted((it[0] for it in items), reverse=True)      # sponges first
 
 
