@@ -341,24 +341,25 @@ int sg_cosets_to_pieces_dev(void* d_values, void* const* d_pieces, uint32_t k, u
   if (!d_values || !d_pieces || !coset_shape_ok(k, ext_k, n_cosets)) return fail(SG_ERR_INVALID, "sg_cosets_to_pieces: bad argument");
   for (uint32_t t = 0; t < n_cosets; t++)
     if (!d_pieces[t]) return fail(SG_ERR_INVALID, "sg_cosets_to_pieces: null piece");
+  // (refused before the inverse transforms below run in place: a refused call writes nothing)
+  const size_t n = (size_t)1 << k;
+  for (uint32_t i = 0; i < n_cosets; i++) {
+    const uint8_t* lo = static_cast<const uint8_t*>(d_pieces[i]);
+    const uint8_t* vb = static_cast<const uint8_t*>(d_values);
+    if (lo < vb + 32 * n * n_cosets && vb < lo + 32 * n) return fail(SG_ERR_INVALID, "sg_cosets_to_pieces: the pieces may not overlap the values");
+  }
   LOCKED_CTX();
   const Context::CosetTables* t;
   TRY(coset_tables_for(k, ext_k, n_cosets, &t));
   hipStream_t s = pick_stream(stream);
   TRY(sync_own_stream_into(s));
-  const size_t n = (size_t)1 << k;
   fp_words* v = static_cast<fp_words*>(d_values);
   std::vector<fp_words*> blocks;
   for (uint32_t b = 0; b < n_cosets; b++) blocks.push_back(v + b * n);
   TRY(coset_ntts(blocks.data(), blocks.size(), k, true, s));
   CosetCombineArgs a{};
   a.raw = v;
-  for (uint32_t i = 0; i < n_cosets; i++) {
-    a.pieces[i] = static_cast<fp_words*>(d_pieces[i]);
-    const uint8_t* lo = reinterpret_cast<const uint8_t*>(a.pieces[i]);
-    const uint8_t* vb = reinterpret_cast<const uint8_t*>(v);
-    if (lo < vb + 32 * n * n_cosets && vb < lo + 32 * n) return fail(SG_ERR_INVALID, "sg_cosets_to_pieces: the pieces may not overlap the values");
-  }
+  for (uint32_t i = 0; i < n_cosets; i++) a.pieces[i] = static_cast<fp_words*>(d_pieces[i]);
   a.table_inv = t->inv;
   a.log_n = k;
   a.nc = n_cosets;

@@ -29,14 +29,15 @@ struct QuotLookupArgs {
   uint32_t cosets;   // > 0: coset-major arrays of cosets * 2^k rows (ext_k = k)
 };
 // ---- the quotient on quotient-degree many cosets of the 2^k domain instead of the whole extended domain
-// deg h < d n (d = cs.degree() - 1 = 5 here), so h is determined by its values on d cosets c_b H of the 2^k domain H:
-// halo2 evaluates on the 2^(k+3) extended domain = 8 such cosets, c_b = zeta omega_ext^b; the first d of them suffice.
+// deg h < d n, so h is determined by its values on d cosets c_b H of the 2^k domain H.  The count d is the caller's
+// (cs.degree() - 1; 5 for the reference circuit): any 1 <= d <= MAX_COSETS with d <= 2^(ext_k - k).  halo2 evaluates on the
+// 2^ext_k extended domain = 2^(ext_k - k) such cosets, c_b = zeta omega_ext^b; the first d of them suffice.
 // On c_b H the polynomial X^n is the constant g_b = c_b^n, therefore
 //   * the vanishing polynomial X^n - 1 is the constant g_b - 1 there, and
 //   * h restricted to the coset is P_b = h mod (X^n - g_b) = sum_t g_b^t h_t, h_t the pieces of n coefficients,
 // so the pieces follow from d inverse transforms of size n and one d x d Vandermonde solve per coefficient index:
 //   h_t[i] = sum_b M[t][b] c_b^-i iNTT_n(values_b)[i],   M = V^-1 diag(1 / (g_b - 1)),  V[b][t] = g_b^t.
-// The same h as halo2's extended_to_coeff (it is unique), from 5/8 of the rows.
+// The same h as halo2's extended_to_coeff (it is unique), from d / 2^(ext_k - k) of the rows (5/8 for the reference circuit).
 static constexpr uint32_t MAX_COSETS = 8, COSET_BATCH_MAX = 16;
 struct CosetScaleArgs {  // out[j][b * n + i] = in[j][i] * c_b^i
   const fp_words* in[COSET_BATCH_MAX];

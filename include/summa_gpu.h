@@ -244,7 +244,8 @@ int sg_divide_by_vanishing_poly_dev(void* d_ext, uint32_t k, uint32_t ext_k, voi
  * coefficient.  Same h as extended_to_coeff(divide_by_vanishing_poly(.)) -- it is unique -- from d / 2^(ext_k - k) of the rows. */
 int sg_coeff_to_cosets_batch_dev(const void* const* d_coeffs, void* const* d_out, size_t count, uint32_t k, uint32_t ext_k,
                                  uint32_t n_cosets, void* stream);
-/* d_values: n_cosets * 2^k coset-major values of the quotient's NUMERATOR (destroyed); d_pieces: n_cosets vectors of 2^k */
+/* d_values: n_cosets * 2^k coset-major values of the quotient's NUMERATOR (destroyed); d_pieces: n_cosets vectors of 2^k.
+ * SG_ERR_INVALID, with nothing written: n_cosets outside 1..8 or above 2^(ext_k - k), ext_k <= k, a piece that overlaps the values */
 int sg_cosets_to_pieces_dev(void* d_values, void* const* d_pieces, uint32_t k, uint32_t ext_k, uint32_t n_cosets, void* stream);
 
 /* ---- domain constants (EvaluationDomain::new): omega = ROOT_OF_UNITY^(2^(28-k)) etc.
