@@ -1,6 +1,7 @@
 // C ABI, quotient family: sg_quotient_*, the gate-program cache, sg_gates_program_*, and the circuit's keygen and witness
 // entry points (summa_gpu.hip holds the core).
 #include "abi_internal.h"
+#include "mst_entries.h"
 
 using namespace sg;
 namespace {
@@ -399,6 +400,33 @@ int sg_mst_build_dev(const void* d_usernames, const void* d_leaf_balances, uint3
     if (rc != SG_OK) return rc;
     off = parent;
   }
+  return SG_OK;
+}
+// Entry::new for a whole snapshot (mst_entries.hip).  Everything that can be wrong with the host buffers is found here, before
+// the device is touched: the kernels trust their offsets.  The four buffers travel in one work space of the caller's stream
+// (names, digits, then the two offset arrays from an 8-byte boundary on), so calls on one stream reuse it in stream order.
+int sg_mst_entries_dev(const uint8_t* name_bytes, const uint64_t* name_off, const uint8_t* digit_bytes, const uint64_t* digit_off,
+                       size_t n, size_t rows, uint32_t n_currencies, void* d_usernames, void* d_balances, void* stream) {
+  if (!name_bytes || !name_off || !digit_bytes || !digit_off || !d_usernames || !d_balances)
+    return fail(SG_ERR_INVALID, "sg_mst_entries: null argument");
+  if (n == 0 || rows < n || rows >= (1ull << 32) || n_currencies == 0 || n_currencies > 64)
+    return fail(SG_ERR_INVALID, "sg_mst_entries: bad size");
+  const std::string problem = mst_entries_problem(name_off, digit_bytes, digit_off, n, n_currencies);
+  if (!problem.empty()) return fail(SG_ERR_INVALID, ("sg_mst_entries: " + problem).c_str());
+  const size_t fields = n * (size_t)n_currencies;
+  const size_t name_len = name_off[n], digit_len = digit_off[fields];
+  const size_t at_digits = name_len, at_name_off = (name_len + digit_len + 7) & ~(size_t)7, at_digit_off = at_name_off + 8 * (n + 1);
+  LOCKED_CTX();
+  hipStream_t s = pick_stream(stream);
+  uint8_t* d = nullptr;
+  CHECK_HIP(scratch_for(s, 11, at_digit_off + 8 * (fields + 1), &d), "sg_mst_entries: work space");
+  if (name_len) CHECK_HIP(hipMemcpyAsync(d, name_bytes, name_len, hipMemcpyHostToDevice, s), "sg_mst_entries: names");
+  CHECK_HIP(hipMemcpyAsync(d + at_digits, digit_bytes, digit_len, hipMemcpyHostToDevice, s), "sg_mst_entries: digits");
+  CHECK_HIP(hipMemcpyAsync(d + at_name_off, name_off, 8 * (n + 1), hipMemcpyHostToDevice, s), "sg_mst_entries: name offsets");
+  CHECK_HIP(hipMemcpyAsync(d + at_digit_off, digit_off, 8 * (fields + 1), hipMemcpyHostToDevice, s), "sg_mst_entries: digit offsets");
+  CHECK_HIP(mst_entries_launch(d, reinterpret_cast<const uint64_t*>(d + at_name_off), d + at_digits,
+                               reinterpret_cast<const uint64_t*>(d + at_digit_off), n, rows, n_currencies, d_usernames, d_balances, s),
+            "sg_mst_entries");
   return SG_OK;
 }
 

@@ -25,6 +25,7 @@ hipError_t poly_set_side_prio(uint32_t on);
 hipError_t quotient_set_side_prio(uint32_t on);
 hipError_t gates_set_side_prio(uint32_t on);
 hipError_t witness_set_side_prio(uint32_t on);
+hipError_t mst_entries_set_side_prio(uint32_t on);
 hipError_t abi_set_side_prio(uint32_t on);
 }  // namespace sg
 #define SG_DEFINE_SIDE_PRIO_SETTER(name) \

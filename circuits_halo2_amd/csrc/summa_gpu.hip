@@ -129,6 +129,7 @@ int set_side_prio(int on) {
   if (e == hipSuccess) e = gates_set_side_prio(on);
   if (e == hipSuccess) e = numerator_set_side_prio(on);
   if (e == hipSuccess) e = witness_set_side_prio(on);
+  if (e == hipSuccess) e = mst_entries_set_side_prio(on);
   if (e == hipSuccess) e = abi_set_side_prio(on);
   if (e != hipSuccess) return hip_fail("side_prio", e);
   return SG_OK;

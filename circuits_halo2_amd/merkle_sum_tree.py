@@ -4,6 +4,8 @@ utils/csv_parser.rs, utils/operation_helpers.rs:10-12) with the hashing on the G
 
 Host logic kept here: CSV parsing, keccak256(username) -> field element, decimal balances ->
 field elements, zero-entry padding to 2^depth, Merkle-proof extraction (tree.rs:85-137).
+DeviceMerkleSumTree.from_entries / from_csv leave only the CSV parsing here: names and decimal balances
+become field elements on the device (sg_mst_entries_dev) and the tree stays in HBM.
 """
 from __future__ import annotations
 
@@ -391,12 +393,46 @@ class MerkleSumTree:
         return bool((node_h == rh).all() and (node_b == rb).all())
 
 
+def pack_entries(entries, n_currencies: int):
+    """[(username, [balances])] -> (name_bytes, name_off, digit_bytes, digit_off), the host buffers of sg_mst_entries_dev:
+    the UTF-8 names back to back with n + 1 byte offsets, the balances as `str(int)` back to back (entry-major, one field
+    per currency) with n * n_currencies + 1 offsets.  Host code only; refuses what MerkleSumTree.from_entries refuses."""
+    names, flat = [], []
+    for name, bal in entries:
+        if len(bal) != n_currencies:
+            raise ValueError("entry with a wrong number of balances")
+        names.append(name.encode())
+        flat += bal
+    if flat and min(flat) < 0:
+        raise ValueError("Invalid balance")
+    name_off = np.zeros(len(names) + 1, dtype=np.uint64)
+    np.cumsum(np.fromiter(map(len, names), dtype=np.uint64, count=len(names)), out=name_off[1:])
+    # the balances in one string with a comma between them: a field ends where a comma stood, less the commas before it
+    text = np.frombuffer(",".join(map(str, flat)).encode(), dtype=np.uint8)
+    comma = text == ord(",")
+    ends = np.flatnonzero(comma)
+    digit_off = np.zeros(len(flat) + 1, dtype=np.uint64)
+    if flat:
+        digit_off[1:-1] = ends - np.arange(ends.size)
+        digit_off[-1] = text.size - ends.size
+    return np.frombuffer(b"".join(names), dtype=np.uint8), name_off, text[~comma], digit_off
+
+
 class DeviceMerkleSumTree:
     """A Merkle sum tree whose leaves are already field elements on the device (a snapshot of 2^depth users: username
     field elements and balances as Montgomery Fr), built and KEPT in HBM: level-major node arrays as `sg_mst_build_dev`
     lays them out.  The reference's `Tree` trait [REF zk_prover/src/merkle_sum_tree/tree.rs:8-137] for the two methods a
     prover needs -- `root`, `generate_proof` --; a Merkle proof costs one gather of 3 * depth + 2 rows and one small
-    device-to-host copy.  (MerkleSumTree above is the CSV / entries flavour with the nodes mirrored on the host.)"""
+    device-to-host copy.  (MerkleSumTree above is the CSV / entries flavour with the nodes mirrored on the host.)
+
+    `from_entries`, `from_csv` and `from_csv_sorted` build the same tree from what an exchange has, usernames and
+    integer balances: the leaves' field elements are made on the device (sg_mst_entries_dev) and nothing comes back.  Such
+    a tree also knows its entries by name -- `entries`, `get_entry`, `index_of_username`, `cryptocurrencies`, `is_sorted`, and
+    the `entry` of a Merkle proof carries the name, as MerkleSumTree's do; after the plain constructor `entries` is None."""
+
+    entries = None            # [(name, balances)] padded with (None, [0] * n_currencies): trees built from entries only
+    is_sorted = False
+    cryptocurrencies = ()
 
     def __init__(self, d_usernames, d_balances, depth: int, n_currencies: int):
         import torch
@@ -418,6 +454,69 @@ class DeviceMerkleSumTree:
         for level in range(depth):
             self.offsets.append(self.offsets[-1] + (size >> level))
         self._root = None
+
+    @classmethod
+    def from_entries(cls, entries, n_currencies: int, n_bytes: int = 8, is_sorted: bool = False):
+        """mst.rs:103-134 with the tree in HBM: `Entry::new` of every entry on the device (keccak256 of the name, the decimal
+        balances folded in the field), zero entries up to 2^depth, then the constructor's build.  As in MerkleSumTree.from_entries
+        a balance that does not fit `n_bytes` only fails later, in the circuit's range check."""
+        import torch
+        entries = list(entries)
+        n = len(entries)
+        if n == 0:
+            raise ValueError("empty tree")
+        packed = pack_entries(entries, n_currencies)
+        name_bytes, name_off, digit_bytes, digit_off = packed
+        if name_bytes.size == 0:
+            name_bytes = np.zeros(1, dtype=np.uint8)          # only empty names: a buffer to point at all the same
+        depth = max(0, (n - 1).bit_length())
+        size = 1 << depth
+        d_users = torch.empty(32 * size, dtype=torch.uint8, device="cuda")
+        d_bals = torch.empty(32 * size * n_currencies, dtype=torch.uint8, device="cuda")
+        ffi.check(ffi.lib().sg_mst_entries_dev(ffi.ptr(name_bytes), ffi.ptr(name_off), ffi.ptr(digit_bytes), ffi.ptr(digit_off),
+                                               C.c_size_t(n), C.c_size_t(size), C.c_uint32(n_currencies), ffi.dev_ptr(d_users),
+                                               ffi.dev_ptr(d_bals), ffi.current_stream_ptr()))
+        tree = cls(d_users, d_bals, depth, n_currencies)       # same stream; synchronized when it returns
+        tree.entries = entries + [(None, [0] * n_currencies)] * (size - n)
+        tree.is_sorted = is_sorted
+        tree.cryptocurrencies = []
+        return tree
+
+    @classmethod
+    def from_csv(cls, path: str, n_currencies: int, n_bytes: int = 8):
+        entries, crypto = parse_csv_to_entries(path, n_currencies)
+        t = cls.from_entries(entries, n_currencies, n_bytes)
+        t.cryptocurrencies = crypto
+        return t
+
+    @classmethod
+    def from_csv_sorted(cls, path: str, n_currencies: int, n_bytes: int = 8):
+        """mst.rs:89-100: leaves sorted by the username byte values"""
+        entries, crypto = parse_csv_to_entries(path, n_currencies)
+        entries.sort(key=lambda e: e[0].encode())
+        t = cls.from_entries(entries, n_currencies, n_bytes, is_sorted=True)
+        t.cryptocurrencies = crypto
+        return t
+
+    def get_entry(self, index: int):
+        if self.entries is None:
+            raise ValueError("a tree built from field elements holds no entries")
+        return self.entries[index]
+
+    def index_of_username(self, username: str) -> int:
+        """mst.rs:207-223, MerkleSumTree's own search over this tree's entries"""
+        if self.entries is None:
+            raise KeyError("Username not found")
+        return MerkleSumTree.index_of_username(self, username)
+
+    @staticmethod
+    def _entry_fields(name, bal):
+        """MerkleSumTree._entry_fields; a username may also be its field element (the proofs of a tree without entries)"""
+        if isinstance(name, int):
+            return _to_fr_bytes(name), b"".join(_to_fr_bytes(v) for v in bal)
+        return MerkleSumTree._entry_fields(name, bal)
+
+    verify_proof = MerkleSumTree.verify_proof   # tree.rs:140-190: the same code, over this class's n_currencies and _entry_fields
 
     def _rows(self, hash_nodes, balance_nodes, users):
         """one gather + one copy: rows of the hash array, of the balance array (n_currencies rows per node), leaf inputs"""
@@ -465,7 +564,8 @@ class DeviceMerkleSumTree:
 
     def generate_proof(self, index: int):
         """the fields of the reference's MerkleProof (see MerkleSumTree.generate_proof); `entry` carries the username as
-        its field element (int), since a device snapshot holds no names"""
+        its field element (int) where the snapshot holds no names, and the entry itself (name, integer balances) where the
+        tree was built from entries"""
         if not 0 <= index < (1 << self.depth):
             raise IndexError("Index out of bounds")
         hash_nodes, bal_nodes, bits = [self.offsets[0] + index], [], []
@@ -482,6 +582,8 @@ class DeviceMerkleSumTree:
         to_int = lambda row: int.from_bytes(bytes(row), "little") * rinv % R_MODULUS
         nc = self.n_currencies
         entry = (to_int(users[0]), [to_int(bals[0][32 * c:32 * c + 32]) for c in range(nc)])
+        if self.entries is not None:
+            entry = self.entries[index]
         pre_mid = [np.concatenate([b[l], h[1 + 2 * l], h[2 + 2 * l]]) for l in range(max(0, self.depth - 1))]
         pre_leaf = np.concatenate([users[1], bals[1]]) if self.depth else None
         return {"entry": entry, "leaf": (h[0], bals[0]), "path_indices": bits, "root": self.root(),

@@ -545,6 +545,19 @@ int sg_mst_level_dev(const void* d_child_hashes, const void* d_child_balances, s
  * 2^(depth-1) parents, ..., the root last (2^(depth+1) - 1 nodes; balances NC per node) */
 int sg_mst_build_dev(const void* d_usernames, const void* d_leaf_balances, uint32_t depth, uint32_t n_currencies,
                      void* d_node_hashes, void* d_node_balances, void* stream);
+/* Entry::new (entry.rs:15-27) for n entries at once, the inputs of sg_mst_build_dev from usernames and decimal balances.
+ * HOST inputs, DEVICE outputs.
+ * names:  name_bytes[name_off[i] .. name_off[i+1]),  name_off: n+1 x uint64, name_off[0] = 0; any length, 0 included
+ * digits: field j = i*nc + c is digit_bytes[digit_off[j] .. digit_off[j+1]), digit_off: n*nc+1 x uint64; ASCII '0'..'9', any
+ *         length but 0: the number mod r, as Fp::from_str_vartime folds it
+ * d_usernames: rows x 32 B = keccak256(name) as a big-endian integer mod r, d_balances: rows x nc x 32 B (Montgomery),
+ * rows >= n; rows n.. are zeroed (the zero entry, entry.rs:30-38).
+ * SG_ERR_INVALID, found on the host before any device call: a null pointer; n == 0, rows < n, rows >= 2^32; n_currencies
+ * outside 1..64; offsets that do not start at 0 or that decrease; a balance field that is empty or holds another byte than
+ * a digit (sg_last_error names the lowest such field's index).  Complete in stream order.  Pageable host buffers have been read when the call returns; page-locked ones
+ * (sg_host_register) are read in stream order and stay as they are until the stream has passed the call. */
+int sg_mst_entries_dev(const uint8_t* name_bytes, const uint64_t* name_off, const uint8_t* digit_bytes, const uint64_t* digit_off,
+                       size_t n, size_t rows, uint32_t n_currencies, void* d_usernames, void* d_balances, void* stream);
 /* `MstInclusionCircuit::synthesize` (zk_prover/src/circuits/merkle_sum_tree.rs:228-520) on the device, for `n_users`
  * users of a tree built by sg_mst_build_dev: the three advice columns in the reference's own floor plan.  The floor plan
  * is a function of <LEVELS, N_CURRENCIES, N_BYTES> only and arrives as `d_program` (device memory): n_items x 5 u32

@@ -4,7 +4,8 @@ generate the verifying key (:52-68: the 17 commitments) and the proving key (:70
 the proof (:88-116: `full_prover`, Blake2b transcript) and verify it (:118-150: `full_verifier`); plus the inclusion witness of
 one user in the reference circuit's own floor plan (mst_inclusion.reference_assignment) and the Keccak-flavour create_proof.
 `build(levels, k)` returns everything a caller needs (tests/test_gpu_prover.py verifies the proof); run as a script
-it prints the timings."""
+it prints the timings.  With `--csv PATH` the snapshot is a real one: the tree is DeviceMerkleSumTree.from_csv of that file
+(its depth is LEVELS, its header gives the currencies) and the proof is the first user's."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import ctypes as C
@@ -82,6 +83,22 @@ def build(levels=20, k=13, user=123457, nc=2, timings=None):
     return asg
 
 
+def build_from_csv(path, k=13, nc=2, user=0, timings=None):
+    """`build` for a snapshot given as the reference's CSV (`username,balance_<name>_<chain>,...`): the entries become field
+    elements on the device and the tree stays there (DeviceMerkleSumTree.from_csv); -> (assignment, levels)"""
+    from circuits_halo2_amd import api
+    from circuits_halo2_amd.merkle_sum_tree import DeviceMerkleSumTree
+    t = {} if timings is None else timings
+    DeviceMerkleSumTree.from_csv(path, nc)
+    t0 = time.perf_counter(); tree = DeviceMerkleSumTree.from_csv(path, nc)       # synchronized when it returns
+    t["mst_from_csv_ms"] = (time.perf_counter() - t0) * 1e3
+    t0 = time.perf_counter()
+    asg = api.MstInclusionCircuit.init(tree.generate_proof(user), tree.depth, nc).synthesize(k)
+    t["witness_assignment_host_ms"] = (time.perf_counter() - t0) * 1e3
+    assert asg["instances"] == tree.public_inputs(user), "the assignment's public inputs are the device tree's leaf / root"
+    return asg, tree.depth
+
+
 def keygen_and_prove(asg, k, params, reps=3, timings=None, nc=2):
     t = {} if timings is None else timings
     dev = lambda v: torch.from_numpy(ints_to_fr(v)).cuda()
@@ -118,10 +135,13 @@ def keygen_and_prove(asg, k, params, reps=3, timings=None, nc=2):
     return pk, advice, proof
 
 
-def run(levels=20, k=13, cpp=True, nc=2):
+def run(levels=20, k=13, cpp=True, nc=2, csv=None):
     import json, subprocess, tempfile
     t = {}
-    asg = build(levels, k, nc=nc, timings=t)
+    if csv is not None:
+        asg, levels = build_from_csv(csv, k, nc=nc, timings=t)
+    else:
+        asg = build(levels, k, nc=nc, timings=t)
     params = sg.ParamsKZG.setup(k, ints_to_fr([0x1D0C0FFEE1234567890ABCDEF]))
     params.precompute()
     pk, advice, proof = keygen_and_prove(asg, k, params, timings=t, nc=nc)
@@ -139,5 +159,10 @@ def run(levels=20, k=13, cpp=True, nc=2):
 
 if __name__ == "__main__":
     ffi.check(ffi.lib().sg_init(0))
-    print(run(int(sys.argv[1]) if len(sys.argv) > 1 else 20, int(sys.argv[2]) if len(sys.argv) > 2 else 13,
-              nc=int(sys.argv[3]) if len(sys.argv) > 3 else 2))
+    argv, csv_path = sys.argv[1:], None
+    if "--csv" in argv:                       # [LEVELS [K [N_CURRENCIES]]] --csv PATH: LEVELS is then the tree's own depth
+        at = argv.index("--csv")
+        csv_path = argv[at + 1]
+        del argv[at:at + 2]
+    print(run(int(argv[0]) if len(argv) > 0 else 20, int(argv[1]) if len(argv) > 1 else 13,
+              nc=int(argv[2]) if len(argv) > 2 else 2, csv=csv_path))
