@@ -27,7 +27,8 @@ def make_setup(k):
     asg = MA.build(k)
     if k <= 10:
         assert MA.check_gates(asg, k)      # row by row with Python integers (the floor plan does not depend on k)
-    tau = ints_to_fr([0x1D0C0FFEE1234567890ABCDEF])
+    tau_int = 0x1D0C0FFEE1234567890ABCDEF     # a KNOWN tau: tests/prover_definition.py computes on the host what a column commits to
+    tau = ints_to_fr([tau_int])
     params = sg.ParamsKZG.setup(k, tau)
     dev = lambda ints: torch.from_numpy(ints_to_fr(ints)).cuda()
     pk = prover.ProvingKey(params, k, [dev(c) for c in asg["fixed"]], [dev(c) for c in asg["sigma"]])
@@ -36,7 +37,7 @@ def make_setup(k):
     s_g2 = (f2(params.s_g2[:64]), f2(params.s_g2[64:]))
     vk = {"k": k, "vk_digest": pk.vk_digest, "fixed_comms": pk.fixed_comms, "permutation_comms": pk.permutation_comms, "g2": g2,
           "neg_s_g2": (s_g2[0], ((-s_g2[1][0]) % PR.Q, (-s_g2[1][1]) % PR.Q))}
-    return {"k": k, "asg": asg, "params": params, "pk": pk, "vk": vk, "dev": dev, "prover": prover}
+    return {"k": k, "asg": asg, "params": params, "pk": pk, "vk": vk, "dev": dev, "prover": prover, "tau": tau_int}
 
 
 @pytest.fixture(scope="module")
@@ -213,8 +214,12 @@ def test_cpp_prover_proof_is_accepted(k, tmp_path):
 def test_cpp_prover_under_a_fixed_blinding_key_equals_the_python_driver(setup, tmp_path):
     """the two drivers number their blinding draws alike (1-5 advice and permuted columns, 6-8 grand products, 9 the random
     polynomial), so under one ChaCha20 key the compiled driver (Options::blinding_key, the tool's fourth argument) writes the
-    proof prover.create_proof(seed=key) returns, byte for byte; without a key it draws its own and the proof differs"""
+    proof prover.create_proof(seed=key) returns, byte for byte; without a key it draws its own and the proof differs.
+    That the two agree says nothing about a mistake they share: the compiled driver's first nine commitments are also the
+    definition's (tests/prover_definition.py: every column restated with Python integers, blinding rows included, committed under the
+    known tau), bit for bit"""
     import subprocess
+    import prover_definition as D
     from oracle import summa_verifier as SV
     s = setup
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -229,11 +234,16 @@ def test_cpp_prover_under_a_fixed_blinding_key_equals_the_python_driver(setup, t
     r = subprocess.run([exe, bundle, out, "1", key.hex()], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
     fixed = open(out, "rb").read()
-    assert len(fixed) == 2144 and fixed == want
+    assert len(fixed) == 2144
+    D.check_proof(fixed, s["asg"], s["k"], s["tau"], key, s["vk"])     # before the comparison: each driver answers to the definition
+    assert fixed == want
     r = subprocess.run([exe, bundle, out, "1"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
     fresh = open(out, "rb").read()
     assert len(fresh) == 2144 and fresh != want and SV.verify(fresh, inst, s["vk"])
+    # "differs" at EVERY point: a draw left out under its own key would show as a point it shares with the fixed-key proof
+    for (name, p), (_, q) in zip(D.proof_points(fresh), D.proof_points(fixed)):
+        assert p != q, name
     assert subprocess.run([exe, bundle, out, "1", "abc"], capture_output=True).returncode == 2   # not 64 hex digits
 
 
