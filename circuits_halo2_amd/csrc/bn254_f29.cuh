@@ -161,7 +161,9 @@ SG_HD f29 f29_add(const f29& a, const f29& b) {
   for (int i = 0; i < 9; i++) r.l[i] = a.l[i] + b.l[i];
   return f29_carry(r);
 }
-// lazy subtraction a - b + K*p, K = 2 << LOGK_MINUS1 must be >= bound(b); bound Ba + K
+// lazy subtraction a - b + K*p, K = 2 << LOGK_MINUS1 must be >= bound(b); bound Ba + K.  The one carry step settles the top
+// limb only while the result is not far below 2^232 (the odds against are 2^-50 on uniform values; b = K (p - 1), a = 0 is such
+// a case): where every canonical input has to come out right, normalise exactly (gates_sub, gates_device.cuh)
 template <class P, int KIDX>
 SG_HD f29 f29_sub(const f29& a, const f29& b) {
   f29 r;

@@ -52,12 +52,12 @@ __global__ void __launch_bounds__(T) gates_kernel(GateArgs a) {
   };
   auto sub_k = [&](uint32_t kidx, const f29& x, const f29& y) {
     switch (kidx) {
-      case 0: return f29_sub<P, 0>(x, y);
-      case 1: return f29_sub<P, 1>(x, y);
-      case 2: return f29_sub<P, 2>(x, y);
-      case 3: return f29_sub<P, 3>(x, y);
-      case 4: return f29_sub<P, 4>(x, y);
-      default: return f29_sub<P, 5>(x, y);
+      case 0: return gates_sub<P, 0>(x, y);
+      case 1: return gates_sub<P, 1>(x, y);
+      case 2: return gates_sub<P, 2>(x, y);
+      case 3: return gates_sub<P, 3>(x, y);
+      case 4: return gates_sub<P, 4>(x, y);
+      default: return gates_sub<P, 5>(x, y);
     }
   };
   for (uint32_t pc = 0; pc < a.n_ops; pc++) {

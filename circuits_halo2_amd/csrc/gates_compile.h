@@ -449,7 +449,7 @@ inline GateTile gates_interpreter_tile(uint32_t n_slots, uint32_t n_consts, uint
 }
 
 // ------------------------------------------------------------------ lowered programs by structure
-// The lowered program depends on the graph's structure only, so it is cached under the structure itself.  A prover sends the
+// The lowered program depends on the graph's structure and the GateLowering only, so it is cached under those themselves.  A prover sends the
 // same two programs proof after proof, so the most recent hits are tried first with one memcmp each (the structure of the
 // reference circuit's gate program is 100+ KB: hashing it byte by byte cost 0.3 ms of host time per proof, with the device
 // idle behind it); only a miss there hashes.
@@ -471,8 +471,13 @@ struct GateProgramCache {
   uint32_t recent_next = 0;
   uint64_t (*key_of)(const std::vector<uint8_t>&) = gate_signature_key;   // (a seam for tests: colliding keys)
 
-  static std::vector<uint8_t> signature(const sg_graph& g, uint32_t n_fixed, uint32_t n_advice, uint32_t n_instance, uint32_t n_challenges) {
-    const uint32_t hdr[8] = {g.n_constants, g.n_rotations, g.n_calculations, g.n_horner_parts, n_fixed, n_advice, n_instance, n_challenges};
+  // everything the lowered words depend on: the graph's structure, the column counts and the knobs of the lowering (a lane that
+  // has compiled a graph under one GateLowering must not hand that program out under another)
+  static std::vector<uint8_t> signature(const sg_graph& g, uint32_t n_fixed, uint32_t n_advice, uint32_t n_instance, uint32_t n_challenges,
+                                        const GateLowering& how) {
+    const uint64_t reload = how.reload_distance;
+    const uint32_t hdr[12] = {g.n_constants, g.n_rotations, g.n_calculations, g.n_horner_parts, n_fixed, n_advice, n_instance, n_challenges,
+                              (uint32_t)reload, (uint32_t)(reload >> 32), how.convert_at_load ? 1u : 0u, how.convert_at_load ? how.convert_above : 0u};
     const size_t parts[4] = {sizeof hdr, g.rotations ? sizeof(int32_t) * g.n_rotations : 0,
                              g.calculations ? sizeof(sg_calculation) * g.n_calculations : 0,
                              g.horner_parts ? sizeof(sg_value_source) * g.n_horner_parts : 0};
@@ -493,7 +498,7 @@ struct GateProgramCache {
   // compile_gates' message.
   std::string lookup_or_compile(const sg_graph& g, uint32_t n_fixed, uint32_t n_advice, uint32_t n_instance, uint32_t n_challenges,
                                 const GateLowering& how, GateProgram** out) {
-    std::vector<uint8_t> sig = signature(g, n_fixed, n_advice, n_instance, n_challenges);
+    std::vector<uint8_t> sig = signature(g, n_fixed, n_advice, n_instance, n_challenges, how);
     auto hit = programs.end();
     for (uint64_t key : recent) {
       auto it = programs.find(key);

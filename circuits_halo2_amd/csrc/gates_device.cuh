@@ -20,6 +20,15 @@ struct GateArgs {
   uint64_t rows, blockmask;
 };
 
+// a - b + K p of a gate program (G_SUB, G_NEG), K = 2 << KIDX.  Not f29_sub: its one parallel carry step leaves the top limb
+// right only while the difference is not far below 2^232.  With b within a few words of K p -- the negation of a column word
+// r - 1 is 32 p - 32 (r - 1) = 32 -- the carries have to ripple through all nine limbs, and the top limb came out as -1, which
+// the next product read as 2^32 - 1.  The exact sequential normalisation is the same number of instructions.
+template <class P, int KIDX>
+__device__ __forceinline__ f29 gates_sub(const f29& a, const f29& b) {
+  return f29_normalize(f29_sub_nc<P, KIDX>(a, b));
+}
+
 // where a straight-line program reads from: column pointers (fixed ++ advice ++ instance, indexed by compile-time constants)
 // and the previous values (nullptr: zero)
 struct GateSrc {
@@ -72,11 +81,11 @@ __device__ __forceinline__ void fixed_step(f29 (&slot)[PROG::n_slots], const uin
     } else {
       const f29 x = fixed_operand<ak, op.a, NS>(slot, s_const);
       if constexpr (code == G_ADD) r = f29_add(x, fixed_operand<bk, op.b, NS>(slot, s_const));
-      else if constexpr (code == G_SUB) r = f29_sub<P, (kidx < 5 ? kidx : 5)>(x, fixed_operand<bk, op.b, NS>(slot, s_const));
+      else if constexpr (code == G_SUB) r = gates_sub<P, (kidx < 5 ? kidx : 5)>(x, fixed_operand<bk, op.b, NS>(slot, s_const));
       else if constexpr (code == G_MUL) r = f29_mul<P>(x, fixed_operand<bk, op.b, NS>(slot, s_const));
       else if constexpr (code == G_SQR) r = f29_sqr<P>(x);
       else if constexpr (code == G_DBL) r = f29_add(x, x);
-      else if constexpr (code == G_NEG) r = f29_sub<P, (kidx < 5 ? kidx : 5)>(f29_zero(), x);
+      else if constexpr (code == G_NEG) r = gates_sub<P, (kidx < 5 ? kidx : 5)>(f29_zero(), x);
       else if constexpr (code == G_MULADD)
         r = f29_mul_add<P>(x, fixed_operand<bk, op.b, NS>(slot, s_const), fixed_operand<kidx, ci, NS>(slot, s_const));
       else r = f29_reduce_small<P>(x);   // G_RED

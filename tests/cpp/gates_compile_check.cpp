@@ -139,6 +139,39 @@ static const char* cache_check() {
     GateProgram *a = look(c, 101), *b = look(c, 102);
     if (!a || !b || a == b || c.programs.size() != (before == 61 ? 63u : 2u) || a->n_columns != 101 || a->signature.empty()) return "a reserved pair stays";
   }
+  {  // one graph, several lowerings, one cache: each GateLowering gets the program compile_gates gives for it, and keeps it
+    static const int32_t rots[2] = {0, 1};
+    const sg_value_source a0{SG_VS_ADVICE, 0, 0}, a1{SG_VS_ADVICE, 0, 1}, none{0, 0, 0};
+    std::vector<sg_calculation> cals;   // the two cells of a column, added over and over: 40 additions, then their square
+    cals.push_back({SG_OP_ADD, a0, a1, 0, 0});
+    for (uint32_t i = 1; i < 40; i++) cals.push_back({SG_OP_ADD, {SG_VS_INTERMEDIATE, i - 1, 0}, i % 2 ? a0 : a1, 0, 0});
+    cals.push_back({SG_OP_SQUARE, {SG_VS_INTERMEDIATE, 39, 0}, none, 0, 0});
+    const sg_graph chain{nullptr, 0, rots, 2, cals.data(), (uint32_t)cals.size(), nullptr, 0};
+    GateLowering plain, never_reuse, convert;
+    never_reuse.reload_distance = 0;
+    convert.convert_at_load = true;
+    convert.convert_above = 1;
+    GateProgramCache c;
+    auto same = [](const GateProgram& p, const GateProgram& q) {
+      return p.n_slots == q.n_slots && p.result_kind == q.result_kind && p.result_index == q.result_index && p.ops.size() == q.ops.size() &&
+             (p.ops.empty() || std::memcmp(p.ops.data(), q.ops.data(), p.ops.size() * sizeof(GateOp)) == 0);
+    };
+    std::vector<GateProgram> fresh(3), got;
+    const GateLowering* hows[3] = {&plain, &never_reuse, &convert};
+    for (int round = 0; round < 2; round++)
+      for (int i = 0; i < 3; i++) {
+        GateProgram* p = nullptr;
+        if (!compile_gates(chain, 0, 1, 0, 0, *hows[i], &fresh[i]).empty() || !c.lookup_or_compile(chain, 0, 1, 0, 0, *hows[i], &p).empty()) return "compile";
+        if (!same(*p, fresh[i])) return "a look-up gives the program of its own lowering";
+        if (round == 0) got.push_back(*p);
+      }
+    if (same(got[0], got[1]) || same(got[0], got[2]) || same(got[1], got[2])) return "different lowerings give different programs";
+    if (c.programs.size() != 3) return "one entry per lowering";
+    GateLowering off_but_above = plain;   // convert_above means nothing while convert_at_load is off: the same entry
+    off_but_above.convert_above = 9;
+    GateProgram* p = nullptr;
+    if (!c.lookup_or_compile(chain, 0, 1, 0, 0, off_but_above, &p).empty() || !same(*p, fresh[0]) || c.programs.size() != 3) return "an idle knob is no new entry";
+  }
   return nullptr;
 }
 

@@ -1,6 +1,9 @@
 """The gate compiler's corpus and an independent reading of what it emits (no GPU): the graphs whose lowering
 tests/golden/gates_lowering.json pins, their text form for tests/cpp/gates_compile_check.cpp, a restatement of the interpreter's
-tile rule, and a Python interpreter of the ten opcodes over integers mod r that re-derives the operand bounds on the way."""
+tile rule, and a Python interpreter of the ten opcodes over integers mod r that re-derives the operand bounds on the way.
+Below that the device corpus (what tests/test_gpu_gates_edges.py runs: those graphs and hand-written ones at the compiler's bounds,
+rotations beyond the domain, the LDS budget and the blob ring's slot size), the word patterns, the rows expected of the device by
+the C oracle and by halo2's definition in Python integers, and the device's lazy arithmetic replayed in integers."""
 import ctypes as C
 import hashlib
 
@@ -32,13 +35,19 @@ class RawGraph:
             parts.extend(own)
         return cls(len(g.constants), g.rotations, calcs, parts)
 
-    def _struct(self):   # what circuits_halo2_amd.arithmetic hands to the library
+    def _struct(self, constants=None):   # what circuits_halo2_amd.arithmetic hands to the library (constants: n_constants x 32 B, else zeros)
         consts = np.zeros(32 * max(1, self.n_constants), np.uint8)
-        rots = np.asarray(self.rotations or [0], dtype=np.int32)
-        calcs = (A._Calc * max(1, len(self.calcs)))()
-        for i, (op, a, b, off, n) in enumerate(self.calcs):
-            calcs[i].op, calcs[i].a, calcs[i].b, calcs[i].parts_offset, calcs[i].parts_len = op, A._VS(*a), A._VS(*b), off, n
-        parr = (A._VS * max(1, len(self.parts)))(*[A._VS(*p) for p in self.parts])
+        if constants is not None:
+            assert constants.size == 32 * self.n_constants
+            consts[:constants.size] = constants
+        if getattr(self, "_arrays", None) is None or self._arrays[0] != (len(self.calcs), len(self.parts)):   # (the large graphs: built once)
+            rots = np.asarray(self.rotations or [0], dtype=np.int32)
+            calcs = (A._Calc * max(1, len(self.calcs)))()
+            for i, (op, a, b, off, n) in enumerate(self.calcs):
+                calcs[i].op, calcs[i].a, calcs[i].b, calcs[i].parts_offset, calcs[i].parts_len = op, A._VS(*a), A._VS(*b), off, n
+            parr = (A._VS * max(1, len(self.parts)))(*[A._VS(*p) for p in self.parts])
+            self._arrays = ((len(self.calcs), len(self.parts)), rots, calcs, parr)
+        _, rots, calcs, parr = self._arrays
         at = lambda name, p: None if name in self.null else p
         g = A._Graph(at("constants", consts.ctypes.data), self.n_constants, at("rotations", rots.ctypes.data), len(self.rotations),
                      at("calculations", C.addressof(calcs)), len(self.calcs), at("parts", C.addressof(parr)), len(self.parts))
@@ -265,10 +274,11 @@ def decode(words):
     return n_slots, result_kind, result_index, ops
 
 
-def run_program(words, consts, column, previous):
+def run_program(words, consts, column, previous, trace=None):
     """the program's result over integers mod r.  consts: the constant table; column(index, rotation) -> value of fixed ++ advice
     ++ instance.  Re-derives every operand's bound by the compiler's rules and asserts them, and that a slot is written before
-    it is read and lies below n_slots.  Returns (value, largest bound met)."""
+    it is read and lies below n_slots.  Returns (value, largest bound met).  trace: a list that receives, per instruction,
+    (opcode, kidx, bound of a, bound of b, bound of a G_MULADD's addend, bound of the result), None where there is none."""
     n_slots, result_kind, result_index, ops = decode(words)
     assert n_slots >= 1
     slot = [None] * n_slots       # (value, bound)
@@ -282,6 +292,7 @@ def run_program(words, consts, column, previous):
 
     for pc, o in enumerate(ops):
         code, kidx = o["code"], o["kidx"]
+        bx = by = bz = None
         if code == LOADCOL:
             assert kidx in (0, 1)
             r = column(o["a"], o["b"]) % R, (2 if kidx else 32)
@@ -314,4 +325,424 @@ def run_program(words, consts, column, previous):
         assert o["dst"] < n_slots
         slot[o["dst"]] = r
         top = max(top, r[1])
+        if trace is not None:
+            trace.append((code, kidx, bx, by, bz, r[1]))
     return get(result_kind, result_index)[0], top
+
+
+# ============================================================================= the device corpus
+# What the GPU tests of the gate evaluator run (tests/test_gpu_gates_edges.py) and what tests/test_gates_cases_cpu.py checks
+# without one: every graph of corpus() that lowers, and hand-written graphs named after what they reach.
+class _Build:
+    """a RawGraph written by hand: nothing is deduplicated, every constant is a table entry of its own"""
+
+    def __init__(self):
+        self.n_constants, self.rotations, self.calcs, self.parts = 0, [], [], []
+
+    def const(self):
+        self.n_constants += 1
+        return (A.CONSTANT, self.n_constants - 1, 0)
+
+    def q(self, kind, column, rot=0):
+        if rot not in self.rotations:
+            self.rotations.append(rot)
+        return (kind, column, self.rotations.index(rot))
+
+    def op(self, op, a, b=NO_B):
+        self.calcs.append((op, tuple(a), tuple(b), 0, 0))
+        return (A.INTERMEDIATE, len(self.calcs) - 1, 0)
+
+    def horner(self, start, parts, factor):
+        self.calcs.append((A.HORNER, tuple(start), tuple(factor), len(self.parts), len(parts)))
+        self.parts += [tuple(p) for p in parts]
+        return (A.INTERMEDIATE, len(self.calcs) - 1, 0)
+
+    def sum_of(self, terms):
+        acc = terms[0]
+        for t in terms[1:]:
+            acc = self.op(A.ADD, acc, t)
+        return acc
+
+    def raw(self):
+        return RawGraph(self.n_constants, self.rotations or [0], self.calcs, self.parts)
+
+
+def _loads_and_constants(b, n_loads, n_consts, column=0):
+    """n_loads cells of advice columns from `column` on (bound 32 each) plus n_consts constants (bound 2 each), summed"""
+    return b.sum_of([b.q(A.ADVICE, column + i, i % 2) for i in range(n_loads)] + [b.const() for _ in range(n_consts)])
+
+
+def fill_mul_160():
+    """two loads plus eight constants: an addition result at 80; times a constant: a product at 80 x 2 = 160"""
+    b = _Build()
+    b.op(A.MUL, _loads_and_constants(b, 2, 8), b.const())
+    return b.raw()
+
+
+def fill_muladd_160_plus_78():
+    """x y + z in one G_MULADD with x y at 80 x 2 and z at 78 (two loads, seven constants: the compiler lets an addend run to
+    80 - 2, so that the fused sum stays within 80)"""
+    b = _Build()
+    z = _loads_and_constants(b, 2, 7, column=2)
+    b.op(A.ADD, b.op(A.MUL, _loads_and_constants(b, 2, 8), b.const()), z)
+    return b.raw()
+
+
+def fill_sqr_144():
+    """the square of a sum of six constants: 12 x 12 = 144"""
+    b = _Build()
+    b.op(A.SQUARE, b.sum_of([b.const() for _ in range(6)]))
+    return b.raw()
+
+
+SUBTRAHENDS = {0: (0, 1), 1: (0, 2), 2: (0, 4), 3: (0, 8), 4: (1, 0), 5: (2, 0)}   # kidx -> (loads, constants): bound 2 << kidx
+
+
+def fill_sub_neg(kidx, small_minuend=False):
+    """a - b and -b with b at the whole of K = 2 << kidx (above half of it: no smaller K would do), then (a - b) c + (-b).
+    a is a load (bound 32), at kidx 5 a load and twelve constants (56: the subtraction's result at 56 + 64 = 120); with
+    small_minuend a constant, so that a - b + K p has nothing to spare when every word is the largest"""
+    b = _Build()
+    sub = _loads_and_constants(b, *SUBTRAHENDS[kidx], column=1)
+    a =b.const() if small_minuend else _loads_and_constants(b, 1, 12 if kidx == 5 else 0)
+    t, n = b.op(A.SUB, a, sub), b.op(A.NEGATE, sub)
+    b.op(A.ADD, b.op(A.MUL, t, b.const()), n)
+    return b.raw()
+
+
+def fill_doubling():
+    """doublings of a constant to 64 and on (the seventh reduces first), of a load to 64 and on, and of 40 (a load and four
+    constants) to 80, which a constant then multiplies: 160"""
+    b = _Build()
+    x = b.const()
+    for _ in range(8):
+        x = b.op(A.DOUBLE, x)
+    y = b.q(A.ADVICE, 0, 0)
+    for _ in range(3):
+        y = b.op(A.DOUBLE, y)
+    z = b.op(A.MUL, b.op(A.DOUBLE, _loads_and_constants(b, 1, 4, column=1)), b.const())
+    b.op(A.ADD, b.op(A.ADD, x, y), z)
+    return b.raw()
+
+
+def fill_product_at_the_top():
+    """a product the compiler reduces one operand of: a = two loads and eight constants (80), b = P + P for a square P of a sum
+    of constants (4), so G_RED(a) first; then -(a b) with K = 2.  (Canonical words do not bring a b to the top of 320 with the
+    reduction left out: a constant's 2^261 form is what a product leaves, about p for the word r - 1, half its bound of 2.)"""
+    b = _Build()
+    p = b.op(A.SQUARE, b.sum_of([b.const() for _ in range(5)]))
+    a = _loads_and_constants(b, 2, 8)
+    b.op(A.NEGATE, b.op(A.MUL, a, b.op(A.ADD, p, p)))
+    return b.raw()
+
+
+ROTATION_KS = (1, 2, 5, 6)
+
+
+def rotation_list(k):
+    n = 1 << k
+    out = []
+    for r in (0, 1, -1, n - 1, -(n - 1), n, -n, n + 1, -(n + 1), -5, 17):
+        if r not in out:
+            out.append(r)
+    return out
+
+
+def rotations_graph(k):
+    """a fixed, an advice and an instance column at rotations 0, +-1, +-(n - 1), +-n, +-(n + 1), -5 and 17 of n = 2^k (they wrap
+    more than once at k = 1 and 2), folded by Horner in y so that no two queries may change places"""
+    b = _Build()
+    parts = [b.q(kind, 0, r) for r in rotation_list(k) for kind in (A.FIXED, A.ADVICE, A.INSTANCE)]
+    b.horner(b.const(), parts, (A.Y, 0, 0))
+    return b.raw()
+
+
+MANY_CONSTANTS = 1500
+
+
+def many_constants_graph():
+    """40 live values (many_live_values(39)), then a Horner over 1500 constants of the table: 1504 entries with beta, gamma,
+    theta and y.  At 64 rows per workgroup that is within one slot of the LDS budget"""
+    g = RawGraph.of(many_live_values(39))
+    last = (A.INTERMEDIATE, len(g.calcs) - 1, 0)
+    g.parts = [(A.CONSTANT, i, 0) for i in range(MANY_CONSTANTS)]
+    g.calcs.append((A.HORNER, last, (A.THETA, 0, 0), 0, MANY_CONSTANTS))
+    g.n_constants = MANY_CONSTANTS
+    return g
+
+
+LARGE_PRODUCTS = 7000
+
+
+def large_program_graph():
+    """a balanced sum of 7000 products of two cells: more than 16384 lowered instructions (a blob above 256 KiB), 14 levels deep"""
+    b = _Build()
+    rots = (0, 1, -1, 2)
+    level = [b.op(A.MUL, b.q(A.ADVICE, i % 4, rots[(i // 4) % 4]), b.q(A.FIXED, i % 3, rots[(i // 12) % 4])) for i in range(LARGE_PRODUCTS)]
+    while len(level) > 1:
+        level = [b.op(A.ADD, level[i], level[i + 1]) if i + 1 < len(level) else level[i] for i in range(0, len(level), 2)]
+    return b.raw()
+
+
+def random_folded_graph(rng, n_fixed, n_advice, n_instance, n_chal, n_calc, O):
+    """random_graph ended the way halo2 ends a program, Horner(previous value, [every calculation], y): the last calculation
+    of a random_graph reaches only a handful of the others (the lowering is demand-driven), this one reaches them all"""
+    g = random_graph(rng, n_fixed, n_advice, n_instance, n_chal, n_calc, O)
+    g.add_calculation(A.HORNER, (A.PREVIOUS_VALUE, 0, 0), (A.Y, 0, 0), [(A.INTERMEDIATE, q, 0) for q in range(len(g.calculations))])
+    return g
+
+
+FOLDED_SEEDS = [(501, 8, (3, 4, 1, 2)), (502, 40, (3, 4, 1, 2)), (503, 40, (1, 2, 0, 0)), (504, 120, (3, 4, 1, 2)), (505, 120, (2, 5, 1, 3)),
+                (506, 300, (3, 4, 1, 2)), (507, 300, (4, 3, 0, 1))]
+BOUND_FILLERS = ["fill_mul_160", "fill_muladd_160_plus_78", "fill_sqr_144", "fill_doubling", "fill_product_at_the_top",
+                 *[f"fill_sub_neg_kidx{k}" for k in range(6)], *[f"fill_sub_neg_small_minuend_kidx{k}" for k in range(6)]]
+REFUSED = ("live_values_70", "live_values_63")     # they lower; sg_quotient_gates* refuses them (65 slots and more; 64 slots)
+_device_corpus = None
+
+
+def device_corpus(O):
+    """every graph of corpus(O) that lowers (the error_* graphs are the ones that do not), then the hand-written ones"""
+    global _device_corpus
+    if _device_corpus is not None:
+        return _device_corpus
+    cases = [c for c in corpus(O) if not c.name.startswith("error_")]
+    own = lambda name, graph, na, nf=0, ni=0: cases.append(Case(name, graph, nf, na, ni, 0))
+    for seed, n_calc, dims in FOLDED_SEEDS:
+        cases.append(Case(f"random_folded_seed{seed}_calc{n_calc}", random_folded_graph(np.random.default_rng(seed), *dims, n_calc, O), *dims))
+    own("fill_mul_160", fill_mul_160(), 2)
+    own("fill_muladd_160_plus_78", fill_muladd_160_plus_78(), 4)
+    own("fill_sqr_144", fill_sqr_144(), 1)
+    own("fill_doubling", fill_doubling(), 2)
+    own("fill_product_at_the_top", fill_product_at_the_top(), 2)
+    for kidx in range(6):
+        own(f"fill_sub_neg_kidx{kidx}", fill_sub_neg(kidx), 3)
+        own(f"fill_sub_neg_small_minuend_kidx{kidx}", fill_sub_neg(kidx, small_minuend=True), 3)
+    for k in ROTATION_KS:
+        own(f"rotations_k{k}", rotations_graph(k), 1, 1, 1)
+    own("many_constants", many_constants_graph(), 1)
+    own("large_program", large_program_graph(), 4, 3)
+    own("live_values_62", many_live_values(62), 1)
+    own("live_values_63", many_live_values(63), 1)
+    assert len({c.name for c in cases}) == len(cases) and set(BOUND_FILLERS) <= {c.name for c in cases}
+    _device_corpus = cases
+    return cases
+
+
+def device_case(O, name):
+    return next(c for c in device_corpus(O) if c.name == name)
+
+
+# ----------------------------------------------------------------------------- words
+# Every word fed is canonical (below r).  That is the compiler's contract (gates_compile.h at convert_at_load: "column words
+# (canonical, < p) enter as x~ << 5 = x^ with bound 32"), and the prover hands the evaluator nothing else: NTT outputs and columns
+# it has counted canonical.  A word at or above r would break the bound 32 the lowering starts from, so none is fed here.
+PATTERNS = ["top", "zero", "one", "columns_alternate", "columns_alternate_reversed", "rows_cycle", "random"]
+ONE = (1 << 256) % R
+CYCLE = [0, 1, R - 1, R - 2, 1 << 253, None]    # None: a random word
+
+
+def _words(values):
+    return np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in values), dtype=np.uint8).copy()
+
+
+def _ints(words):
+    raw = bytes(np.ascontiguousarray(words, dtype=np.uint8))
+    return [int.from_bytes(raw[i:i + 32], "little") for i in range(0, len(raw), 32)]
+
+
+def _pattern_words(O, pattern, n, j, seed):
+    """n words of the j-th array (a column, the previous values, the constants, the challenges, beta .. y)"""
+    if pattern == "random" or n == 0:
+        return O.random_fr(seed, n)
+    if pattern == "rows_cycle":
+        rnd = _ints(O.random_fr(seed, n))
+        return _words([rnd[i] if CYCLE[i % 6] is None else CYCLE[i % 6] for i in range(n)])
+    if pattern.startswith("columns_alternate"):
+        pattern = "top" if (j % 2 == 0) != pattern.endswith("reversed") else "zero"
+    return np.tile(_words([{"top": R - 1, "zero": 0, "one": ONE}[pattern]]), n)
+
+
+def make_inputs(O, case, pattern, rows, seed=0):
+    """{"fixed" / "advice" / "instance": [rows x 32 B], "previous": rows x 32 B, "constants", "challenges", "beta", "gamma",
+    "theta", "y"}: the pattern applies to all of them alike.  beta .. y are the four words of one array (rows_cycle: 0, 1,
+    r - 1, r - 2); under columns_alternate the arrays count on from the columns: previous, constants, challenges, beta .. y."""
+    assert pattern in PATTERNS
+    j, inp = 0, {}
+
+    def take(n):
+        nonlocal j
+        j += 1
+        return _pattern_words(O, pattern, n, j - 1, 7919 * seed + 31 * j + 1)
+    for group, n in (("fixed", case.n_fixed), ("advice", case.n_advice), ("instance", case.n_instance)):
+        inp[group] = [take(rows) for _ in range(n)]
+    inp["previous"] = take(rows)
+    inp["constants"] = take(case.graph.n_constants)
+    inp["challenges"] = take(case.n_challenges)
+    four = take(4)
+    for i, name in enumerate(("beta", "gamma", "theta", "y")):
+        inp[name] = four[32 * i:32 * i + 32].copy()
+    return inp
+
+
+class GraphWithConstants:
+    """what circuits_halo2_amd.arithmetic.quotient_gates* takes for a graph: the case's structure with these constants"""
+
+    def __init__(self, case, constants):
+        self.case, self.constants = case, np.ascontiguousarray(constants, dtype=np.uint8)
+
+    def _struct(self):
+        return self.case.graph._struct(self.constants)
+
+
+# ----------------------------------------------------------------------------- the expectation
+def _reached(graph):
+    calcs = graph.calcs
+    seen, todo = set(), [len(calcs) - 1]
+    while todo:
+        q = todo.pop()
+        if q in seen:
+            continue
+        seen.add(q)
+        op, a, b, off, n = calcs[q]
+        srcs = [a] + ([b] if op <= A.MUL or op == A.HORNER else []) + (graph.parts[off:off + n] if op == A.HORNER else [])
+        todo += [s[1] for s in srcs if s[0] == A.INTERMEDIATE]
+    return seen
+
+
+def _oracle_graph(case, constants):
+    """the graph as oracle.quotient_gates reads it.  The C oracle evaluates every calculation in order, also those the result
+    never looks at; the unreached_* graphs keep their faults there, so an unreached calculation becomes a copy of the previous
+    value (the library never lowers it, halo2 never reads it)"""
+    g = case.graph
+    if not hasattr(case, "_oracle_calcs"):
+        seen = _reached(g)
+        case._oracle_calcs = [(op, a, b, g.parts[off:off + n]) if q in seen else (A.STORE, (A.PREVIOUS_VALUE, 0, 0), NO_B, [])
+                              for q, (op, a, b, off, n) in enumerate(g.calcs)]
+    return {"constants": np.ascontiguousarray(constants, dtype=np.uint8), "rotations": g.rotations, "calculations": case._oracle_calcs}
+
+
+def _blocks(k, ext_k, cosets):
+    """(rows per block, number of blocks, rows a unit rotation moves by)"""
+    return (1 << k, cosets, 1) if cosets else (1 << ext_k, 1, 1 << (ext_k - k))
+
+
+def expected_rows(O, case, inp, k, ext_k, cosets=0):
+    """the rows sg_quotient_gates_dev (cosets = 0: one block of 2^ext_k rows) or sg_quotient_gates_cosets_dev (cosets blocks of 2^k
+    rows, each a domain of its own) must give, by the C oracle"""
+    n, blocks, _ = _blocks(k, ext_k, cosets)
+    g = _oracle_graph(case, inp["constants"])
+    out = []
+    for b in range(blocks):
+        blk = lambda a: a[32 * n * b:32 * n * (b + 1)]
+        out.append(O.quotient_gates(blk(inp["previous"]), g, *[[blk(c) for c in inp[grp]] for grp in ("fixed", "advice", "instance")],
+                                    inp["challenges"], inp["beta"], inp["gamma"], inp["theta"], inp["y"], *((k, k) if cosets else (k, ext_k))))
+    return np.concatenate(out)
+
+
+MONT_INV = pow(1 << 256, -1, R)
+
+
+def definition_rows(case, inp, k, ext_k, cosets=0, rows=None, rotation_wraps_at_k=False):
+    """the same rows from halo2's definition in Python integers (oracle.pyref.eval_graph, row by row) under the Montgomery reading:
+    a word w stands for w 2^-256 mod r, the result v is the word v 2^256 mod r, and rotation rho reads row
+    (i + rho 2^(ext_k - k)) mod 2^ext_k of the block (coset-major: ext_k = k inside every block).  rows: only these.
+    rotation_wraps_at_k: the wrong reading (i + rho) mod 2^k within the row's 2^k, for showing that the cases tell the two apart"""
+    from oracle import pyref
+    n, blocks, step = _blocks(k, ext_k, cosets)
+    val = lambda words: [w * MONT_INV % R for w in _ints(words)]
+    cols = {A.FIXED: [val(c) for c in inp["fixed"]], A.ADVICE: [val(c) for c in inp["advice"]], A.INSTANCE: [val(c) for c in inp["instance"]]}
+    prev, consts, chal = val(inp["previous"]), val(inp["constants"]), val(inp["challenges"])
+    beta, gamma, theta, y = (val(inp[name])[0] for name in ("beta", "gamma", "theta", "y"))
+    graph = case.graph.as_dict(consts)
+    out = []
+    for i in (range(n * blocks) if rows is None else rows):
+        base, at = i - i % n, i % n
+        if rotation_wraps_at_k:
+            cell = lambda kind, index, rot: cols[kind][index][base + (at - at % (1 << k)) + (at + rot) % (1 << k)]
+        else:
+            cell = lambda kind, index, rot: cols[kind][index][base + (at + rot * step) % n]
+        out.append(pyref.eval_graph(graph, cell, chal, beta, gamma, theta, y, prev[i]) * (1 << 256) % R)
+    return _words(out)
+
+
+# ----------------------------------------------------------------------------- the device's arithmetic, in integers
+# What gates_kernel does to a row, value for value, where run_program above only keeps residues: a value is the integer its nine
+# limbs hold (csrc/bn254_f29.cuh).  A load is the word shifted left by 5 bits; a constant, and a load with kidx 1, is the
+# Montgomery product with 2^266; a product is (a b + m p) / 2^261 with m = -a b / p mod 2^261, below (Ba Bb / 170.7 + 1) p; a
+# subtraction adds K p = (2 << kidx) p first and must not go below zero (the top limb is 32 bits wide: a negative value is out by
+# 2^264); a reduction takes off q p with q estimated from the top limb.  The row's word is the product with 2^256, less p if
+# it is not below p.  Beside the value every tracked bound is re-derived as in run_program.
+R261 = 1 << 261
+_NEG_P_INV = -pow(R, -1, R261) % R261
+_RECIP = (1 << 40) // ((R >> 232) + 1)
+
+
+def mont261(a, b):
+    t = a * b
+    return (t + t * _NEG_P_INV % R261 * R) >> 261
+
+
+class DeviceModelFault(AssertionError):
+    pass
+
+
+def run_device_model(words, const_words, column_word, previous_word, skip_reduction=None, kidx_delta=0, check=True, products=None):
+    """the word the interpreter stores for one row.  const_words: the table's words; column_word(index, rotation) -> word.
+    check: every value stays below its tracked bound times p, no subtraction goes below zero and the stored word is canonical
+    (DeviceModelFault otherwise).  Two ways to break the program, for showing that the cases notice: skip_reduction = n turns
+    the n-th G_RED into a copy that keeps its operand's bound (the compiler letting a product through at a bound above 170;
+    products, a list, receives every product's Ba Bb); kidx_delta = -1 subtracts with half the K the compiler chose."""
+    n_slots, result_kind, result_index, ops = decode(words)
+    r266, r256 = (1 << 266) % R, (1 << 256) % R
+    consts = [mont261(w, r266) for w in const_words]
+    slot = [None] * n_slots
+
+    def get(kind, idx):
+        return (consts[idx], 2) if kind == CONST else slot[idx]
+
+    def minus(x, y, kidx):
+        v = x + (2 << max(0, kidx + kidx_delta)) * R - y
+        if v < 0:
+            if check:
+                raise DeviceModelFault(("a subtraction below zero", pc, kidx))
+            v += 1 << 264
+        return v
+
+    n_red = 0
+    for pc, o in enumerate(ops):
+        code, kidx = o["code"], o["kidx"]
+        if code == LOADCOL:
+            w = column_word(o["a"], o["b"])
+            r = (mont261(w, r266), 2) if kidx else (w << 5, 32)
+        elif code == LOADPREV:
+            r = previous_word << 5, 32
+        else:
+            (x, bx), (y, by) = get(o["ak"], o["a"]), get(o["bk"], o["b"])
+            if code == G_ADD:
+                r = x + y, bx + by
+            elif code == G_SUB:
+                r = minus(x, y, kidx), bx + (2 << kidx)
+            elif code == G_MUL:
+                r = mont261(x, y), 2
+            elif code == G_SQR:
+                r = mont261(x, x), 2
+            elif code == G_DBL:
+                r = 2 * x, 2 * bx
+            elif code == G_NEG:
+                r = minus(0, x, kidx), 2 << kidx
+            elif code == G_RED:
+                r = (x, bx) if n_red == skip_reduction else (x - (((x >> 232) * _RECIP) >> 40) * R, 2)
+                n_red += 1
+            else:
+                z, bz = get(kidx, o["c"])
+                r = mont261(x, y) + z, 2 + bz
+            if products is not None and code in (G_MUL, G_SQR, G_MULADD):
+                products.append(bx * (bx if code == G_SQR else by))
+        if check and not 0 <= r[0] <= r[1] * R:
+            raise DeviceModelFault(("a value at or above its bound", pc, OPCODES[code], r[1], r[0] / R))
+        slot[o["dst"]] = r
+    v = mont261(get(result_kind, result_index)[0], r256)
+    v = v - R if v >= R else v
+    if check and not 0 <= v < R:
+        raise DeviceModelFault(("the stored word is not canonical", v / R))
+    return v % (1 << 256)
