@@ -2,6 +2,7 @@
 // entry points (summa_gpu.hip holds the core).
 #include "abi_internal.h"
 #include "mst_entries.h"
+#include "mst_update_plan.h"
 
 using namespace sg;
 namespace {
@@ -427,6 +428,59 @@ int sg_mst_entries_dev(const uint8_t* name_bytes, const uint64_t* name_off, cons
   CHECK_HIP(mst_entries_launch(d, reinterpret_cast<const uint64_t*>(d + at_name_off), d + at_digits,
                                reinterpret_cast<const uint64_t*>(d + at_digit_off), n, rows, n_currencies, d_usernames, d_balances, s),
             "sg_mst_entries");
+  return SG_OK;
+}
+// New balances for m leaves of a built tree, in place (mst.rs:169-204 for many leaves at once; witness.hip has the kernels).
+// As above everything that can be wrong is found on the host first.  The geometry is the host's too (mst_update_plan.h): the
+// parents to redo on every level, one launch per level, stream order the only barrier between levels.  One work space of the
+// caller's stream holds the new balances as field elements (made from the digits by mst_balances_kernel), the digit offsets,
+// the leaf indices followed by the plan's lists, then the digits.
+int sg_mst_update_dev(const uint32_t* leaf_indices, const uint8_t* digit_bytes, const uint64_t* digit_off, size_t m, uint32_t depth,
+                      uint32_t n_currencies, const void* d_usernames, void* d_leaf_balances, void* d_node_hashes, void* d_node_balances,
+                      void* stream) {
+  if (!leaf_indices || !digit_bytes || !digit_off || !d_usernames || !d_leaf_balances || !d_node_hashes || !d_node_balances)
+    return fail(SG_ERR_INVALID, "sg_mst_update: null argument");
+  if (depth > 30 || n_currencies == 0 || n_currencies > 64) return fail(SG_ERR_INVALID, "sg_mst_update: bad size");
+  const uint32_t nc = n_currencies;
+  const size_t leaves = (size_t)1 << depth;
+  {
+    // the leaves' balances live twice, in their own array and as level 0 of the nodes': two allocations
+    const uintptr_t lo_a = (uintptr_t)d_leaf_balances, hi_a = lo_a + 32 * leaves * nc;
+    const uintptr_t lo_b = (uintptr_t)d_node_balances, hi_b = lo_b + 32 * (2 * leaves - 1) * nc;
+    if (lo_a < hi_b && lo_b < hi_a) return fail(SG_ERR_INVALID, "sg_mst_update: d_leaf_balances overlaps d_node_balances");
+  }
+  const std::string problem = mst_update_problem(leaf_indices, digit_bytes, digit_off, m, depth, nc);
+  if (!problem.empty()) return fail(SG_ERR_INVALID, ("sg_mst_update: " + problem).c_str());
+  const MstUpdatePlan plan = mst_update_plan(leaf_indices, m, depth);
+  std::vector<uint32_t> lists(leaf_indices, leaf_indices + m);   // the indices, then list 1 .. list depth: one copy
+  lists.insert(lists.end(), plan.nodes.begin(), plan.nodes.end());
+  const size_t fields = m * (size_t)nc, digit_len = digit_off[fields];
+  const size_t at_digit_off = 32 * fields, at_lists = at_digit_off + 8 * (fields + 1), at_digits = at_lists + 4 * lists.size();
+  LOCKED_CTX();
+  hipStream_t s = pick_stream(stream);
+  CHECK_HIP(g_ctx->witness.init(g_ctx->stream), "sg_mst_update: Poseidon table");
+  uint8_t* d = nullptr;
+  CHECK_HIP(scratch_for(s, 12, at_digits + digit_len, &d), "sg_mst_update: work space");
+  CHECK_HIP(hipMemcpyAsync(d + at_digit_off, digit_off, 8 * (fields + 1), hipMemcpyHostToDevice, s), "sg_mst_update: digit offsets");
+  CHECK_HIP(hipMemcpyAsync(d + at_lists, lists.data(), 4 * lists.size(), hipMemcpyHostToDevice, s), "sg_mst_update: lists");
+  CHECK_HIP(hipMemcpyAsync(d + at_digits, digit_bytes, digit_len, hipMemcpyHostToDevice, s), "sg_mst_update: digits");
+  fp_words* new_bal = reinterpret_cast<fp_words*>(d);
+  const uint32_t* d_lists = reinterpret_cast<const uint32_t*>(d + at_lists);
+  CHECK_HIP(mst_balances_launch(d + at_digits, reinterpret_cast<const uint64_t*>(d + at_digit_off), fields, new_bal, s),
+            "sg_mst_update: balances");
+  fp_words* h = static_cast<fp_words*>(d_node_hashes);
+  fp_words* b = static_cast<fp_words*>(d_node_balances);
+  CHECK_HIP(g_ctx->witness.update_leaves(d_lists, new_bal, m, nc, static_cast<const fp_words*>(d_usernames),
+                                         static_cast<fp_words*>(d_leaf_balances), h, b, s),
+            "sg_mst_update: leaves");
+  size_t child = 0;                                            // first node of level l - 1 in the level-major arrays
+  for (uint32_t l = 1; l <= depth; l++) {
+    const size_t parent = child + (leaves >> (l - 1));
+    CHECK_HIP(g_ctx->witness.update_level(d_lists + m + plan.offset[l - 1], plan.count(l), h + child, b + child * nc, nc, h + parent,
+                                          b + parent * nc, s),
+              "sg_mst_update: level");
+    child = parent;
+  }
   return SG_OK;
 }
 

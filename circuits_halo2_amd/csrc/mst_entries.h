@@ -46,15 +46,9 @@ SG_HD void mst_decimal_words(const uint8_t* p, size_t len, uint32_t out[8]) {
   f29_to_words(f29_reduce_with<Fr29>(acc, Fr29::r517), out);
 }
 
-// What sg_mst_entries_dev refuses before it touches the device: "" if the four host buffers describe n names and n * nc
-// balance fields, else what is wrong with them (the lowest offending balance field by its index).
-inline std::string mst_entries_problem(const uint64_t* name_off, const uint8_t* digit_bytes, const uint64_t* digit_off, size_t n,
-                                       uint32_t nc) {
-  if (name_off[0] != 0) return "name_off[0] is not 0";
-  for (size_t i = 0; i < n; i++) {
-    if (name_off[i + 1] < name_off[i]) return "name_off decreases at entry " + std::to_string(i);
-  }
-  const size_t fields = n * (size_t)nc;
+// "" if digit_bytes / digit_off describe `fields` decimal balance fields, else what is wrong with them (the lowest offending
+// field by its index).  On its own for sg_mst_update_dev, which takes balances without names (mst_update_plan.h).
+inline std::string mst_digit_fields_problem(const uint8_t* digit_bytes, const uint64_t* digit_off, size_t fields) {
   if (digit_off[0] != 0) return "digit_off[0] is not 0";
   for (size_t j = 0; j < fields; j++) {
     if (digit_off[j + 1] < digit_off[j]) return "digit_off decreases at field " + std::to_string(j);
@@ -67,6 +61,16 @@ inline std::string mst_entries_problem(const uint64_t* name_off, const uint8_t* 
   }
   return "";
 }
+// What sg_mst_entries_dev refuses before it touches the device: "" if the four host buffers describe n names and n * nc
+// balance fields, else what is wrong with them.
+inline std::string mst_entries_problem(const uint64_t* name_off, const uint8_t* digit_bytes, const uint64_t* digit_off, size_t n,
+                                       uint32_t nc) {
+  if (name_off[0] != 0) return "name_off[0] is not 0";
+  for (size_t i = 0; i < n; i++) {
+    if (name_off[i + 1] < name_off[i]) return "name_off decreases at entry " + std::to_string(i);
+  }
+  return mst_digit_fields_problem(digit_bytes, digit_off, n * (size_t)nc);
+}
 
 #if defined(__HIPCC__)
 // d_users[i] = Entry::new's username of name i, d_balances[i * nc + c] its balances, i < n; rows n .. rows of both are the
@@ -74,6 +78,9 @@ inline std::string mst_entries_problem(const uint64_t* name_off, const uint8_t* 
 hipError_t mst_entries_launch(const uint8_t* d_name_bytes, const uint64_t* d_name_off, const uint8_t* d_digit_bytes,
                               const uint64_t* d_digit_off, size_t n, size_t rows, uint32_t nc, void* d_users, void* d_balances,
                               hipStream_t stream);
+// the balances alone, no padding rows: d_balances[j] = field j, j < fields (sg_mst_update_dev's new balances)
+hipError_t mst_balances_launch(const uint8_t* d_digit_bytes, const uint64_t* d_digit_off, size_t fields, void* d_balances,
+                               hipStream_t stream);
 #endif
 
 }  // namespace sg

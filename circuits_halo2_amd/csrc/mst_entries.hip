@@ -64,5 +64,12 @@ hipError_t mst_entries_launch(const uint8_t* d_name_bytes, const uint64_t* d_nam
       d_digit_bytes, d_digit_off, (uint64_t)n * nc, total, static_cast<fp_words*>(d_balances));
   return hipGetLastError();
 }
+hipError_t mst_balances_launch(const uint8_t* d_digit_bytes, const uint64_t* d_digit_off, size_t fields, void* d_balances,
+                               hipStream_t stream) {
+  if (!fields) return hipSuccess;
+  mst_balances_kernel<<<(unsigned)((fields + MST_ENTRIES_BLOCK - 1) / MST_ENTRIES_BLOCK), MST_ENTRIES_BLOCK, 0, stream>>>(
+      d_digit_bytes, d_digit_off, (uint64_t)fields, (uint64_t)fields, static_cast<fp_words*>(d_balances));
+  return hipGetLastError();
+}
 
 }  // namespace sg

@@ -145,6 +145,62 @@ __global__ void __launch_bounds__(128) mst_level_kernel(const fp_words* __restri
   store_hat_w(hashes + p, s0);
 }
 
+// ------------------------------------------------------------------ in-place update (sg_mst_update_dev)
+// New balances for m leaves of a built tree, then every level above them for the listed parents only (mst_update_plan.h makes
+// the lists on the host).  One launch per level in stream order: a launch reads level l - 1 and writes level l, rows of one
+// allocation in disjoint ranges, so no thread writes a row another thread of its launch reads.
+// leaf i = index[j], j < m: its balances new_bal[j * nc ..] (Montgomery words) go to the leaves' own array and to the level-0
+// rows of the node balances; its hash is mst_leaves_kernel's.  The indices are distinct: one writer per row.
+__global__ void __launch_bounds__(128) mst_update_leaves_kernel(const uint32_t* __restrict__ index,
+                                                                const fp_words* __restrict__ new_bal, uint32_t m, uint32_t nc,
+                                                                const fp_words* __restrict__ users,
+                                                                const PoseidonTable* __restrict__ table, fp_words* __restrict__ leaf_bal,
+                                                                fp_words* __restrict__ hashes, fp_words* __restrict__ node_bal) {
+  side_kernel_prio();
+  __shared__ LdsTable tab;
+  stage_table(table, &tab);
+  uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= m) return;
+  const uint32_t i = index[j];
+  f29 s0 = f29_zero(), s1 = capacity_element(nc + 1);
+  s0 = f29_add(s0, load_hat_w(users + i));
+  poseidon_permute(s0, s1, &tab);
+  for (uint32_t c = 0; c < nc; c++) {
+    uint32_t w[8];
+    fp_words_load(new_bal + (size_t)j * nc + c, w);
+    fp_words_store(leaf_bal + (size_t)i * nc + c, w);
+    fp_words_store(node_bal + (size_t)i * nc + c, w);
+    s0 = f29_add(s0, f29_words_to_r261<P>(w));
+    poseidon_permute(s0, s1, &tab);
+  }
+  store_hat_w(hashes + i, s0);
+}
+// mst_level_kernel for the parents p = list[t], t < count, alone
+__global__ void __launch_bounds__(128) mst_update_level_kernel(const uint32_t* __restrict__ list, uint32_t count,
+                                                               const fp_words* __restrict__ child_hash,
+                                                               const fp_words* __restrict__ child_bal, uint32_t nc,
+                                                               const PoseidonTable* __restrict__ table, fp_words* __restrict__ hashes,
+                                                               fp_words* __restrict__ bal) {
+  side_kernel_prio();
+  __shared__ LdsTable tab;
+  stage_table(table, &tab);
+  uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= count) return;
+  const uint32_t p = list[t];
+  f29 s0 = f29_zero(), s1 = capacity_element(nc + 2);
+  for (uint32_t c = 0; c < nc; c++) {
+    f29 b = f29_add(load_hat_w(child_bal + (size_t)(2 * p) * nc + c), load_hat_w(child_bal + (size_t)(2 * p + 1) * nc + c));
+    store_hat_w(bal + (size_t)p * nc + c, b);          // canonical sum
+    s0 = f29_add(s0, b);                                // < 2 + 4
+    poseidon_permute(s0, s1, &tab);
+  }
+  s0 = f29_add(s0, load_hat_w(child_hash + 2 * p));
+  poseidon_permute(s0, s1, &tab);
+  s0 = f29_add(s0, load_hat_w(child_hash + 2 * p + 1));
+  poseidon_permute(s0, s1, &tab);
+  store_hat_w(hashes + p, s0);
+}
+
 // ------------------------------------------------------------------ circuit witness (advice columns) on the device
 // `MstInclusionCircuit::synthesize` [REF zk_prover/src/circuits/merkle_sum_tree.rs:228-520] for a user of a device-resident
 // Merkle sum tree: the three advice columns of the inclusion circuit in the reference's own floor plan.  The floor plan
@@ -330,6 +386,21 @@ hipError_t WitnessEngine::level(const fp_words* child_hash, const fp_words* chil
   if (!m) return hipSuccess;
   mst_level_kernel<<<(unsigned)((m + 127) / 128), 128, 0, stream>>>(child_hash, child_bal, (uint32_t)m, nc,
                                                                    static_cast<const PoseidonTable*>(table_), hashes, bal);
+  return hipGetLastError();
+}
+hipError_t WitnessEngine::update_leaves(const uint32_t* d_index, const fp_words* new_bal, size_t m, uint32_t nc, const fp_words* users,
+                                        fp_words* leaf_bal, fp_words* hashes, fp_words* node_bal, hipStream_t stream) {
+  if (!m) return hipSuccess;
+  mst_update_leaves_kernel<<<(unsigned)((m + 127) / 128), 128, 0, stream>>>(d_index, new_bal, (uint32_t)m, nc, users,
+                                                                           static_cast<const PoseidonTable*>(table_), leaf_bal,
+                                                                           hashes, node_bal);
+  return hipGetLastError();
+}
+hipError_t WitnessEngine::update_level(const uint32_t* d_list, size_t count, const fp_words* child_hash, const fp_words* child_bal,
+                                       uint32_t nc, fp_words* hashes, fp_words* bal, hipStream_t stream) {
+  if (!count) return hipSuccess;
+  mst_update_level_kernel<<<(unsigned)((count + 127) / 128), 128, 0, stream>>>(d_list, (uint32_t)count, child_hash, child_bal, nc,
+                                                                              static_cast<const PoseidonTable*>(table_), hashes, bal);
   return hipGetLastError();
 }
 

@@ -5,7 +5,8 @@ utils/csv_parser.rs, utils/operation_helpers.rs:10-12) with the hashing on the G
 Host logic kept here: CSV parsing, keccak256(username) -> field element, decimal balances ->
 field elements, zero-entry padding to 2^depth, Merkle-proof extraction (tree.rs:85-137).
 DeviceMerkleSumTree.from_entries / from_csv leave only the CSV parsing here: names and decimal balances
-become field elements on the device (sg_mst_entries_dev) and the tree stays in HBM.
+become field elements on the device (sg_mst_entries_dev) and the tree stays in HBM; DeviceMerkleSumTree.update_leaf /
+update_leaves / update_leaves_at change balances there in place (sg_mst_update_dev).
 """
 from __future__ import annotations
 
@@ -407,6 +408,12 @@ def pack_entries(entries, n_currencies: int):
         raise ValueError("Invalid balance")
     name_off = np.zeros(len(names) + 1, dtype=np.uint64)
     np.cumsum(np.fromiter(map(len, names), dtype=np.uint64, count=len(names)), out=name_off[1:])
+    return (np.frombuffer(b"".join(names), dtype=np.uint8), name_off) + pack_balances(flat)
+
+
+def pack_balances(flat):
+    """non-negative integers -> (digit_bytes, digit_off): `str(int)` back to back with len(flat) + 1 offsets, the balance half
+    of sg_mst_entries_dev's host buffers and all of sg_mst_update_dev's"""
     # the balances in one string with a comma between them: a field ends where a comma stood, less the commas before it
     text = np.frombuffer(",".join(map(str, flat)).encode(), dtype=np.uint8)
     comma = text == ord(",")
@@ -415,7 +422,7 @@ def pack_entries(entries, n_currencies: int):
     if flat:
         digit_off[1:-1] = ends - np.arange(ends.size)
         digit_off[-1] = text.size - ends.size
-    return np.frombuffer(b"".join(names), dtype=np.uint8), name_off, text[~comma], digit_off
+    return text[~comma], digit_off
 
 
 class DeviceMerkleSumTree:
@@ -428,9 +435,14 @@ class DeviceMerkleSumTree:
     `from_entries`, `from_csv` and `from_csv_sorted` build the same tree from what an exchange has, usernames and
     integer balances: the leaves' field elements are made on the device (sg_mst_entries_dev) and nothing comes back.  Such
     a tree also knows its entries by name -- `entries`, `get_entry`, `index_of_username`, `cryptocurrencies`, `is_sorted`, and
-    the `entry` of a Merkle proof carries the name, as MerkleSumTree's do; after the plain constructor `entries` is None."""
+    the `entry` of a Merkle proof carries the name, as MerkleSumTree's do; after the plain constructor `entries` is None.
+
+    `update_leaf`, `update_leaves` and `update_leaves_at` change balances in place (sg_mst_update_dev): the leaves and the nodes
+    above them are re-hashed on the device, in the arrays the tree was built from (`d_balances` of the plain constructor is
+    written too), and nothing comes back but the root when it is next asked for."""
 
     entries = None            # [(name, balances)] padded with (None, [0] * n_currencies): trees built from entries only
+    _name_index = None        # {name: first index}, made by the first update_leaves
     is_sorted = False
     cryptocurrencies = ()
 
@@ -508,6 +520,64 @@ class DeviceMerkleSumTree:
         if self.entries is None:
             raise KeyError("Username not found")
         return MerkleSumTree.index_of_username(self, username)
+
+    def update_leaf(self, username: str, new_balances):
+        """mst.rs:169-204: new balances for one user; the leaf and its `depth` ancestors are re-hashed in place on the device.
+        Returns the new root (hash, balances)."""
+        return self.update_leaves([(username, new_balances)])
+
+    def update_leaves(self, updates):
+        """`update_leaf` for every (username, [balances]) of `updates` as one device call (sg_mst_update_dev): the leaves, then
+        the distinct ancestors level by level.  A username that appears twice keeps its last balances, which is what the
+        updates applied one after another leave.  Everything is checked first: a refused batch leaves the tree as it was."""
+        if self.entries is None:
+            raise KeyError("Username not found")
+        if self._name_index is None:      # names never change: the first index of each, as index_of_username finds it
+            self._name_index = {}
+            for i, (name, _) in enumerate(self.entries):
+                if name is not None:
+                    self._name_index.setdefault(name, i)
+        indices = []
+        for name, _ in updates:
+            if name not in self._name_index:
+                raise KeyError("Username not found")
+            indices.append(self._name_index[name])
+        return self.update_leaves_at(indices, [bal for _, bal in updates])
+
+    def update_leaves_at(self, indices, balances):
+        """the same by leaf index: `balances[j]` are the new balances of leaf `indices[j]`, padded rows and the leaves of a tree
+        built from field elements included.  A repeated index keeps its last balances."""
+        indices, balances = list(indices), list(balances)
+        if len(indices) != len(balances):
+            raise ValueError("as many balance rows as indices expected")
+        nc = self.n_currencies
+        if not indices:
+            return self.root()
+        if min(indices) < 0 or max(indices) >= (1 << self.depth):
+            raise IndexError("Index out of bounds")
+        if any(len(bal) != nc for bal in balances):
+            raise ValueError("wrong number of balances")
+        if min(map(min, balances)) < 0:
+            raise ValueError("Invalid balance")
+        last = dict(zip(indices, balances))                   # a repeated index keeps its last row
+        order = sorted(last)
+        flat = [int(b) for i in order for b in last[i]]
+        digit_bytes, digit_off = pack_balances(flat)
+        self._update_dev(np.array(order, dtype=np.uint32), digit_bytes, digit_off)
+        self._root = None
+        if self.entries is not None:
+            for j, i in enumerate(order):
+                self.entries[i] = (self.entries[i][0], flat[nc * j:nc * j + nc])
+        return self.root()
+
+    def _update_dev(self, indices, digit_bytes, digit_off):
+        """sg_mst_update_dev over the tree's four arrays, on the current stream; complete when it returns, for the
+        constructor's reason -- and no proof may be reading the tree from another stream while it runs"""
+        import torch
+        ffi.check(ffi.lib().sg_mst_update_dev(ffi.ptr(indices), ffi.ptr(digit_bytes), ffi.ptr(digit_off), indices.size, self.depth,
+                                              self.n_currencies, ffi.dev_ptr(self.d_users), ffi.dev_ptr(self.d_bals),
+                                              ffi.dev_ptr(self.d_h), ffi.dev_ptr(self.d_b), ffi.current_stream_ptr()))
+        torch.cuda.current_stream().synchronize()
 
     @staticmethod
     def _entry_fields(name, bal):

@@ -558,6 +558,22 @@ int sg_mst_build_dev(const void* d_usernames, const void* d_leaf_balances, uint3
  * (sg_host_register) are read in stream order and stay as they are until the stream has passed the call. */
 int sg_mst_entries_dev(const uint8_t* name_bytes, const uint64_t* name_off, const uint8_t* digit_bytes, const uint64_t* digit_off,
                        size_t n, size_t rows, uint32_t n_currencies, void* d_usernames, void* d_balances, void* stream);
+/* MerkleSumTree::update_leaf (mst.rs:169-204) for m leaves at once, in place on the device: new balances for the leaves
+ * leaf_indices[0 .. m) of a tree sg_mst_build_dev built from d_usernames / d_leaf_balances into d_node_hashes / d_node_balances.
+ * HOST inputs: the indices (strictly increasing, each below 2^depth) and their m * n_currencies balances as decimal fields,
+ * field j * nc + c the balance c of leaf_indices[j], laid out as in sg_mst_entries_dev.  The balances become field elements on
+ * the device and replace the leaves' rows of d_leaf_balances and of level 0 of d_node_balances; the m leaf hashes and, level by
+ * level, every node above an updated leaf (at most m per level, one launch per level) are recomputed.  Afterwards the four
+ * arrays hold, byte for byte, what a fresh sg_mst_entries_dev + sg_mst_build_dev of the changed entries would.  Usernames stay.
+ * SG_ERR_INVALID, found on the host before any device call: a null pointer; depth > 30; n_currencies outside 1..64;
+ * d_leaf_balances overlapping d_node_balances; m == 0 or m > 2^depth; an index out of range; indices that do not strictly
+ * increase (sg_last_error names the first such position); digit offsets or fields sg_mst_entries_dev would refuse.
+ * Complete in stream order.  Pageable host buffers have been read when the call returns; page-locked ones (sg_host_register)
+ * are read in stream order and stay as they are until the stream has passed the call.  The tree is changed level by level:
+ * while the call's stream passes it, no other stream may have a reader of the tree in flight. */
+int sg_mst_update_dev(const uint32_t* leaf_indices, const uint8_t* digit_bytes, const uint64_t* digit_off, size_t m, uint32_t depth,
+                      uint32_t n_currencies, const void* d_usernames, void* d_leaf_balances, void* d_node_hashes,
+                      void* d_node_balances, void* stream);
 /* `MstInclusionCircuit::synthesize` (zk_prover/src/circuits/merkle_sum_tree.rs:228-520) on the device, for `n_users`
  * users of a tree built by sg_mst_build_dev: the three advice columns in the reference's own floor plan.  The floor plan
  * is a function of <LEVELS, N_CURRENCIES, N_BYTES> only and arrives as `d_program` (device memory): n_items x 5 u32

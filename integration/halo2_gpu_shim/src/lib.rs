@@ -122,6 +122,22 @@ extern "C" {
         d_status: *mut c_void,
         stream: *mut c_void,
     ) -> c_int;
+    // `MerkleSumTree::update_leaf` for m leaves of a device-resident tree at once, in place: host indices (strictly increasing)
+    // and decimal balances in, the leaves and every node above them redone on the device, one launch per level.  No other
+    // stream may read the tree while this call's stream passes it
+    pub fn sg_mst_update_dev(
+        leaf_indices: *const u32,
+        digit_bytes: *const u8,
+        digit_off: *const u64,
+        m: size_t,
+        depth: u32,
+        n_currencies: u32,
+        d_usernames: *const c_void,
+        d_leaf_balances: *mut c_void,
+        d_node_hashes: *mut c_void,
+        d_node_balances: *mut c_void,
+        stream: *mut c_void,
+    ) -> c_int;
 }
 
 /// `sg_graph` of include/summa_gpu.h: the plain-struct image of halo2's `GraphEvaluator` (what `pk.ev` holds)
