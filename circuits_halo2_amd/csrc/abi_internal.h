@@ -1,5 +1,5 @@
-// What the translation units of the C ABI share (summa_gpu.hip: the core; abi_msm / abi_ntt / abi_poly / abi_quotient.hip: the
-// entry points by family).  Private to csrc/: the public interface is include/summa_gpu.h alone.
+// What the translation units of the C ABI share (summa_gpu.hip: the core; abi_msm / abi_ntt / abi_poly / abi_quotient / abi_mst.hip:
+// the entry points by family).  Private to csrc/: the public interface is include/summa_gpu.h alone.
 #pragma once
 #include "../../include/summa_gpu.h"
 

@@ -1,8 +1,6 @@
-// C ABI, quotient family: sg_quotient_*, the gate-program cache, sg_gates_program_*, and the circuit's keygen and witness
-// entry points (summa_gpu.hip holds the core).
+// C ABI, quotient family: sg_quotient_*, the gate-program cache and sg_gates_program_* (summa_gpu.hip holds the core; the
+// circuit's keygen and witness entry points are abi_mst.hip's).
 #include "abi_internal.h"
-#include "mst_entries.h"
-#include "mst_update_plan.h"
 
 using namespace sg;
 namespace {
@@ -318,191 +316,6 @@ int sg_gates_program_words(const sg_graph* graph, uint32_t n_fixed, uint32_t n_a
   for (const GateOp& o : prog.ops) { w.push_back(o.w0); w.push_back(o.dst); w.push_back(o.a); w.push_back(o.b); }
   *n_words_out = (uint32_t)w.size();
   if (cap_words >= w.size()) std::memcpy(words_out, w.data(), 4 * w.size());
-  return SG_OK;
-}
-
-// ------------------------------------------------------------------ keygen's circuit side
-// What `keygen_vk` / `keygen_pk` need of `MstInclusionCircuit::synthesize` over 2^k rows [REF zk_prover/src/circuits/
-// merkle_sum_tree.rs:228-520 replayed over halo2's SimpleFloorPlanner: include/summa_circuit.hpp]: the 11 fixed columns (round
-// constants, range table, compressed selectors, constants) and the 6 permutation columns sigma_c[row] = the label delta^c' omega^row'
-// of the cell (c, row) is copy-constrained to.  Host only (no device needed); Montgomery words, column-major.
-int sg_mst_inclusion_keygen_columns(uint32_t k, uint32_t levels, uint32_t n_currencies, uint32_t n_bytes, uint8_t* fixed_out,
-                                    uint8_t* sigma_out, uint32_t* rows_used_out) {
-  if (!fixed_out || !sigma_out || k < 4 || k > 25 || levels == 0 || levels > 48 || n_currencies == 0 || n_currencies > 16 || n_bytes == 0 ||
-      n_bytes > 31)
-    return fail(SG_ERR_INVALID, "sg_mst_inclusion_keygen_columns: bad argument");
-  try {
-    using summa::prover::Fr;
-    const summa::circuit::FloorPlan fp(k, levels, n_currencies, n_bytes);
-    const size_t n = (size_t)1 << k;
-    if (fp.rows_used + summa::circuit::BLINDING_FACTORS + 1 > n) return fail(SG_ERR_INVALID, "sg_mst_inclusion_keygen_columns: not enough rows");
-    static const uint8_t root_2_28[32] = {0x03, 0xdd, 0xb9, 0xf5, 0x16, 0x6d, 0x18, 0xb7, 0x98, 0x86, 0x5e, 0xa9, 0x3d, 0xd3, 0x1f, 0x74,
-                                          0x32, 0x15, 0xcf, 0x6d, 0xd3, 0x93, 0x29, 0xc8, 0xd3, 0x4f, 0x1e, 0xd9, 0x60, 0xc3, 0x7c, 0x9c};
-    Fr omega = Fr::from_be_bytes_reduced(root_2_28);
-    for (uint32_t i = k; i < 28; i++) omega = omega * omega;
-    for (uint32_t c = 0; c < summa::circuit::NUM_FIXED; c++) std::memcpy(fixed_out + 32 * n * c, fp.fixed[c].data(), 32 * n);
-    const auto sigma = fp.sigma(omega);
-    for (uint32_t c = 0; c < summa::circuit::NUM_PERM; c++) std::memcpy(sigma_out + 32 * n * c, sigma[c].data(), 32 * n);
-    if (rows_used_out) *rows_used_out = fp.rows_used;
-  } catch (const std::exception& ex) {
-    return fail(SG_ERR_INVALID, (std::string("sg_mst_inclusion_keygen_columns: ") + ex.what()).c_str());
-  }
-  return SG_OK;
-}
-
-// ------------------------------------------------------------------ witness side (Merkle sum tree)
-int sg_mst_leaves_dev(const void* d_usernames, const void* d_balances, size_t n, uint32_t n_currencies,
-                      void* d_hashes, void* stream) {
-  if (n && (!d_usernames || !d_balances || !d_hashes)) return fail(SG_ERR_INVALID, "sg_mst_leaves: null argument");
-  if (n_currencies == 0 || n_currencies > 64 || n >= (1ull << 32)) return fail(SG_ERR_INVALID, "sg_mst_leaves: bad size");
-  LOCKED_CTX();
-  hipStream_t s = pick_stream(stream);
-  hipError_t e = g_ctx->witness.init(g_ctx->stream);
-  if (e == hipSuccess)
-    e = g_ctx->witness.leaves(static_cast<const fp_words*>(d_usernames), static_cast<const fp_words*>(d_balances), n,
-                              n_currencies, static_cast<fp_words*>(d_hashes), s);
-  if (e != hipSuccess) return hip_fail("mst leaves", e);
-  return SG_OK;
-}
-int sg_mst_level_dev(const void* d_child_hashes, const void* d_child_balances, size_t n_parents, uint32_t n_currencies,
-                     void* d_hashes, void* d_balances, void* stream) {
-  if (n_parents && (!d_child_hashes || !d_child_balances || !d_hashes || !d_balances))
-    return fail(SG_ERR_INVALID, "sg_mst_level: null argument");
-  if (n_currencies == 0 || n_currencies > 64 || n_parents >= (1ull << 31)) return fail(SG_ERR_INVALID, "sg_mst_level: bad size");
-  LOCKED_CTX();
-  hipError_t e = g_ctx->witness.init(g_ctx->stream);
-  if (e == hipSuccess)
-    e = g_ctx->witness.level(static_cast<const fp_words*>(d_child_hashes), static_cast<const fp_words*>(d_child_balances),
-                             n_parents, n_currencies, static_cast<fp_words*>(d_hashes),
-                             static_cast<fp_words*>(d_balances), pick_stream(stream));
-  if (e != hipSuccess) return hip_fail("mst level", e);
-  return SG_OK;
-}
-// whole tree: node arrays are level-major (2^depth leaves, then 2^(depth-1) parents, ..., the root)
-int sg_mst_build_dev(const void* d_usernames, const void* d_leaf_balances, uint32_t depth, uint32_t n_currencies,
-                     void* d_node_hashes, void* d_node_balances, void* stream) {
-  if (!d_usernames || !d_leaf_balances || !d_node_hashes || !d_node_balances || depth > 30)
-    return fail(SG_ERR_INVALID, "sg_mst_build: bad argument");
-  const size_t n = (size_t)1 << depth;
-  uint8_t* h = static_cast<uint8_t*>(d_node_hashes);
-  uint8_t* b = static_cast<uint8_t*>(d_node_balances);
-  int rc = sg_mst_leaves_dev(d_usernames, d_leaf_balances, n, n_currencies, h, stream);
-  if (rc != SG_OK) return rc;
-  {
-    LOCKED_CTX();
-    CHECK_HIP(hipMemcpyAsync(b, d_leaf_balances, n * n_currencies * 32, hipMemcpyDeviceToDevice, pick_stream(stream)),
-              "mst balances");
-  }
-  size_t off = 0;
-  for (size_t m = n >> 1; m >= 1; m >>= 1) {
-    const size_t child = off, parent = off + 2 * m;
-    rc = sg_mst_level_dev(h + 32 * child, b + 32 * child * n_currencies, m, n_currencies, h + 32 * parent,
-                          b + 32 * parent * n_currencies, stream);
-    if (rc != SG_OK) return rc;
-    off = parent;
-  }
-  return SG_OK;
-}
-// Entry::new for a whole snapshot (mst_entries.hip).  Everything that can be wrong with the host buffers is found here, before
-// the device is touched: the kernels trust their offsets.  The four buffers travel in one work space of the caller's stream
-// (names, digits, then the two offset arrays from an 8-byte boundary on), so calls on one stream reuse it in stream order.
-int sg_mst_entries_dev(const uint8_t* name_bytes, const uint64_t* name_off, const uint8_t* digit_bytes, const uint64_t* digit_off,
-                       size_t n, size_t rows, uint32_t n_currencies, void* d_usernames, void* d_balances, void* stream) {
-  if (!name_bytes || !name_off || !digit_bytes || !digit_off || !d_usernames || !d_balances)
-    return fail(SG_ERR_INVALID, "sg_mst_entries: null argument");
-  if (n == 0 || rows < n || rows >= (1ull << 32) || n_currencies == 0 || n_currencies > 64)
-    return fail(SG_ERR_INVALID, "sg_mst_entries: bad size");
-  const std::string problem = mst_entries_problem(name_off, digit_bytes, digit_off, n, n_currencies);
-  if (!problem.empty()) return fail(SG_ERR_INVALID, ("sg_mst_entries: " + problem).c_str());
-  const size_t fields = n * (size_t)n_currencies;
-  const size_t name_len = name_off[n], digit_len = digit_off[fields];
-  const size_t at_digits = name_len, at_name_off = (name_len + digit_len + 7) & ~(size_t)7, at_digit_off = at_name_off + 8 * (n + 1);
-  LOCKED_CTX();
-  hipStream_t s = pick_stream(stream);
-  uint8_t* d = nullptr;
-  CHECK_HIP(scratch_for(s, 11, at_digit_off + 8 * (fields + 1), &d), "sg_mst_entries: work space");
-  if (name_len) CHECK_HIP(hipMemcpyAsync(d, name_bytes, name_len, hipMemcpyHostToDevice, s), "sg_mst_entries: names");
-  CHECK_HIP(hipMemcpyAsync(d + at_digits, digit_bytes, digit_len, hipMemcpyHostToDevice, s), "sg_mst_entries: digits");
-  CHECK_HIP(hipMemcpyAsync(d + at_name_off, name_off, 8 * (n + 1), hipMemcpyHostToDevice, s), "sg_mst_entries: name offsets");
-  CHECK_HIP(hipMemcpyAsync(d + at_digit_off, digit_off, 8 * (fields + 1), hipMemcpyHostToDevice, s), "sg_mst_entries: digit offsets");
-  CHECK_HIP(mst_entries_launch(d, reinterpret_cast<const uint64_t*>(d + at_name_off), d + at_digits,
-                               reinterpret_cast<const uint64_t*>(d + at_digit_off), n, rows, n_currencies, d_usernames, d_balances, s),
-            "sg_mst_entries");
-  return SG_OK;
-}
-// New balances for m leaves of a built tree, in place (mst.rs:169-204 for many leaves at once; witness.hip has the kernels).
-// As above everything that can be wrong is found on the host first.  The geometry is the host's too (mst_update_plan.h): the
-// parents to redo on every level, one launch per level, stream order the only barrier between levels.  One work space of the
-// caller's stream holds the new balances as field elements (made from the digits by mst_balances_kernel), the digit offsets,
-// the leaf indices followed by the plan's lists, then the digits.
-int sg_mst_update_dev(const uint32_t* leaf_indices, const uint8_t* digit_bytes, const uint64_t* digit_off, size_t m, uint32_t depth,
-                      uint32_t n_currencies, const void* d_usernames, void* d_leaf_balances, void* d_node_hashes, void* d_node_balances,
-                      void* stream) {
-  if (!leaf_indices || !digit_bytes || !digit_off || !d_usernames || !d_leaf_balances || !d_node_hashes || !d_node_balances)
-    return fail(SG_ERR_INVALID, "sg_mst_update: null argument");
-  if (depth > 30 || n_currencies == 0 || n_currencies > 64) return fail(SG_ERR_INVALID, "sg_mst_update: bad size");
-  const uint32_t nc = n_currencies;
-  const size_t leaves = (size_t)1 << depth;
-  {
-    // the leaves' balances live twice, in their own array and as level 0 of the nodes': two allocations
-    const uintptr_t lo_a = (uintptr_t)d_leaf_balances, hi_a = lo_a + 32 * leaves * nc;
-    const uintptr_t lo_b = (uintptr_t)d_node_balances, hi_b = lo_b + 32 * (2 * leaves - 1) * nc;
-    if (lo_a < hi_b && lo_b < hi_a) return fail(SG_ERR_INVALID, "sg_mst_update: d_leaf_balances overlaps d_node_balances");
-  }
-  const std::string problem = mst_update_problem(leaf_indices, digit_bytes, digit_off, m, depth, nc);
-  if (!problem.empty()) return fail(SG_ERR_INVALID, ("sg_mst_update: " + problem).c_str());
-  const MstUpdatePlan plan = mst_update_plan(leaf_indices, m, depth);
-  std::vector<uint32_t> lists(leaf_indices, leaf_indices + m);   // the indices, then list 1 .. list depth: one copy
-  lists.insert(lists.end(), plan.nodes.begin(), plan.nodes.end());
-  const size_t fields = m * (size_t)nc, digit_len = digit_off[fields];
-  const size_t at_digit_off = 32 * fields, at_lists = at_digit_off + 8 * (fields + 1), at_digits = at_lists + 4 * lists.size();
-  LOCKED_CTX();
-  hipStream_t s = pick_stream(stream);
-  CHECK_HIP(g_ctx->witness.init(g_ctx->stream), "sg_mst_update: Poseidon table");
-  uint8_t* d = nullptr;
-  CHECK_HIP(scratch_for(s, 12, at_digits + digit_len, &d), "sg_mst_update: work space");
-  CHECK_HIP(hipMemcpyAsync(d + at_digit_off, digit_off, 8 * (fields + 1), hipMemcpyHostToDevice, s), "sg_mst_update: digit offsets");
-  CHECK_HIP(hipMemcpyAsync(d + at_lists, lists.data(), 4 * lists.size(), hipMemcpyHostToDevice, s), "sg_mst_update: lists");
-  CHECK_HIP(hipMemcpyAsync(d + at_digits, digit_bytes, digit_len, hipMemcpyHostToDevice, s), "sg_mst_update: digits");
-  fp_words* new_bal = reinterpret_cast<fp_words*>(d);
-  const uint32_t* d_lists = reinterpret_cast<const uint32_t*>(d + at_lists);
-  CHECK_HIP(mst_balances_launch(d + at_digits, reinterpret_cast<const uint64_t*>(d + at_digit_off), fields, new_bal, s),
-            "sg_mst_update: balances");
-  fp_words* h = static_cast<fp_words*>(d_node_hashes);
-  fp_words* b = static_cast<fp_words*>(d_node_balances);
-  CHECK_HIP(g_ctx->witness.update_leaves(d_lists, new_bal, m, nc, static_cast<const fp_words*>(d_usernames),
-                                         static_cast<fp_words*>(d_leaf_balances), h, b, s),
-            "sg_mst_update: leaves");
-  size_t child = 0;                                            // first node of level l - 1 in the level-major arrays
-  for (uint32_t l = 1; l <= depth; l++) {
-    const size_t parent = child + (leaves >> (l - 1));
-    CHECK_HIP(g_ctx->witness.update_level(d_lists + m + plan.offset[l - 1], plan.count(l), h + child, b + child * nc, nc, h + parent,
-                                          b + parent * nc, s),
-              "sg_mst_update: level");
-    child = parent;
-  }
-  return SG_OK;
-}
-
-// Circuit::synthesize on the device for users of a device-resident tree (witness.hip: the program is the floor plan)
-int sg_mst_inclusion_witness_dev(const void* d_program, uint32_t n_items, uint32_t n_absorbs, const void* d_usernames,
-                                 const void* d_node_hashes, const void* d_node_balances, uint32_t depth, uint32_t n_currencies,
-                                 const void* d_user_indices, uint32_t n_users, void* d_advice, uint64_t rows, void* stream) {
-  if (!d_program || !d_usernames || !d_node_hashes || !d_node_balances || !d_user_indices || !d_advice)
-    return fail(SG_ERR_INVALID, "sg_mst_inclusion_witness: null argument");
-  if (depth > 30 || n_currencies == 0 || n_currencies > 64 || rows == 0 || rows > (1ull << 28) || n_items > (1u << 24) || n_users > 65535)
-    return fail(SG_ERR_INVALID, "sg_mst_inclusion_witness: bad size");
-  LOCKED_CTX();
-  hipStream_t s = pick_stream(stream);
-  hipError_t e = g_ctx->witness.init(g_ctx->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(d_advice, 0, (size_t)n_users * 3 * rows * 32, s);
-  if (e == hipSuccess)
-    e = g_ctx->witness.inclusion_witness(static_cast<const uint32_t*>(d_program), n_items, n_absorbs,
-                                         static_cast<const fp_words*>(d_usernames), static_cast<const fp_words*>(d_node_hashes),
-                                         static_cast<const fp_words*>(d_node_balances), depth, n_currencies,
-                                         static_cast<const uint32_t*>(d_user_indices), n_users, static_cast<fp_words*>(d_advice),
-                                         (size_t)rows, s);
-  if (e != hipSuccess) return hip_fail("mst inclusion witness", e);
   return SG_OK;
 }
 

@@ -1,6 +1,6 @@
 // The leaves' inputs of a Merkle sum tree from what an exchange has -- usernames and decimal balances -- on the device: the
 // GPU counterpart of `Entry::new` over a whole snapshot (mst_entries.h has the arithmetic and the references).  Both
-// kernels trust their offsets: sg_mst_entries_dev (abi_quotient.hip) validates them on the host before it launches.
+// kernels trust their offsets: sg_mst_entries_dev (abi_mst.hip) validates them on the host before it launches.
 #include "mst_entries.h"
 
 #include "bn254_curve29.cuh"

@@ -13,6 +13,10 @@
 
 namespace sg {
 
+// The level-major node arrays of a tree of 2^depth leaves: the leaves, then the 2^(depth - 1) parents, .., the root.  The first
+// node of level `level` <= depth: 2^depth + .. + 2^(depth - level + 1) = 2^(depth + 1) - 2^(depth - level + 1); depth <= 62.
+inline uint64_t mst_level_first(uint32_t level, uint32_t depth) { return ((uint64_t)2 << depth) - ((uint64_t)2 << (depth - level)); }
+
 // For level l = 1 .. depth the distinct parents {index >> l} of the updated leaves, as node numbers within their level,
 // strictly increasing; the lists back to back in `nodes`, list l = nodes[offset[l - 1] .. offset[l]), offset[0] = 0.
 // At most m entries per list, all lists together fewer than 2^depth (the nodes above the leaves); the last list is {0}.

@@ -8,6 +8,7 @@
 // One thread per hash; 472-ish Fr products per permutation, so the kernels are VALU-bound.
 #include "witness.h"
 #include "host_wait.h"
+#include "mst_update_plan.h"
 #include "side_prio.cuh"
 
 #include "poseidon_constants.inc"
@@ -64,23 +65,28 @@ __device__ __forceinline__ void mix(f29& s0, f29& s1, const LdsTable* t) {
   s0 = a;
   s1 = b;
 }
+// the first half of round r: the constants, then the s-box on word 0 and, in a full round, on word 1
+template <bool FULL>
+__device__ __forceinline__ void add_constants_sbox(f29& s0, f29& s1, const LdsTable* t, uint32_t r) {
+  s0 = pow5(f29_add(s0, lds_f29(t->rc, 2 * r)));      // (<4 + <2)^5
+  s1 = f29_add(s1, lds_f29(t->rc, 2 * r + 1));        // < 4: a partial round enters mix with bound product 1*4
+  if (FULL) s1 = pow5(s1);
+}
+template <bool FULL>
+__device__ __forceinline__ void poseidon_round(f29& s0, f29& s1, const LdsTable* t, uint32_t r) {
+  add_constants_sbox<FULL>(s0, s1, t, r);
+  mix(s0, s1, t);
+}
 __device__ __forceinline__ void poseidon_permute(f29& s0, f29& s1, const LdsTable* t) {
   uint32_t r = 0;
-  for (int k = 0; k < 4; k++, r++) {
-    s0 = pow5(f29_add(s0, lds_f29(t->rc, 2 * r)));      // (<4 + <2)^5
-    s1 = pow5(f29_add(s1, lds_f29(t->rc, 2 * r + 1)));
-    mix(s0, s1, t);
-  }
-  for (int k = 0; k < 56; k++, r++) {
-    s0 = pow5(f29_add(s0, lds_f29(t->rc, 2 * r)));
-    s1 = f29_add(s1, lds_f29(t->rc, 2 * r + 1));        // < 4, enters mix with bound product 1*4
-    mix(s0, s1, t);
-  }
-  for (int k = 0; k < 4; k++, r++) {
-    s0 = pow5(f29_add(s0, lds_f29(t->rc, 2 * r)));
-    s1 = pow5(f29_add(s1, lds_f29(t->rc, 2 * r + 1)));
-    mix(s0, s1, t);
-  }
+  for (int k = 0; k < 4; k++, r++) poseidon_round<true>(s0, s1, t, r);
+  for (int k = 0; k < 56; k++, r++) poseidon_round<false>(s0, s1, t, r);
+  for (int k = 0; k < 4; k++, r++) poseidon_round<true>(s0, s1, t, r);
+}
+// the sponge's step at rate 1: a word into state[0], one permutation
+__device__ __forceinline__ void absorb(f29& s0, f29& s1, const f29& word, const LdsTable* t) {
+  s0 = f29_add(s0, word);
+  poseidon_permute(s0, s1, t);
 }
 __device__ __forceinline__ f29 load_hat_w(const fp_words* p) {
   uint32_t w[8];
@@ -103,101 +109,58 @@ __device__ __forceinline__ f29 capacity_element(uint32_t L) {
   return f29_mul<P>(f29_mul<P>(v, f29_const<P>(P::r517)), f29_const<P>(P::r266));
 }
 
-__global__ void __launch_bounds__(128) mst_leaves_kernel(const fp_words* __restrict__ users,
-                                                         const fp_words* __restrict__ balances, uint32_t n,
-                                                         uint32_t nc, const PoseidonTable* __restrict__ table,
-                                                         fp_words* __restrict__ hashes) {
-  side_kernel_prio();
-  __shared__ LdsTable tab;
-  stage_table(table, &tab);
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  f29 s0 = f29_zero(), s1 = capacity_element(nc + 1);
-  s0 = f29_add(s0, load_hat_w(users + i));
-  poseidon_permute(s0, s1, &tab);
-  for (uint32_t c = 0; c < nc; c++) {
-    s0 = f29_add(s0, load_hat_w(balances + (size_t)i * nc + c));
-    poseidon_permute(s0, s1, &tab);
-  }
-  store_hat_w(hashes + i, s0);
-}
-// parents p = 0..m-1 from children 2p, 2p+1
-__global__ void __launch_bounds__(128) mst_level_kernel(const fp_words* __restrict__ child_hash,
-                                                        const fp_words* __restrict__ child_bal, uint32_t m,
-                                                        uint32_t nc, const PoseidonTable* __restrict__ table,
-                                                        fp_words* __restrict__ hashes, fp_words* __restrict__ bal) {
-  side_kernel_prio();
-  __shared__ LdsTable tab;
-  stage_table(table, &tab);
-  uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= m) return;
-  f29 s0 = f29_zero(), s1 = capacity_element(nc + 2);
-  for (uint32_t c = 0; c < nc; c++) {
-    f29 b = f29_add(load_hat_w(child_bal + (size_t)(2 * p) * nc + c), load_hat_w(child_bal + (size_t)(2 * p + 1) * nc + c));
-    store_hat_w(bal + (size_t)p * nc + c, b);          // canonical sum
-    s0 = f29_add(s0, b);                                // < 2 + 4
-    poseidon_permute(s0, s1, &tab);
-  }
-  s0 = f29_add(s0, load_hat_w(child_hash + 2 * p));
-  poseidon_permute(s0, s1, &tab);
-  s0 = f29_add(s0, load_hat_w(child_hash + 2 * p + 1));
-  poseidon_permute(s0, s1, &tab);
-  store_hat_w(hashes + p, s0);
-}
-
-// ------------------------------------------------------------------ in-place update (sg_mst_update_dev)
-// New balances for m leaves of a built tree, then every level above them for the listed parents only (mst_update_plan.h makes
-// the lists on the host).  One launch per level in stream order: a launch reads level l - 1 and writes level l, rows of one
-// allocation in disjoint ranges, so no thread writes a row another thread of its launch reads.
-// leaf i = index[j], j < m: its balances new_bal[j * nc ..] (Montgomery words) go to the leaves' own array and to the level-0
-// rows of the node balances; its hash is mst_leaves_kernel's.  The indices are distinct: one writer per row.
-__global__ void __launch_bounds__(128) mst_update_leaves_kernel(const uint32_t* __restrict__ index,
-                                                                const fp_words* __restrict__ new_bal, uint32_t m, uint32_t nc,
-                                                                const fp_words* __restrict__ users,
-                                                                const PoseidonTable* __restrict__ table, fp_words* __restrict__ leaf_bal,
-                                                                fp_words* __restrict__ hashes, fp_words* __restrict__ node_bal) {
-  side_kernel_prio();
-  __shared__ LdsTable tab;
-  stage_table(table, &tab);
-  uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= m) return;
-  const uint32_t i = index[j];
-  f29 s0 = f29_zero(), s1 = capacity_element(nc + 1);
-  s0 = f29_add(s0, load_hat_w(users + i));
-  poseidon_permute(s0, s1, &tab);
-  for (uint32_t c = 0; c < nc; c++) {
-    uint32_t w[8];
-    fp_words_load(new_bal + (size_t)j * nc + c, w);
-    fp_words_store(leaf_bal + (size_t)i * nc + c, w);
-    fp_words_store(node_bal + (size_t)i * nc + c, w);
-    s0 = f29_add(s0, f29_words_to_r261<P>(w));
-    poseidon_permute(s0, s1, &tab);
-  }
-  store_hat_w(hashes + i, s0);
-}
-// mst_level_kernel for the parents p = list[t], t < count, alone
-__global__ void __launch_bounds__(128) mst_update_level_kernel(const uint32_t* __restrict__ list, uint32_t count,
-                                                               const fp_words* __restrict__ child_hash,
-                                                               const fp_words* __restrict__ child_bal, uint32_t nc,
-                                                               const PoseidonTable* __restrict__ table, fp_words* __restrict__ hashes,
-                                                               fp_words* __restrict__ bal) {
+// One leaf body and one parent body, each in two forms chosen at compile time.  Dense (sg_mst_build_dev): thread t does node t
+// of n.  Listed (sg_mst_update_dev, new balances for some leaves of a built tree in place): thread t does node list[t], for
+// the listed leaves and then, level by level, the listed parents only (mst_update_plan.h makes the lists on the host).  One
+// launch per level in stream order: a launch reads level l - 1 and writes level l, rows of one allocation in disjoint
+// ranges, so no thread writes a row another thread of its launch reads.  The numbers of a list are distinct: one writer per row.
+//
+// hashes[i] = H(users[i], the nc balances of row t of `balances`), i = t or list[t].  Listed, the balances (Montgomery words)
+// also go to row i of leaf_bal, the leaves' own array, and of node_bal, level 0 of the node balances.
+template <bool LISTED>
+__global__ void __launch_bounds__(128) mst_leaves_kernel(const uint32_t* __restrict__ list, const fp_words* __restrict__ users,
+                                                         const fp_words* __restrict__ balances, uint32_t n, uint32_t nc,
+                                                         const PoseidonTable* __restrict__ table, fp_words* __restrict__ hashes,
+                                                         fp_words* __restrict__ leaf_bal, fp_words* __restrict__ node_bal) {
   side_kernel_prio();
   __shared__ LdsTable tab;
   stage_table(table, &tab);
   uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= count) return;
-  const uint32_t p = list[t];
+  if (t >= n) return;
+  const uint32_t i = LISTED ? list[t] : t;
+  f29 s0 = f29_zero(), s1 = capacity_element(nc + 1);
+  absorb(s0, s1, load_hat_w(users + i), &tab);
+  for (uint32_t c = 0; c < nc; c++) {
+    uint32_t w[8];
+    fp_words_load(balances + (size_t)t * nc + c, w);
+    if (LISTED) {
+      fp_words_store(leaf_bal + (size_t)i * nc + c, w);
+      fp_words_store(node_bal + (size_t)i * nc + c, w);
+    }
+    absorb(s0, s1, f29_words_to_r261<P>(w), &tab);
+  }
+  store_hat_w(hashes + i, s0);
+}
+// parent p = t or list[t], t < m, from children 2p, 2p+1
+template <bool LISTED>
+__global__ void __launch_bounds__(128) mst_level_kernel(const uint32_t* __restrict__ list, const fp_words* __restrict__ child_hash,
+                                                        const fp_words* __restrict__ child_bal, uint32_t m, uint32_t nc,
+                                                        const PoseidonTable* __restrict__ table, fp_words* __restrict__ hashes,
+                                                        fp_words* __restrict__ bal) {
+  side_kernel_prio();
+  __shared__ LdsTable tab;
+  stage_table(table, &tab);
+  uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= m) return;
+  const uint32_t p = LISTED ? list[t] : t;
   f29 s0 = f29_zero(), s1 = capacity_element(nc + 2);
   for (uint32_t c = 0; c < nc; c++) {
     f29 b = f29_add(load_hat_w(child_bal + (size_t)(2 * p) * nc + c), load_hat_w(child_bal + (size_t)(2 * p + 1) * nc + c));
     store_hat_w(bal + (size_t)p * nc + c, b);          // canonical sum
-    s0 = f29_add(s0, b);                                // < 2 + 4
-    poseidon_permute(s0, s1, &tab);
+    absorb(s0, s1, b, &tab);                            // < 2 + 4
   }
-  s0 = f29_add(s0, load_hat_w(child_hash + 2 * p));
-  poseidon_permute(s0, s1, &tab);
-  s0 = f29_add(s0, load_hat_w(child_hash + 2 * p + 1));
-  poseidon_permute(s0, s1, &tab);
+  absorb(s0, s1, load_hat_w(child_hash + 2 * p), &tab);
+  absorb(s0, s1, load_hat_w(child_hash + 2 * p + 1), &tab);
   store_hat_w(hashes + p, s0);
 }
 
@@ -309,25 +272,18 @@ __global__ void __launch_bounds__(64) mst_inclusion_witness_kernel(const Witness
       uint32_t row = ab.permute_row, r = 0;               // "permute state": 37 rows
       for (int k = 0; k < 4; k++, r++, row++) {
         put_state(out, row, s0, s1);
-        s0 = pow5(f29_add(s0, lds_f29(tab.rc, 2 * r)));
-        s1 = pow5(f29_add(s1, lds_f29(tab.rc, 2 * r + 1)));
-        mix(s0, s1, &tab);
+        poseidon_round<true>(s0, s1, &tab, r);
       }
       for (int k = 0; k < 28; k++, r += 2, row++) {        // two partial rounds per row; a2 = the first s-box output
         put_state(out, row, s0, s1);
-        s0 = pow5(f29_add(s0, lds_f29(tab.rc, 2 * r)));
+        add_constants_sbox<false>(s0, s1, &tab, r);
         store_hat_w(out.col[2] + row, s0);
-        s1 = f29_add(s1, lds_f29(tab.rc, 2 * r + 1));
         mix(s0, s1, &tab);
-        s0 = pow5(f29_add(s0, lds_f29(tab.rc, 2 * r + 2)));
-        s1 = f29_add(s1, lds_f29(tab.rc, 2 * r + 3));
-        mix(s0, s1, &tab);
+        poseidon_round<false>(s0, s1, &tab, r + 1);
       }
       for (int k = 0; k < 4; k++, r++, row++) {
         put_state(out, row, s0, s1);
-        s0 = pow5(f29_add(s0, lds_f29(tab.rc, 2 * r)));
-        s1 = pow5(f29_add(s1, lds_f29(tab.rc, 2 * r + 1)));
-        mix(s0, s1, &tab);
+        poseidon_round<true>(s0, s1, &tab, r);
       }
       put_state(out, row, s0, s1);                        // offset 36: the state after the permutation
     }
@@ -361,11 +317,7 @@ hipError_t WitnessEngine::inclusion_witness(const uint32_t* d_program, uint32_t 
                                             hipStream_t stream) {
   if (!n_items || !n_users) return hipSuccess;
   WitnessTree t{users, hashes, balances, depth, nc, {}};
-  uint32_t off = 0;
-  for (uint32_t l = 0; l <= depth; l++) {
-    t.level_offset[l] = off;
-    off += 1u << (depth - l);
-  }
+  for (uint32_t l = 0; l <= depth; l++) t.level_offset[l] = (uint32_t)mst_level_first(l, depth);
   (void)n_absorbs;
   const WitnessItem* items = reinterpret_cast<const WitnessItem*>(d_program);
   const WitnessAbsorb* absorbs = reinterpret_cast<const WitnessAbsorb*>(d_program + 5 * (size_t)n_items);
@@ -374,33 +326,26 @@ hipError_t WitnessEngine::inclusion_witness(const uint32_t* d_program, uint32_t 
                                                        static_cast<const PoseidonTable*>(table_), advice, rows, 3 * rows);
   return hipGetLastError();
 }
-hipError_t WitnessEngine::leaves(const fp_words* users, const fp_words* balances, size_t n, uint32_t nc,
-                                 fp_words* hashes, hipStream_t stream) {
+hipError_t WitnessEngine::leaves(const uint32_t* d_list, const fp_words* users, const fp_words* balances, size_t n, uint32_t nc,
+                                 fp_words* hashes, fp_words* leaf_bal, fp_words* node_bal, hipStream_t stream) {
   if (!n) return hipSuccess;
-  mst_leaves_kernel<<<(unsigned)((n + 127) / 128), 128, 0, stream>>>(users, balances, (uint32_t)n, nc,
-                                                                    static_cast<const PoseidonTable*>(table_), hashes);
+  const unsigned blocks = (unsigned)((n + 127) / 128);
+  const PoseidonTable* table = static_cast<const PoseidonTable*>(table_);
+  if (d_list)
+    mst_leaves_kernel<true><<<blocks, 128, 0, stream>>>(d_list, users, balances, (uint32_t)n, nc, table, hashes, leaf_bal, node_bal);
+  else
+    mst_leaves_kernel<false><<<blocks, 128, 0, stream>>>(nullptr, users, balances, (uint32_t)n, nc, table, hashes, nullptr, nullptr);
   return hipGetLastError();
 }
-hipError_t WitnessEngine::level(const fp_words* child_hash, const fp_words* child_bal, size_t m, uint32_t nc,
+hipError_t WitnessEngine::level(const uint32_t* d_list, const fp_words* child_hash, const fp_words* child_bal, size_t m, uint32_t nc,
                                 fp_words* hashes, fp_words* bal, hipStream_t stream) {
   if (!m) return hipSuccess;
-  mst_level_kernel<<<(unsigned)((m + 127) / 128), 128, 0, stream>>>(child_hash, child_bal, (uint32_t)m, nc,
-                                                                   static_cast<const PoseidonTable*>(table_), hashes, bal);
-  return hipGetLastError();
-}
-hipError_t WitnessEngine::update_leaves(const uint32_t* d_index, const fp_words* new_bal, size_t m, uint32_t nc, const fp_words* users,
-                                        fp_words* leaf_bal, fp_words* hashes, fp_words* node_bal, hipStream_t stream) {
-  if (!m) return hipSuccess;
-  mst_update_leaves_kernel<<<(unsigned)((m + 127) / 128), 128, 0, stream>>>(d_index, new_bal, (uint32_t)m, nc, users,
-                                                                           static_cast<const PoseidonTable*>(table_), leaf_bal,
-                                                                           hashes, node_bal);
-  return hipGetLastError();
-}
-hipError_t WitnessEngine::update_level(const uint32_t* d_list, size_t count, const fp_words* child_hash, const fp_words* child_bal,
-                                       uint32_t nc, fp_words* hashes, fp_words* bal, hipStream_t stream) {
-  if (!count) return hipSuccess;
-  mst_update_level_kernel<<<(unsigned)((count + 127) / 128), 128, 0, stream>>>(d_list, (uint32_t)count, child_hash, child_bal, nc,
-                                                                              static_cast<const PoseidonTable*>(table_), hashes, bal);
+  const unsigned blocks = (unsigned)((m + 127) / 128);
+  const PoseidonTable* table = static_cast<const PoseidonTable*>(table_);
+  if (d_list)
+    mst_level_kernel<true><<<blocks, 128, 0, stream>>>(d_list, child_hash, child_bal, (uint32_t)m, nc, table, hashes, bal);
+  else
+    mst_level_kernel<false><<<blocks, 128, 0, stream>>>(nullptr, child_hash, child_bal, (uint32_t)m, nc, table, hashes, bal);
   return hipGetLastError();
 }
 

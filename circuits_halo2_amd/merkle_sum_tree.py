@@ -81,12 +81,34 @@ def big_uint_to_fp(big_uint: int) -> bytes:
     return _to_fr_bytes(big_uint)
 
 
+_R_INV = pow(1 << 256, -1, R_MODULUS)
+
+
+def _mont_to_int(row) -> int:
+    """32 bytes in memory form (Montgomery, little-endian) -> the integer they stand for"""
+    return int.from_bytes(bytes(row), "little") * _R_INV % R_MODULUS
+
+
 def fp_to_big_uint(f) -> int:
     """utils/operation_helpers.rs:15-17: the canonical integer of a field element given in memory form"""
-    v = int.from_bytes(bytes(f), "little")
-    if v >= R_MODULUS:
+    if int.from_bytes(bytes(f), "little") >= R_MODULUS:
         raise ValueError("not a field element")
-    return v * pow(1 << 256, -1, R_MODULUS) % R_MODULUS
+    return _mont_to_int(f)
+
+
+def _level_first(depth: int, level: int) -> int:
+    """the first node of `level` in the level-major node arrays of a tree of 2^depth leaves (the leaves, the 2^(depth - 1)
+    parents, .., the root): mst_level_first of csrc/mst_update_plan.h"""
+    return (2 << depth) - (2 << (depth - level))
+
+
+def _check_balance_rows(rows, n_currencies: int, wrong_count: str):
+    """what every front end asks of `rows`, a list of balance rows, in this order: n_currencies balances in each (else
+    ValueError(wrong_count)), none negative"""
+    if set(map(len, rows)) - {n_currencies}:
+        raise ValueError(wrong_count)
+    if rows and n_currencies and min(map(min, rows)) < 0:
+        raise ValueError("Invalid balance")
 
 
 def parse_csv_to_entries(path: str, n_currencies: int):
@@ -135,16 +157,21 @@ def _hash_batch(kind: str, *arrays, n: int, nc: int):
     return h.cpu().numpy(), b.cpu().numpy()
 
 
-class MerkleSumTree:
-    """MerkleSumTree<N_CURRENCIES, N_BYTES> (mst.rs): `from_csv`, `from_csv_sorted`, `from_entries`, `from_params`, `root`,
-    `leaves`, `entries`, `index_of_username`, `update_leaf`; Tree trait (tree.rs): `depth`, `nodes`, `cryptocurrencies`,
-    `get_entry`, the two preimage getters, `generate_proof`, `verify_proof`; `Entry::compute_leaf / recompute_leaf` by index.  All Poseidon hashing runs on the device; nodes are kept level-major on the host."""
+def _build_nodes(d_users, d_bals, depth: int, n_currencies: int):
+    """sg_mst_build_dev on the current stream over 2^depth leaves on the device: the level-major node hashes and node
+    balances, allocated here.  Nothing is waited for."""
+    import torch
+    nodes = (2 << depth) - 1
+    d_h = torch.empty(32 * nodes, dtype=torch.uint8, device="cuda")
+    d_b = torch.empty(32 * nodes * n_currencies, dtype=torch.uint8, device="cuda")
+    ffi.check(ffi.lib().sg_mst_build_dev(ffi.dev_ptr(d_users), ffi.dev_ptr(d_bals), C.c_uint32(depth), C.c_uint32(n_currencies),
+                                         ffi.dev_ptr(d_h), ffi.dev_ptr(d_b), ffi.current_stream_ptr()))
+    return d_h, d_b
 
-    def __init__(self, depth, n_currencies, entries, node_hashes, node_balances, is_sorted=False, cryptocurrencies=None):
-        self.depth, self.n_currencies, self.entries = depth, n_currencies, entries
-        self._h, self._b = node_hashes, node_balances  # level-major numpy buffers
-        self.is_sorted = is_sorted
-        self.cryptocurrencies = cryptocurrencies or []
+
+class _Tree:
+    """What MerkleSumTree and DeviceMerkleSumTree share: everything that needs only `depth`, `n_currencies`, `entries` (None
+    where a tree holds none), `is_sorted` and the class's `from_entries`."""
 
     @classmethod
     def from_csv(cls, path: str, n_currencies: int, n_bytes: int = 8):
@@ -163,11 +190,86 @@ class MerkleSumTree:
         return t
 
     @staticmethod
-    def _entry_fields(name: str, bal):
+    def _entry_fields(name, bal):
         """(username field element, balance field elements) as Montgomery bytes; the zero entry is ("0", 0...)
-        with username field element 0 (entry.rs:30-38)"""
-        u = 0 if name is None else big_intify_username(name)
+        with username field element 0 (entry.rs:30-38).  A username may also be its field element, an int (the proofs of a
+        tree without entries)."""
+        u = name if isinstance(name, int) else 0 if name is None else big_intify_username(name)
         return _to_fr_bytes(u), b"".join(_to_fr_bytes(v) for v in bal)
+
+    def get_entry(self, index: int):
+        if self.entries is None:
+            raise ValueError("a tree built from field elements holds no entries")
+        return self.entries[index]
+
+    def index_of_username(self, username: str) -> int:
+        """mst.rs:207-223: linear scan, or binary search when the tree was built sorted"""
+        if self.entries is None:
+            raise KeyError("Username not found")
+        if self.is_sorted:
+            real = [e for e in self.entries if e[0] is not None]
+            lo, hi = 0, len(real)
+            key = username.encode()
+            while lo < hi:
+                mid = (lo + hi) // 2
+                if real[mid][0].encode() < key:
+                    lo = mid + 1
+                else:
+                    hi = mid
+            if lo < len(real) and real[lo][0] == username:
+                return lo
+            raise KeyError("Username not found")
+        for i, (name, _) in enumerate(self.entries):
+            if name == username:
+                return i
+        raise KeyError("Username not found")
+
+    def _path(self, index: int):
+        """tree.rs:85-137's walk from leaf `index` up to below the root: for every level (path bit, the sibling's number in
+        its level)"""
+        if not 0 <= index < (1 << self.depth):
+            raise IndexError("Index out of bounds")
+        return [((index >> level) & 1, (index >> level) ^ 1) for level in range(self.depth)]
+
+    def verify_proof(self, proof) -> bool:
+        """tree.rs:140-190: recompute the path from the entry and the sibling preimages (hashes on the device),
+        compare the root hash and balances"""
+        nc = self.n_currencies
+        name, bal = proof["entry"]
+        u, b = self._entry_fields(name, bal)
+        bb = np.frombuffer(b, dtype=np.uint8)
+        node_h, node_b = _hash_batch("leaf", np.frombuffer(u, dtype=np.uint8), bb, n=1, nc=nc), bb
+        for level, bit in enumerate(proof["path_indices"]):
+            if level == 0:
+                pre = proof["sibling_leaf_node_hash_preimage"]
+                sib_b = pre[32:]
+                sib_h = _hash_batch("leaf", pre[:32], sib_b, n=1, nc=nc)
+            else:
+                pre = proof["sibling_middle_node_hash_preimages"][level - 1]
+                sib_b = pre[:32 * nc]
+                # a middle node is H(balances..., left.hash, right.hash): rebuild it from two pseudo-children whose
+                # balances add up to the preimage's (left = the sums, right = zero)
+                zeros = np.zeros(32 * nc, dtype=np.uint8)
+                sib_h, chk_b = _hash_batch("middle", pre[32 * nc:], np.concatenate([sib_b, zeros]), n=1, nc=nc)
+                if not (chk_b == sib_b).all():
+                    return False
+            pair_h = np.concatenate([sib_h, node_h]) if bit else np.concatenate([node_h, sib_h])
+            pair_b = np.concatenate([sib_b, node_b]) if bit else np.concatenate([node_b, sib_b])
+            node_h, node_b = _hash_batch("middle", pair_h, pair_b, n=1, nc=nc)
+        rh, rb = proof["root"]
+        return bool((node_h == rh).all() and (node_b == rb).all())
+
+
+class MerkleSumTree(_Tree):
+    """MerkleSumTree<N_CURRENCIES, N_BYTES> (mst.rs): `from_csv`, `from_csv_sorted`, `from_entries`, `from_params`, `root`,
+    `leaves`, `entries`, `index_of_username`, `update_leaf`; Tree trait (tree.rs): `depth`, `nodes`, `cryptocurrencies`,
+    `get_entry`, the two preimage getters, `generate_proof`, `verify_proof`; `Entry::compute_leaf / recompute_leaf` by index.  All Poseidon hashing runs on the device; nodes are kept level-major on the host."""
+
+    def __init__(self, depth, n_currencies, entries, node_hashes, node_balances, is_sorted=False, cryptocurrencies=None):
+        self.depth, self.n_currencies, self.entries = depth, n_currencies, entries
+        self._h, self._b = node_hashes, node_balances  # level-major numpy buffers
+        self.is_sorted = is_sorted
+        self.cryptocurrencies = cryptocurrencies or []
 
     @classmethod
     def from_entries(cls, entries, n_currencies: int, n_bytes: int = 8, is_sorted: bool = False):
@@ -175,13 +277,9 @@ class MerkleSumTree:
         n = len(entries)
         if n == 0:
             raise ValueError("empty tree")
-        for _, bal in entries:
-            if len(bal) != n_currencies:
-                raise ValueError("entry with a wrong number of balances")
-            # mst.rs:103-134 builds the tree from any BigUint balances: one that does not fit N_BYTES only fails later, in
-            # the circuit's range check (circuits/tests.rs:268-299 builds its tree from entry_16_overflow.csv)
-            if any(b < 0 for b in bal):
-                raise ValueError("Invalid balance")
+        # mst.rs:103-134 builds the tree from any BigUint balances: one that does not fit N_BYTES only fails later, in
+        # the circuit's range check (circuits/tests.rs:268-299 builds its tree from entry_16_overflow.csv)
+        _check_balance_rows([bal for _, bal in entries], n_currencies, "entry with a wrong number of balances")
         depth = max(0, (n - 1).bit_length())
         size = 1 << depth
         users = bytearray(32 * size)      # zero entries: username 0, balances 0 (entry.rs:30-38)
@@ -192,12 +290,7 @@ class MerkleSumTree:
             bals[32 * i * n_currencies:32 * (i + 1) * n_currencies] = b
         d_users = torch.from_numpy(np.frombuffer(bytes(users), dtype=np.uint8).copy()).cuda()
         d_bals = torch.from_numpy(np.frombuffer(bytes(bals), dtype=np.uint8).copy()).cuda()
-        nodes = 2 * size - 1
-        d_h = torch.empty(32 * nodes, dtype=torch.uint8, device="cuda")
-        d_b = torch.empty(32 * nodes * n_currencies, dtype=torch.uint8, device="cuda")
-        ffi.check(ffi.lib().sg_mst_build_dev(ffi.dev_ptr(d_users), ffi.dev_ptr(d_bals), C.c_uint32(depth),
-                                             C.c_uint32(n_currencies), ffi.dev_ptr(d_h), ffi.dev_ptr(d_b),
-                                             ffi.current_stream_ptr()))
+        d_h, d_b = _build_nodes(d_users, d_bals, depth, n_currencies)
         torch.cuda.synchronize()
         padded = list(entries) + [(None, [0] * n_currencies)] * (size - n)
         return cls(depth, n_currencies, padded, d_h.cpu().numpy(), d_b.cpu().numpy(), is_sorted)
@@ -239,8 +332,7 @@ class MerkleSumTree:
         return _hash_batch("leaf", np.frombuffer(u, dtype=np.uint8), bb, n=1, nc=self.n_currencies), bb.copy()
 
     def _level_offset(self, level: int) -> int:
-        size = 1 << self.depth
-        return sum(size >> l for l in range(level))
+        return _level_first(self.depth, level)
 
     def node(self, level: int, index: int):
         o = self._level_offset(level) + index
@@ -261,34 +353,11 @@ class MerkleSumTree:
         size = 1 << self.depth
         return self._h[:32 * size], self._b[:32 * size * self.n_currencies]
 
-    def index_of_username(self, username: str) -> int:
-        """mst.rs:207-223: linear scan, or binary search when the tree was built sorted"""
-        if self.is_sorted:
-            real = [e for e in self.entries if e[0] is not None]
-            lo, hi = 0, len(real)
-            key = username.encode()
-            while lo < hi:
-                mid = (lo + hi) // 2
-                if real[mid][0].encode() < key:
-                    lo = mid + 1
-                else:
-                    hi = mid
-            if lo < len(real) and real[lo][0] == username:
-                return lo
-            raise KeyError("Username not found")
-        for i, (name, _) in enumerate(self.entries):
-            if name == username:
-                return i
-        raise KeyError("Username not found")
-
     def update_leaf(self, username: str, new_balances):
         """mst.rs:169-204: new balances for one user, the leaf and its `depth` ancestors are re-hashed (device,
         one call per level); returns the new root (hash, balances)"""
         nc = self.n_currencies
-        if len(new_balances) != nc:
-            raise ValueError("wrong number of balances")
-        if any(int(b) < 0 for b in new_balances):
-            raise ValueError("Invalid balance")
+        _check_balance_rows([new_balances], nc, "wrong number of balances")
         index = self.index_of_username(username)
         self.entries[index] = (username, list(new_balances))
         u, b = self._entry_fields(username, new_balances)
@@ -303,9 +372,6 @@ class MerkleSumTree:
             self._set_node(level, parent, h, bsum)
             cur = parent
         return self.root()
-
-    def get_entry(self, index: int):
-        return self.entries[index]
 
     def get_middle_node_hash_preimage(self, level: int, index: int) -> np.ndarray:
         """tree.rs:22-56: [left.balances + right.balances ..., left.hash, right.hash] of the middle node (level, index) as
@@ -343,61 +409,20 @@ class MerkleSumTree:
         """tree.rs:85-137.  Besides the sibling nodes (hash, balances) the proof carries what the reference's
         MerkleProof holds: the sibling leaf's hash preimage [username, balances...] and, for every level above,
         the sibling middle node's preimage [left.bal + right.bal ..., left.hash, right.hash]."""
-        if not 0 <= index < (1 << self.depth):
-            raise IndexError("Index out of bounds")
-        nc = self.n_currencies
-        sib, bits, pre_mid, idx = [], [], [], index
-        for level in range(self.depth):
-            bits.append(idx & 1)
-            sidx = idx ^ 1
-            sib.append(self.node(level, sidx))
-            if level > 0:
-                lh, _ = self.node(level - 1, 2 * sidx)
-                rh, _ = self.node(level - 1, 2 * sidx + 1)
-                pre_mid.append(np.concatenate([self.node(level, sidx)[1], lh, rh]))
-            idx >>= 1
-        pre_leaf = None
-        if self.depth:
-            name, bal = self.entries[index ^ 1]
-            u, b = self._entry_fields(name, bal)
-            pre_leaf = np.frombuffer(u + b, dtype=np.uint8).copy()
-        return {"entry": self.entries[index], "leaf": self.node(0, index), "siblings": sib, "path_indices": bits,
-                "root": self.root(), "sibling_leaf_node_hash_preimage": pre_leaf,
-                "sibling_middle_node_hash_preimages": pre_mid}
-
-    def verify_proof(self, proof) -> bool:
-        """tree.rs:140-190: recompute the path from the entry and the sibling preimages (hashes on the device),
-        compare the root hash and balances"""
-        nc = self.n_currencies
-        name, bal = proof["entry"]
-        u, b = self._entry_fields(name, bal)
-        bb = np.frombuffer(b, dtype=np.uint8)
-        node_h, node_b = _hash_batch("leaf", np.frombuffer(u, dtype=np.uint8), bb, n=1, nc=nc), bb
-        for level, bit in enumerate(proof["path_indices"]):
-            if level == 0:
-                pre = proof["sibling_leaf_node_hash_preimage"]
-                sib_b = pre[32:]
-                sib_h = _hash_batch("leaf", pre[:32], sib_b, n=1, nc=nc)
-            else:
-                pre = proof["sibling_middle_node_hash_preimages"][level - 1]
-                sib_b = pre[:32 * nc]
-                # a middle node is H(balances..., left.hash, right.hash): rebuild it from two pseudo-children whose
-                # balances add up to the preimage's (left = the sums, right = zero)
-                zeros = np.zeros(32 * nc, dtype=np.uint8)
-                sib_h, chk_b = _hash_batch("middle", pre[32 * nc:], np.concatenate([sib_b, zeros]), n=1, nc=nc)
-                if not (chk_b == sib_b).all():
-                    return False
-            pair_h = np.concatenate([sib_h, node_h]) if bit else np.concatenate([node_h, sib_h])
-            pair_b = np.concatenate([sib_b, node_b]) if bit else np.concatenate([node_b, sib_b])
-            node_h, node_b = _hash_batch("middle", pair_h, pair_b, n=1, nc=nc)
-        rh, rb = proof["root"]
-        return bool((node_h == rh).all() and (node_b == rb).all())
+        path = self._path(index)
+        return {"entry": self.entries[index], "leaf": self.node(0, index),
+                "siblings": [self.node(level, sib) for level, (_, sib) in enumerate(path)],
+                "path_indices": [bit for bit, _ in path], "root": self.root(),
+                "sibling_leaf_node_hash_preimage": self.get_leaf_node_hash_preimage(index ^ 1) if self.depth else None,
+                "sibling_middle_node_hash_preimages": [self.get_middle_node_hash_preimage(level, sib)
+                                                       for level, (_, sib) in enumerate(path) if level > 0]}
 
 
 def pack_entries(entries, n_currencies: int):
     """[(username, [balances])] -> (name_bytes, name_off, digit_bytes, digit_off), the host buffers of sg_mst_entries_dev:
     the UTF-8 names back to back with n + 1 byte offsets, the balances as `str(int)` back to back (entry-major, one field
     per currency) with n * n_currencies + 1 offsets.  Host code only; refuses what MerkleSumTree.from_entries refuses."""
+    # _check_balance_rows' checks, in its order, inside the one pass that packs: a pass of their own costs 2 ms in 2^16 entries
     names, flat = [], []
     for name, bal in entries:
         if len(bal) != n_currencies:
@@ -425,7 +450,7 @@ def pack_balances(flat):
     return text[~comma], digit_off
 
 
-class DeviceMerkleSumTree:
+class DeviceMerkleSumTree(_Tree):
     """A Merkle sum tree whose leaves are already field elements on the device (a snapshot of 2^depth users: username
     field elements and balances as Montgomery Fr), built and KEPT in HBM: level-major node arrays as `sg_mst_build_dev`
     lays them out.  The reference's `Tree` trait [REF zk_prover/src/merkle_sum_tree/tree.rs:8-137] for the two methods a
@@ -453,18 +478,11 @@ class DeviceMerkleSumTree:
             raise ValueError("DeviceMerkleSumTree: 2^depth usernames and 2^depth * n_currencies balances expected")
         self.depth, self.n_currencies = depth, n_currencies
         self.d_users, self.d_bals = d_usernames, d_balances
-        nodes = 2 * size - 1
-        self.d_h = torch.empty(32 * nodes, dtype=torch.uint8, device="cuda")
-        self.d_b = torch.empty(32 * nodes * n_currencies, dtype=torch.uint8, device="cuda")
-        ffi.check(ffi.lib().sg_mst_build_dev(ffi.dev_ptr(d_usernames), ffi.dev_ptr(d_balances), C.c_uint32(depth),
-                                             C.c_uint32(n_currencies), ffi.dev_ptr(self.d_h), ffi.dev_ptr(self.d_b),
-                                             ffi.current_stream_ptr()))
+        self.d_h, self.d_b = _build_nodes(d_usernames, d_balances, depth, n_currencies)
         # the snapshot is read from other streams afterwards (proofs in flight run one stream per worker thread, and the
         # first reader caches the root): the build -- one-off, tens of milliseconds -- is complete when the constructor returns
         torch.cuda.current_stream().synchronize()
-        self.offsets = [0]
-        for level in range(depth):
-            self.offsets.append(self.offsets[-1] + (size >> level))
+        self.offsets = [_level_first(depth, level) for level in range(depth + 1)]
         self._root = None
 
     @classmethod
@@ -493,33 +511,6 @@ class DeviceMerkleSumTree:
         tree.is_sorted = is_sorted
         tree.cryptocurrencies = []
         return tree
-
-    @classmethod
-    def from_csv(cls, path: str, n_currencies: int, n_bytes: int = 8):
-        entries, crypto = parse_csv_to_entries(path, n_currencies)
-        t = cls.from_entries(entries, n_currencies, n_bytes)
-        t.cryptocurrencies = crypto
-        return t
-
-    @classmethod
-    def from_csv_sorted(cls, path: str, n_currencies: int, n_bytes: int = 8):
-        """mst.rs:89-100: leaves sorted by the username byte values"""
-        entries, crypto = parse_csv_to_entries(path, n_currencies)
-        entries.sort(key=lambda e: e[0].encode())
-        t = cls.from_entries(entries, n_currencies, n_bytes, is_sorted=True)
-        t.cryptocurrencies = crypto
-        return t
-
-    def get_entry(self, index: int):
-        if self.entries is None:
-            raise ValueError("a tree built from field elements holds no entries")
-        return self.entries[index]
-
-    def index_of_username(self, username: str) -> int:
-        """mst.rs:207-223, MerkleSumTree's own search over this tree's entries"""
-        if self.entries is None:
-            raise KeyError("Username not found")
-        return MerkleSumTree.index_of_username(self, username)
 
     def update_leaf(self, username: str, new_balances):
         """mst.rs:169-204: new balances for one user; the leaf and its `depth` ancestors are re-hashed in place on the device.
@@ -555,10 +546,7 @@ class DeviceMerkleSumTree:
             return self.root()
         if min(indices) < 0 or max(indices) >= (1 << self.depth):
             raise IndexError("Index out of bounds")
-        if any(len(bal) != nc for bal in balances):
-            raise ValueError("wrong number of balances")
-        if min(map(min, balances)) < 0:
-            raise ValueError("Invalid balance")
+        _check_balance_rows(balances, nc, "wrong number of balances")
         last = dict(zip(indices, balances))                   # a repeated index keeps its last row
         order = sorted(last)
         flat = [int(b) for i in order for b in last[i]]
@@ -578,15 +566,6 @@ class DeviceMerkleSumTree:
                                               self.n_currencies, ffi.dev_ptr(self.d_users), ffi.dev_ptr(self.d_bals),
                                               ffi.dev_ptr(self.d_h), ffi.dev_ptr(self.d_b), ffi.current_stream_ptr()))
         torch.cuda.current_stream().synchronize()
-
-    @staticmethod
-    def _entry_fields(name, bal):
-        """MerkleSumTree._entry_fields; a username may also be its field element (the proofs of a tree without entries)"""
-        if isinstance(name, int):
-            return _to_fr_bytes(name), b"".join(_to_fr_bytes(v) for v in bal)
-        return MerkleSumTree._entry_fields(name, bal)
-
-    verify_proof = MerkleSumTree.verify_proof   # tree.rs:140-190: the same code, over this class's n_currencies and _entry_fields
 
     def _rows(self, hash_nodes, balance_nodes, users):
         """one gather + one copy: rows of the hash array, of the balance array (n_currencies rows per node), leaf inputs"""
@@ -613,48 +592,33 @@ class DeviceMerkleSumTree:
 
     def public_inputs(self, index: int):
         """[leaf hash, root hash, root balances..] of user `index` as integers: `circuit.instances()[0]`"""
-        if not 0 <= index < (1 << self.depth):
-            raise IndexError("Index out of bounds")
-        h, _, _, _ = self._rows([index], [], [])
-        rinv = pow(1 << 256, -1, R_MODULUS)
-        to_int = lambda row: int.from_bytes(bytes(row), "little") * rinv % R_MODULUS
-        rh, rb = self.root()
-        return [to_int(h[0]), to_int(rh)] + [to_int(rb[32 * c:32 * c + 32]) for c in range(self.n_currencies)]
+        return self.public_inputs_many([index])[0]
 
     def public_inputs_many(self, indices):
         """`public_inputs` of several users with one gather and one copy"""
         if any(not 0 <= i < (1 << self.depth) for i in indices):
             raise IndexError("Index out of bounds")
         h, _, _, _ = self._rows([int(i) for i in indices], [], [])
-        rinv = pow(1 << 256, -1, R_MODULUS)
-        to_int = lambda row: int.from_bytes(bytes(row), "little") * rinv % R_MODULUS
         rh, rb = self.root()
-        tail = [to_int(rh)] + [to_int(rb[32 * c:32 * c + 32]) for c in range(self.n_currencies)]
-        return [[to_int(row)] + tail for row in h]
+        tail = [_mont_to_int(rh)] + [_mont_to_int(rb[32 * c:32 * c + 32]) for c in range(self.n_currencies)]
+        return [[_mont_to_int(row)] + tail for row in h]
 
     def generate_proof(self, index: int):
         """the fields of the reference's MerkleProof (see MerkleSumTree.generate_proof); `entry` carries the username as
         its field element (int) where the snapshot holds no names, and the entry itself (name, integer balances) where the
         tree was built from entries"""
-        if not 0 <= index < (1 << self.depth):
-            raise IndexError("Index out of bounds")
-        hash_nodes, bal_nodes, bits = [self.offsets[0] + index], [], []
-        idx = index
-        for level in range(self.depth):
-            bits.append(idx & 1)
-            sib = idx ^ 1
+        path = self._path(index)
+        hash_nodes, bal_nodes = [self.offsets[0] + index], []
+        for level, (_, sib) in enumerate(path):
             if level > 0:   # the sibling middle node's preimage: its balances, its children's hashes
                 bal_nodes.append(self.offsets[level] + sib)
                 hash_nodes += [self.offsets[level - 1] + 2 * sib, self.offsets[level - 1] + 2 * sib + 1]
-            idx >>= 1
         h, b, users, bals = self._rows(hash_nodes, bal_nodes, [index, index ^ 1] if self.depth else [index])
-        rinv = pow(1 << 256, -1, R_MODULUS)
-        to_int = lambda row: int.from_bytes(bytes(row), "little") * rinv % R_MODULUS
         nc = self.n_currencies
-        entry = (to_int(users[0]), [to_int(bals[0][32 * c:32 * c + 32]) for c in range(nc)])
+        entry = (_mont_to_int(users[0]), [_mont_to_int(bals[0][32 * c:32 * c + 32]) for c in range(nc)])
         if self.entries is not None:
             entry = self.entries[index]
         pre_mid = [np.concatenate([b[l], h[1 + 2 * l], h[2 + 2 * l]]) for l in range(max(0, self.depth - 1))]
         pre_leaf = np.concatenate([users[1], bals[1]]) if self.depth else None
-        return {"entry": entry, "leaf": (h[0], bals[0]), "path_indices": bits, "root": self.root(),
+        return {"entry": entry, "leaf": (h[0], bals[0]), "path_indices": [bit for bit, _ in path], "root": self.root(),
                 "sibling_leaf_node_hash_preimage": pre_leaf, "sibling_middle_node_hash_preimages": pre_mid}

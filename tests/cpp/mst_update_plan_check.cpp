@@ -1,5 +1,6 @@
 // The HIP-free planning behind sg_mst_update_dev (csrc/mst_update_plan.h) on the host, built by a host compiler alone.
 // tests/test_mst_update_cpu.py feeds commands on stdin and compares what is printed with sets of Python integers.
+//   o DEPTH                                             mst_level_first of every level 0 .. DEPTH ("first F_0 .. F_DEPTH")
 //   p DEPTH M I_0 .. I_{M-1}                            the plan of M leaf indices
 //   v DEPTH NC M I_0 .. I_{M-1} K O_0 .. O_{K-1} HEX    mst_update_problem of the indices, K digit offsets and the digit bytes
 //                                                       ("-" = none)
@@ -44,6 +45,11 @@ int main() {
         for (uint32_t t = 0; t < plan.count(l); t++) std::printf(" %u", plan.list(l)[t]);
         std::printf("\n");
       }
+    } else if (cmd == "o") {
+      if (!(std::cin >> depth)) return 2;
+      std::printf("first");
+      for (uint32_t l = 0; l <= depth; l++) std::printf(" %llu", (unsigned long long)sg::mst_level_first(l, depth));
+      std::printf("\n");
     } else if (cmd == "v") {
       uint32_t nc = 0;
       size_t k = 0;

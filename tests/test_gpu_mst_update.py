@@ -1,6 +1,6 @@
-"""A device-resident Merkle sum tree updated in place: sg_mst_update_dev (mst_update_leaves_kernel / mst_update_level_kernel of
-csrc/witness.hip, the launch plan of csrc/mst_update_plan.h) through `DeviceMerkleSumTree.update_leaf / update_leaves /
-update_leaves_at` and through the C ABI.
+"""A device-resident Merkle sum tree updated in place: sg_mst_update_dev of csrc/abi_mst.hip (the listed forms of mst_leaves_kernel /
+mst_level_kernel of csrc/witness.hip, the launch plan of csrc/mst_update_plan.h) through `DeviceMerkleSumTree.update_leaf /
+update_leaves / update_leaves_at` and through the C ABI.
 
 Every expected value comes from the oracle: the tree of the MODIFIED entries, built by the C oracle's leaf and level functions
 over pyref.mst_entry's field elements (oracle.fr_to_mont brings integers to memory form).  After every update all four arrays
@@ -95,13 +95,14 @@ def applied(entries, idx, rows):
 # ============================================================================= every shape of the plan
 DEPTH5 = [[0], [31], [0, 31], [6, 7], [7, 8], list(range(32))]
 CASES = ([(0, 1, [0])] + [(1, 2, idx) for idx in ([0], [1], [0, 1])] + [(5, nc, idx) for nc in (1, 2, 3) for idx in DEPTH5] +
-         [(8, 2, sorted(random.Random(8).sample(range(256), 129))), (8, 2, list(range(256)))])
+         [(8, 2, sorted(random.Random(8).sample(range(256), 129))), (8, 2, list(range(256))), (9, 1, list(range(0, 258, 2)))])
 
 
 @pytest.mark.parametrize("depth,nc,idx", CASES, ids=[f"depth{d}-nc{nc}-{len(idx)}from{idx[0]}to{idx[-1]}" for d, nc, idx in CASES])
 def test_update_leaves_at_gives_the_tree_of_the_modified_entries(gpu, depth, nc, idx):
     """one leaf at either end, both ends (they meet at the root only), siblings, neighbours under different parents, every leaf;
-    129 leaves cross the 128-thread block of the leaf kernel and of the first level's.  The new balances hold 0, 2^64 - 1,
+    129 leaves cross the 128-thread block of the leaf kernel and of the first level's; the 129 even leaves of depth 9 have 129
+    distinct parents, the one list of a level kernel that runs one past a block.  The new balances hold 0, 2^64 - 1,
     r - 1, r, r + 1 and a 90-digit number."""
     from circuits_halo2_amd.merkle_sum_tree import DeviceMerkleSumTree
     entries = start_entries(1 << depth, nc)

@@ -1,4 +1,4 @@
-"""The witness side of csrc/witness.hip through the C ABI -- sg_mst_leaves_dev, sg_mst_level_dev, sg_mst_build_dev (the
+"""The witness side of csrc/witness.hip through the C ABI (csrc/abi_mst.hip) -- sg_mst_leaves_dev, sg_mst_level_dev, sg_mst_build_dev (the
 Poseidon Merkle sum tree) and sg_mst_inclusion_witness_dev (the advice columns of the inclusion circuit) -- at the sizes
 where their launches change and on the values uniform sampling never gives: n off the 128-thread block edge (the threads
 behind n leave after the staging barrier), up to 64 currencies, usernames and balances 0, 1, r - 1 and the 64-bit

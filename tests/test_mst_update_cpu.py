@@ -15,7 +15,7 @@ import pytest
 from conftest import ROOT
 
 from circuits_halo2_amd import ffi
-from circuits_halo2_amd.merkle_sum_tree import DeviceMerkleSumTree, pack_balances, pack_entries
+from circuits_halo2_amd.merkle_sum_tree import DeviceMerkleSumTree, _level_first, pack_balances, pack_entries
 
 SG_ERR_INVALID = -1
 
@@ -43,7 +43,21 @@ PLAN_CASES = [(0, [0]),
               (1, [0]), (1, [1]), (1, [0, 1]),
               (5, [0]), (5, [31]), (5, [0, 31]), (5, [6, 7]), (5, [7, 8]), (5, list(range(32))),
               (8, sorted(random.Random(8).sample(range(256), 129))),
+              (9, list(range(0, 258, 2))),
               (30, [0, (1 << 30) - 1])]
+
+
+def test_level_first_is_the_sum_of_the_levels_below(exe):
+    """mst_level_first, the one place that knows the level-major layout (the build, the update and the witness kernel's table use
+    it), against the sum it stands for; 62 is the deepest tree a 64-bit node number takes"""
+    depths = [0, 1, 2, 30, 31, 62]
+    out = ask(exe, [f"o {d}" for d in depths])
+    assert len(out) == len(depths)
+    for d, line in zip(depths, out):
+        assert line.split()[0] == "first"
+        want = [sum(1 << (d - j) for j in range(l)) for l in range(d + 1)]
+        assert [int(x) for x in line.split()[1:]] == want, d
+        assert [_level_first(d, l) for l in range(d + 1)] == want, d           # the Python front end's copy
 
 
 def test_plan_lists_are_the_distinct_parents_of_every_level(exe):
@@ -59,6 +73,8 @@ def test_plan_lists_are_the_distinct_parents_of_every_level(exe):
             assert line[:2] == ["list", str(l)] and [int(x) for x in line[2:]] == want[l - 1], f"{what}: level {l}"
         if depth:
             assert want[-1] == [0] and sum(map(len, want)) <= len(idx) * depth, what
+        if depth == 9:     # what this case is there for: the one list that runs one past a 128-thread block of the level kernel
+            assert [len(w) for w in want[:2]] == [129, 65] and [int(x) for x in head[1:3]] == [0, 129], what
         at += depth + 1
     assert at == len(out)
     # what the depth-5 pairs are there for: 0 and 31 meet at the root only, 7 and 8 are neighbours that meet high up, 6 and 7 are siblings

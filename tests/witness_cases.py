@@ -1,5 +1,5 @@
-"""The cases that tests/test_gpu_witness.py runs against the kernels of csrc/witness.hip (mst_leaves_kernel, mst_level_kernel,
-mst_inclusion_witness_kernel, reached through sg_mst_leaves_dev / sg_mst_level_dev / sg_mst_build_dev /
+"""The cases that tests/test_gpu_witness.py runs against the kernels of csrc/witness.hip (the dense forms of mst_leaves_kernel and
+mst_level_kernel, mst_inclusion_witness_kernel, reached through csrc/abi_mst.hip's sg_mst_leaves_dev / sg_mst_level_dev / sg_mst_build_dev /
 sg_mst_inclusion_witness_dev): the sizes around the 128-thread blocks of the tree kernels and the 64-thread x-blocks of the
 witness kernel, the input generators (edge values of the field, words >= r, child balances whose sums wrap mod r, trees with
 balances in and out of the range check's range) and a plain-integer interpreter of the witness program, which restates what
