@@ -82,11 +82,9 @@ struct Context {
   DevBuf<uint8_t> stage_a, stage_b, scratch;
   std::vector<uint8_t> gate_blob_host;
   GateProgramCache gate_programs;   // lowered gate programs by structure (gates_compile.h)
-  // in-place multi-pass transforms need a scratch vector; one per caller stream, so that transforms
-  // enqueued on a side stream never share it with work in flight on another stream
-  std::map<hipStream_t, DevBuf<uint8_t>> ntt_scratch;
-  // work space of the scan-type helpers (prefix / grand products, Kate division): per (stream, slot), so
-  // that the calls are asynchronous -- work on one stream is ordered, other streams own other buffers
+  // work space of the scan-type helpers (prefix / grand products, Kate division) and the scratch vector of in-place multi-pass
+  // transforms: per (stream, slot), so that the calls are asynchronous -- work on one stream is ordered, other streams own
+  // other buffers
   std::map<std::pair<hipStream_t, int>, DevBuf<uint8_t>> stream_scratch;
   DomainConsts* d_consts = nullptr;
   struct CosetTables {       // sg_coeff_to_cosets / sg_cosets_to_pieces: per (k, ext_k, cosets)

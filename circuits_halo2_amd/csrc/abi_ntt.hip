@@ -1,18 +1,26 @@
 // C ABI, transform family: NTTs, the extended domain, the cosets of the quotient, the vanishing polynomial (summa_gpu.hip
 // holds the core).
 #include "abi_internal.h"
+#include "coset_plan.h"
 
 using namespace sg;
 namespace {
 
-// `count` transforms of one size (1 <= log_n <= 18: the batched plans), NTT_BATCH_MAX of them per launch.  ins == nullptr: in
-// place, and multi-pass plans then need a scratch vector per transform -- slot 3 of the stream, reserved once, for the
-// largest chunk, before the first launch (growing it frees the old buffer, which waits for the device).
-int batched_transforms(fp_words* const* outs, const fp_words* const* ins, size_t in_len, size_t count, uint32_t log_n,
-                       const words8& omega, const words8* divisor, const words8* pre3, const fp_words* const* pre_tab,
-                       hipStream_t s, const char* what) {
+// `count` transforms of one size on `s`: batched while ntt_batched(log_n) holds, NTT_BATCH_MAX of them per launch, otherwise one
+// after the other (pre_tab: batched sizes only).  ins == nullptr: in place, and multi-pass plans then need a scratch vector per
+// transform -- slot 3 of the stream, reserved once, for the largest chunk, before the first launch (growing it frees the old
+// buffer, which waits for the device).
+int transforms(fp_words* const* outs, const fp_words* const* ins, size_t in_len, size_t count, uint32_t log_n,
+               const words8& omega, const words8* divisor, const words8* pre3, const fp_words* const* pre_tab,
+               hipStream_t s, const char* what) {
+  if (!ntt_batched(log_n)) {
+    if (pre_tab) return fail(SG_ERR_INVALID, what);
+    for (size_t i = 0; i < count; i++)
+      TRY(ntt_dev(ins ? ins[i] : outs[i], ins ? in_len : (size_t)1 << log_n, outs[i], log_n, omega, divisor, pre3, nullptr, s));
+    return SG_OK;
+  }
   uint8_t* scr = nullptr;
-  if (!ins && count && log_n > g_ctx->ntt.config().max_single_log) {
+  if (count && ntt_needs_scratch(g_ctx->ntt.config(), log_n, !ins)) {
     hipError_t e = scratch_for(s, 3, std::min<size_t>(count, NTT_BATCH_MAX) * ((size_t)32 << log_n), &scr);
     if (e != hipSuccess) return hip_fail("ntt scratch", e);
   }
@@ -51,8 +59,8 @@ int sg_ntt_fr(uint8_t* a, const uint8_t omega[32], uint32_t log_n) {
   return staged_in_place(a, (size_t)32 << log_n, [&](void* d, void* s) { return sg_ntt_fr_dev(d, omega, log_n, s); });
 }
 // A batch of independent in-place transforms of one size (the 9 lagrange_to_coeff / 9
-// coeff_to_extended calls of a proof): round-robin over the two batch streams so that one
-// transform's tail overlaps the next one's head.  divisor == NULL: plain best_fft.
+// coeff_to_extended calls of a proof): batched launches on the caller's stream while the size allows, above that round-robin
+// over the two batch streams so that one transform's tail overlaps the next one's head.  divisor == NULL: plain best_fft.
 int sg_ntt_fr_batch_dev(void* const* d_a, size_t count, const uint8_t omega[32], const uint8_t* divisor,
                         uint32_t log_n, void* stream) {
   if ((count && !d_a) || !omega || log_n > 28) return fail(SG_ERR_INVALID, "sg_ntt_fr_batch: bad argument");
@@ -62,14 +70,11 @@ int sg_ntt_fr_batch_dev(void* const* d_a, size_t count, const uint8_t omega[32],
   Context& c = *g_ctx;
   const words8 w = load32(omega), dv = divisor ? load32(divisor) : words8{};
   const size_t n = (size_t)1 << log_n;
-  const bool need_scratch = log_n > c.ntt.config().max_single_log;
-  if (log_n >= 1 && log_n <= 18) {
-    // small transforms: one launch per pass for up to NTT_BATCH_MAX vectors (each launch is at its ~5 us floor otherwise);
-    // asynchronous on the caller's stream, scratch per stream
-    return batched_transforms(reinterpret_cast<fp_words* const*>(d_a), nullptr, 0, count, log_n, w, divisor ? &dv : nullptr, nullptr,
-                              nullptr, pick_stream(stream), "ntt batch");
-  }
-  // one scratch area per stream
+  const bool need_scratch = ntt_needs_scratch(c.ntt.config(), log_n, true);
+  if (ntt_batched(log_n))   // asynchronous on the caller's stream, scratch per stream
+    return transforms(reinterpret_cast<fp_words* const*>(d_a), nullptr, 0, count, log_n, w, divisor ? &dv : nullptr, nullptr, nullptr,
+                      pick_stream(stream), "ntt batch");
+  // larger ones: round robin over the two batch streams, one scratch area per stream, and the host waits for both
   if (need_scratch) {
     hipError_t e = c.scratch.reserve(2 * n * 32);
     if (e != hipSuccess) return hip_fail("ntt scratch", e);
@@ -108,15 +113,15 @@ int sg_ntt_fr_batch_oop_dev(const void* const* d_in, void* const* d_out, size_t 
       }
     }
   }
-  if (log_n < 1 || log_n > 18) {   // outside the batched plans: copy, then in place
+  if (!ntt_batched(log_n)) {   // copy, then in place over the two batch streams
     for (size_t i = 0; i < count; i++)
       CHECK_HIP(hipMemcpyAsync(d_out[i], d_in[i], n * 32, hipMemcpyDeviceToDevice, pick_stream(stream)), "D2D copy");
     return sg_ntt_fr_batch_dev(d_out, count, omega, divisor, log_n, stream);
   }
   LOCKED_CTX();
   const words8 w = load32(omega), dv = divisor ? load32(divisor) : words8{};
-  return batched_transforms(reinterpret_cast<fp_words* const*>(d_out), reinterpret_cast<const fp_words* const*>(d_in), n, count, log_n, w,
-                            divisor ? &dv : nullptr, nullptr, nullptr, pick_stream(stream), "ntt batch");
+  return transforms(reinterpret_cast<fp_words* const*>(d_out), reinterpret_cast<const fp_words* const*>(d_in), n, count, log_n, w,
+                    divisor ? &dv : nullptr, nullptr, nullptr, pick_stream(stream), "ntt batch");
 }
 
 int sg_intt_fr_dev(void* d_a, const uint8_t omega_inv[32], const uint8_t divisor[32], uint32_t log_n, void* stream) {
@@ -155,8 +160,7 @@ int sg_coeff_to_extended_dev(const void* d_coeffs, uint32_t k, uint32_t ext_k, v
   return ntt_dev(static_cast<const fp_words*>(d_coeffs), (size_t)1 << k, static_cast<fp_words*>(d_out), ext_k, dc->omega,
                  nullptr, pre, nullptr, pick_stream(stream));
 }
-// several columns at once: one launch per pass while the extended domain is small (<= 2^18), one transform after
-// the other above that (a 2^20 transform fills the chip on its own)
+// several columns at once
 int sg_coeff_to_extended_batch_dev(const void* const* d_coeffs, void* const* d_out, size_t count, uint32_t k, uint32_t ext_k,
                                    void* stream) {
   if ((count && (!d_coeffs || !d_out)) || ext_k > 28 || k > ext_k) return fail(SG_ERR_INVALID, "sg_coeff_to_extended_batch: bad argument");
@@ -168,13 +172,8 @@ int sg_coeff_to_extended_batch_dev(const void* const* d_coeffs, void* const* d_o
   hipStream_t s = pick_stream(stream);
   TRY(sync_own_stream_into(s));
   words8 pre[3] = {dc->one, dc->zeta, dc->zeta2};
-  if (ext_k >= 1 && ext_k <= 18)
-    return batched_transforms(reinterpret_cast<fp_words* const*>(d_out), reinterpret_cast<const fp_words* const*>(d_coeffs),
-                              (size_t)1 << k, count, ext_k, dc->omega, nullptr, pre, nullptr, s, "coeff_to_extended batch");
-  for (size_t i = 0; i < count; i++)
-    TRY(ntt_dev(static_cast<const fp_words*>(d_coeffs[i]), (size_t)1 << k, static_cast<fp_words*>(d_out[i]), ext_k, dc->omega,
-                nullptr, pre, nullptr, s));
-  return SG_OK;
+  return transforms(reinterpret_cast<fp_words* const*>(d_out), reinterpret_cast<const fp_words* const*>(d_coeffs), (size_t)1 << k, count,
+                    ext_k, dc->omega, nullptr, pre, nullptr, s, "coeff_to_extended batch");
 }
 int sg_coeff_to_extended(const uint8_t* coeffs, uint32_t k, uint32_t ext_k, uint8_t* out) {
   if (!coeffs || !out || ext_k > 28 || k > ext_k) return fail(SG_ERR_INVALID, "sg_coeff_to_extended: bad argument");
@@ -215,60 +214,31 @@ int coset_tables_for(uint32_t k, uint32_t ext_k, uint32_t nc, const Context::Cos
     const DomainConsts *dk, *de;
     TRY(get_consts(k, &dk));
     TRY(get_consts(ext_k, &de));
-    Context::CosetTables t;
     Fr zeta, w_ext;
     std::memcpy(zeta.l, &dk->zeta, 32);
     std::memcpy(w_ext.l, &de->omega, 32);
-    std::vector<Fr> shift(nc), gamma(nc);
+    CosetPlan plan;
+    const CosetPlanStatus st = coset_plan(k, nc, zeta, w_ext, &plan);
+    if (st == CosetPlanStatus::singular) return fail(SG_ERR_INVALID, "cosets: singular Vandermonde matrix");
+    if (st == CosetPlanStatus::inside_domain) return fail(SG_ERR_INVALID, "cosets: a coset inside the domain");
+    Context::CosetTables t{};
     words8 inv_shift[MAX_COSETS];
-    const uint64_t n_limbs[4] = {(uint64_t)1 << k, 0, 0, 0};
     for (uint32_t b = 0; b < nc; b++) {
-      shift[b] = zeta * w_ext.pow((uint64_t)b);
-      gamma[b] = shift[b].pow(n_limbs);
-      std::memcpy(&t.shift[b], shift[b].l, 32);
-      const Fr si = shift[b].inv();
-      std::memcpy(&inv_shift[b], si.l, 32);
-    }
-    // V[b][t] = gamma_b^t; inverse by Gauss-Jordan on [V | I] (the gammas are distinct: the cosets differ)
-    std::vector<std::vector<Fr>> a(nc, std::vector<Fr>(2 * nc, Fr::zero()));
-    for (uint32_t b = 0; b < nc; b++) {
-      Fr pw = Fr::one();
-      for (uint32_t tt = 0; tt < nc; tt++) {
-        a[b][tt] = pw;
-        pw = pw * gamma[b];
-      }
-      a[b][nc + b] = Fr::one();
-    }
-    for (uint32_t col = 0; col < nc; col++) {
-      uint32_t piv = col;
-      while (piv < nc && a[piv][col] == Fr::zero()) piv++;
-      if (piv == nc) return fail(SG_ERR_INVALID, "cosets: singular Vandermonde matrix");
-      std::swap(a[piv], a[col]);
-      const Fr inv = a[col][col].inv();
-      for (auto& v : a[col]) v = v * inv;
-      for (uint32_t r = 0; r < nc; r++) {
-        if (r == col || a[r][col] == Fr::zero()) continue;
-        const Fr f = a[r][col];
-        for (uint32_t q = 0; q < 2 * nc; q++) a[r][q] = a[r][q] - f * a[col][q];
-      }
-    }
-    std::memset(t.m, 0, sizeof(t.m));
-    for (uint32_t b = 0; b < nc; b++) {
-      const Fr d = gamma[b] - Fr::one();
-      if (d == Fr::zero()) return fail(SG_ERR_INVALID, "cosets: a coset inside the domain");
-      const Fr di = d.inv();
-      for (uint32_t tt = 0; tt < nc; tt++) {
-        const Fr v = a[tt][nc + b] * di;        // V^-1[t][b] / (gamma_b - 1)
-        std::memcpy(t.m[tt * MAX_COSETS + b], v.l, 32);
-      }
+      std::memcpy(&t.shift[b], plan.shift[b].l, 32);
+      std::memcpy(&inv_shift[b], plan.inv_shift[b].l, 32);
+      for (uint32_t tt = 0; tt < nc; tt++) std::memcpy(t.m[tt * MAX_COSETS + b], plan.m[tt * nc + b].l, 32);
     }
     const size_t n = (size_t)1 << k;
-    CHECK_HIP(hipMalloc(&t.fwd, sizeof(fp_words) * n * nc), "coset tables");
-    CHECK_HIP(hipMalloc(&t.inv, sizeof(fp_words) * n * nc), "coset tables");
-    hipError_t e = coset_fill_powers(t.fwd, t.shift, nc, k, c.stream);
+    hipError_t e = hipMalloc(&t.fwd, sizeof(fp_words) * n * nc);
+    if (e == hipSuccess) e = hipMalloc(&t.inv, sizeof(fp_words) * n * nc);
+    if (e == hipSuccess) e = coset_fill_powers(t.fwd, t.shift, nc, k, c.stream);
     if (e == hipSuccess) e = coset_fill_powers(t.inv, inv_shift, nc, k, c.stream);
     if (e == hipSuccess) e = host_wait_stream(c.stream);
-    if (e != hipSuccess) return hip_fail("coset tables", e);
+    if (e != hipSuccess) {   // (retired, not freed: a fill may still be running)
+      retire_device_memory(t.fwd);
+      retire_device_memory(t.inv);
+      return hip_fail("coset tables", e);
+    }
     it = c.coset_tables.emplace(key, t).first;
   }
   *out = &it->second;
@@ -286,12 +256,8 @@ extern "C" {
 static int coset_ntts(fp_words* const* ptrs, size_t count, uint32_t k, bool inverse, hipStream_t s) {
   const DomainConsts* dk;
   TRY(get_consts(k, &dk));
-  const size_t n = (size_t)1 << k;
-  const words8& w = inverse ? dk->omega_inv : dk->omega;
-  const words8* divisor = inverse ? &dk->n_inv : nullptr;
-  if (k <= 18) return batched_transforms(ptrs, nullptr, 0, count, k, w, divisor, nullptr, nullptr, s, "coset ntt batch");
-  for (size_t i = 0; i < count; i++) TRY(ntt_dev(ptrs[i], n, ptrs[i], k, w, divisor, nullptr, nullptr, s));
-  return SG_OK;
+  return transforms(ptrs, nullptr, 0, count, k, inverse ? dk->omega_inv : dk->omega, inverse ? &dk->n_inv : nullptr, nullptr, nullptr, s,
+                    "coset ntt batch");
 }
 int sg_coeff_to_cosets_batch_dev(const void* const* d_coeffs, void* const* d_out, size_t count, uint32_t k, uint32_t ext_k,
                                  uint32_t n_cosets, void* stream) {
@@ -304,7 +270,7 @@ int sg_coeff_to_cosets_batch_dev(const void* const* d_coeffs, void* const* d_out
   hipStream_t s = pick_stream(stream);
   TRY(sync_own_stream_into(s));
   const size_t n = (size_t)1 << k;
-  if (k <= 18 && !g_sh.param[kRowCosetScalePass].load()) {
+  if (ntt_batched(k) && !g_sh.param[kRowCosetScalePass].load()) {
     // the coset shift c_b^i rides on the load of the first NTT pass (a table of 2^261-domain words per coset, indexed like the
     // input): no pass over HBM of its own, and every block of every column is a vector of ONE batched launch per pass
     const DomainConsts* dk;
@@ -317,8 +283,7 @@ int sg_coeff_to_cosets_batch_dev(const void* const* d_coeffs, void* const* d_out
         srcs.push_back(static_cast<const fp_words*>(d_coeffs[j]));
         tabs.push_back(t->fwd + b * n);
       }
-    return batched_transforms(blocks.data(), srcs.data(), n, blocks.size(), k, dk->omega, nullptr, nullptr, tabs.data(), s,
-                              "coset ntt batch");
+    return transforms(blocks.data(), srcs.data(), n, blocks.size(), k, dk->omega, nullptr, nullptr, tabs.data(), s, "coset ntt batch");
   }
   std::vector<fp_words*> blocks;
   for (size_t first = 0; first < count; first += COSET_BATCH_MAX) {

@@ -55,6 +55,19 @@ class NttEngine {
     words8 omega_r;
     fp_words* tw;
   };
+  // `count` vectors of one size: data[v] is transformed in place (src == nullptr; plans of several passes go through `scratch`,
+  // count * 2^log_n elements) or receives the transform of src[v] (src_len elements, zero beyond) and serves as the
+  // intermediate.  nbatch: what the launch shape counts as the batch (0: a lone transform)
+  struct Job {
+    fp_words* const* data;
+    uint32_t count, nbatch;
+    const fp_words* const* src;
+    size_t src_len;
+    fp_words* scratch;
+    const words8 *scale, *pre3, *post3;
+    const fp_words* const* pre_tab;
+  };
+  hipError_t run(const Job& j, uint32_t log_n, const words8& omega, hipStream_t stream);
   hipError_t get_plan(uint32_t log_n, const words8& omega, const words8* scale, hipStream_t stream, const NttPlan** out);
   NttConfig cfg_;
   std::deque<NttPlan> plans_;

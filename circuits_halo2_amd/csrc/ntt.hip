@@ -32,8 +32,6 @@ SG_DEFINE_SIDE_PRIO_SETTER(ntt_set_side_prio)
 // post-scale, or 1^) which brings the value below 2r, then a conditional subtraction makes it
 // canonical for the 32-byte store.
 struct PassArgs {
-  const fp_words* in;
-  fp_words* out;
   const fp_words* tw_local;  // w_R^k in the 2^261 domain, k < R/2
   const fp_words* tw_pass;   // per-element twiddle in output order (nullptr: none)
   uint32_t log_r;            // log2 R  (DFT length of this pass)
@@ -51,12 +49,11 @@ struct PassArgs {
   uint32_t radix4;           // two DIT stages per sweep over the tile (four elements per thread)
   uint32_t pre[3][8];        // Montgomery-2^256 words, converted once per workgroup
   uint32_t post[3][8];
-  // batched launch (nbatch > 0): blockIdx.y selects the vector; same plan for all (small transforms are a chain
-  // of launches at their ~5 us floor: the 9 iNTTs of a proof become 3 launches instead of 27)
-  uint32_t nbatch;
+  // blockIdx.y selects the vector (a lone transform is vector 0 of a launch with grid.y = 1); same plan for all (small
+  // transforms are a chain of launches at their ~5 us floor: the 9 iNTTs of a proof become 3 launches instead of 27)
   const fp_words* in_b[NTT_BATCH_MAX];
   fp_words* out_b[NTT_BATCH_MAX];
-  // first pass of a batched launch: input element gi of vector y is multiplied by pre_tab_b[y][gi] (2^261-domain words) on load
+  // first pass: input element gi of vector y is multiplied by pre_tab_b[y][gi] (2^261-domain words) on load
   uint32_t pre_tab;
   const fp_words* pre_tab_b[NTT_BATCH_MAX];
 };
@@ -251,105 +248,79 @@ hipError_t NttEngine::get_plan(uint32_t log_n, const words8& omega, const words8
     words8 wr;
     err = omega_pow2(log_n - pl.l[i], &wr);
     if (err != hipSuccess) return err;
-    err = local_twiddles(wr, pl.l[i], stream, &pl.tw_local[i]);
+    err = local_twiddles(wr, pl.l[i], stream, &pl.tw_local[i]);   // (cached by the engine: nothing of the plan's to give back)
     if (err != hipSuccess) return err;
   }
-  words8 one_or_scale = scale ? *scale : omega;  // placeholder when unused
-  if (pl.npass == 2) {
-    err = hipMalloc(&pl.tw_pass[0], sizeof(fp_words) * n);
-    if (err != hipSuccess) return err;
-    fill_pass_twiddles<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(pl.tw_pass[0], omega, one_or_scale,
-                                                                         scale ? 1 : 0, 0, pl.l[0], pl.l[1], 0, log_n, 1);
-  } else if (pl.npass == 3) {
-    err = hipMalloc(&pl.tw_pass[0], sizeof(fp_words) * n);
-    if (err != hipSuccess) return err;
-    err = hipMalloc(&pl.tw_pass[1], sizeof(fp_words) * n);
-    if (err != hipSuccess) return err;
-    fill_pass_twiddles<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(pl.tw_pass[0], omega, one_or_scale,
-                                                                         scale ? 1 : 0, 1, pl.l[0], pl.l[1], pl.l[2], log_n, 0);
-    fill_pass_twiddles<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(pl.tw_pass[1], omega, one_or_scale, 0, 2,
-                                                                         pl.l[0], pl.l[1], pl.l[2], log_n, 1);
+  // one inter-pass table per pass but the last (fill_pass_twiddles: mode 0; modes 1 and 2): the first holds the scale, the last
+  // the factor 2^29.  A step that fails gives back the tables allocated so far.
+  auto give_back = [&](hipError_t e) {
+    for (fp_words* t : pl.tw_pass) retire_device_memory(t);
+    return e;
+  };
+  const words8 one_or_scale = scale ? *scale : omega;  // placeholder when unused
+  for (int t = 0; t < pl.npass - 1; t++) {
+    err = hipMalloc(&pl.tw_pass[t], sizeof(fp_words) * n);
+    if (err != hipSuccess) return give_back(err);
+    fill_pass_twiddles<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(pl.tw_pass[t], omega, one_or_scale, scale && t == 0 ? 1 : 0,
+                                                                         pl.npass == 2 ? 0 : 1 + t, pl.l[0], pl.l[1], pl.l[2], log_n,
+                                                                         t == pl.npass - 2 ? 1 : 0);
   }
   err = hipGetLastError();
-  if (err != hipSuccess) return err;
   // tables must be complete before any other stream may use the cached plan
-  err = host_wait_stream(stream);
-  if (err != hipSuccess) return err;
+  if (err == hipSuccess) err = host_wait_stream(stream);
+  if (err != hipSuccess) return give_back(err);
   plans_.push_back(pl);
   *out = &plans_.back();
   return hipSuccess;
 }
 
-// one launch of pass `i` of the plan: geometry, tile and workgroup from ntt_plan.h; the caller has filled the buffers, in_len and
-// the pre / post factors
-static hipError_t launch_pass(const NttConfig& cfg, const NttPlan& pl, int i, PassArgs& a, hipStream_t stream) {
-  const NttPassGeom g = ntt_pass_geom(NttFactors{pl.npass, {pl.l[0], pl.l[1], pl.l[2]}}, i);
-  a.tw_local = pl.tw_local[g.tw_local];
-  a.tw_pass = g.tw_pass < 0 ? nullptr : pl.tw_pass[g.tw_pass];
-  a.log_r = g.log_r; a.log_b = g.log_b; a.kind = g.kind; a.sig_lo = g.sig_lo; a.sig_hi = g.sig_hi; a.fold29 = g.fold29;
-  const NttPassShape s = ntt_pass_shape(cfg, g, pl.log_n, a.in_len, a.nbatch);
-  if (s.lds_bytes > NTT_LDS_BUDGET || s.threads > (s.radix4 ? NTT_MAX_THREADS_R4 : NTT_MAX_THREADS)) return hipErrorInvalidConfiguration;
-  a.skip = s.skip;
-  a.log_t = s.log_t;
-  a.radix4 = s.radix4;
-  if (s.radix4) hipLaunchKernelGGL(ntt_pass_r4, dim3(s.grid_x, s.grid_y), dim3(s.threads), s.lds_bytes, stream, a);
-  else hipLaunchKernelGGL(ntt_pass, dim3(s.grid_x, s.grid_y), dim3(s.threads), s.lds_bytes, stream, a);
-  return hipGetLastError();
-}
-
-// `count` in-place transforms of one size as ONE launch per pass.  scratch: count * 2^log_n elements (multi-pass plans)
-hipError_t NttEngine::transform_batch(fp_words* const* a, uint32_t count, fp_words* scratch, uint32_t log_n,
-                                      const words8& omega, const words8* scale, hipStream_t stream,
-                                      const fp_words* const* src, size_t src_len, const words8* pre3, const fp_words* const* pre_tab) {
-  if (count == 0) return hipSuccess;
-  if (pre_tab && (!src || src_len < ((size_t)1 << log_n))) return hipErrorInvalidValue;   // (the zero-padded load path does not take a table)
-  if (count > NTT_BATCH_MAX || log_n == 0) return hipErrorInvalidValue;
+// The passes of one job, one launch each: geometry, tile and workgroup of pass `i`, and what rides on it, from ntt_plan.h.
+hipError_t NttEngine::run(const Job& j, uint32_t log_n, const words8& omega, hipStream_t stream) {
+  const NttFactors f = ntt_factor(cfg_, log_n);
   const NttPlan* pl;
-  const bool fold_scale = ntt_scale_in_table(ntt_factor(cfg_, log_n), scale != nullptr, false);
-  hipError_t err = get_plan(log_n, omega, fold_scale ? scale : nullptr, stream, &pl);
+  hipError_t err = get_plan(log_n, omega, ntt_scale_in_table(f, j.scale, j.post3) ? j.scale : nullptr, stream, &pl);
   if (err != hipSuccess) return err;
   const size_t n = (size_t)1 << log_n;
-  // src == nullptr: in place (multi-pass plans go through `scratch`); otherwise out of place from src[i]
-  // (src_len <= n elements, zero beyond; optional pre-scaling by pre3[i % 3]) with a[i] as the intermediate
   PassArgs p{};
-  p.nbatch = count;
-  enum Where { DATA, MID };
-  bool first = true;
-  auto io = [&](Where in, Where out) {
-    for (uint32_t i = 0; i < count; i++) {
-      fp_words* mid = src ? a[i] : scratch + (size_t)i * n;
-      p.in_b[i] = (first && src) ? src[i] : in == DATA ? a[i] : mid;
-      p.out_b[i] = out == DATA ? a[i] : mid;
+  for (int i = 0; i < f.npass; i++) {
+    const NttPassRide r = ntt_pass_ride(f, i, j.src_len, j.scale, j.pre3, j.post3, j.pre_tab);
+    for (uint32_t v = 0; v < j.count; v++) {
+      fp_words* mid = j.src ? j.data[v] : j.scratch + (size_t)v * n;
+      p.in_b[v] = r.in == NTT_MID ? mid : j.src ? j.src[v] : j.data[v];
+      p.out_b[v] = r.out == NTT_MID ? mid : j.data[v];
+      if (r.pre_tab) p.pre_tab_b[v] = j.pre_tab[v];
     }
-    p.in_len = (first && src) ? (uint32_t)std::min(src_len, n) : (uint32_t)n;
-    p.pre3 = 0;
-    if (first && pre3) {
-      p.pre3 = 1;
-      for (int i = 0; i < 3; i++) std::memcpy(p.pre[i], pre3[i].l, 32);
-    }
-    p.pre_tab = 0;
-    if (first && pre_tab) {
-      p.pre_tab = 1;
-      for (uint32_t i = 0; i < count; i++) p.pre_tab_b[i] = pre_tab[i];
-    }
-    first = false;
-  };
-  auto last_scale = [&](bool last) {
-    p.post3 = 0;
-    if (last && scale && !fold_scale) {
-      p.post3 = 1;
-      for (int i = 0; i < 3; i++) std::memcpy(p.post[i], scale->l, 32);
-    }
-  };
-  // one pass: in place; several: the first writes the intermediate, the last the data, a middle one stays in the intermediate
-  for (int i = 0; i < pl->npass; i++) {
-    const bool last = i == pl->npass - 1;
-    io(i == 0 ? DATA : MID, last ? DATA : MID);
-    last_scale(last);
-    err = launch_pass(cfg_, *pl, i, p, stream);
+    p.in_len = r.in_len;
+    p.pre3 = r.pre3;
+    p.pre_tab = r.pre_tab;
+    p.post3 = r.post != NTT_POST_NONE;
+    if (r.pre3) std::memcpy(p.pre, j.pre3, sizeof p.pre);
+    for (int t = 0; t < 3 && p.post3; t++) std::memcpy(p.post[t], r.post == NTT_POST_CALLER ? j.post3[t].l : j.scale->l, 32);
+    const NttPassGeom g = ntt_pass_geom(f, i);
+    p.tw_local = pl->tw_local[g.tw_local];
+    p.tw_pass = g.tw_pass < 0 ? nullptr : pl->tw_pass[g.tw_pass];
+    p.log_r = g.log_r; p.log_b = g.log_b; p.kind = g.kind; p.sig_lo = g.sig_lo; p.sig_hi = g.sig_hi; p.fold29 = g.fold29;
+    const NttPassShape s = ntt_pass_shape(cfg_, g, log_n, p.in_len, j.nbatch);
+    if (s.lds_bytes > NTT_LDS_BUDGET || s.threads > (s.radix4 ? NTT_MAX_THREADS_R4 : NTT_MAX_THREADS)) return hipErrorInvalidConfiguration;
+    p.skip = s.skip;
+    p.log_t = s.log_t;
+    p.radix4 = s.radix4;
+    if (s.radix4) hipLaunchKernelGGL(ntt_pass_r4, dim3(s.grid_x, s.grid_y), dim3(s.threads), s.lds_bytes, stream, p);
+    else hipLaunchKernelGGL(ntt_pass, dim3(s.grid_x, s.grid_y), dim3(s.threads), s.lds_bytes, stream, p);
+    err = hipGetLastError();
     if (err != hipSuccess) return err;
   }
   return hipSuccess;
+}
+
+hipError_t NttEngine::transform_batch(fp_words* const* a, uint32_t count, fp_words* scratch, uint32_t log_n,
+                                      const words8& omega, const words8* scale, hipStream_t stream,
+                                      const fp_words* const* src, size_t src_len, const words8* pre3, const fp_words* const* pre_tab) {
+  const size_t n = (size_t)1 << log_n;
+  if (count == 0) return hipSuccess;
+  if (pre_tab && (!src || src_len < n)) return hipErrorInvalidValue;   // (the zero-padded load path does not take a table)
+  if (count > NTT_BATCH_MAX || log_n == 0) return hipErrorInvalidValue;
+  return run(Job{a, count, count, src, src ? src_len : n, scratch, scale, pre3, nullptr, pre_tab}, log_n, omega, stream);
 }
 
 hipError_t NttEngine::init() {
@@ -362,45 +333,13 @@ hipError_t NttEngine::init() {
 hipError_t NttEngine::transform(const fp_words* in, size_t in_len, fp_words* out, fp_words* scratch, uint32_t log_n,
                                 const words8& omega, const words8* scale, const words8* pre3, const words8* post3,
                                 hipStream_t stream) {
-  const NttPlan* pl;
-  // a plain scale is folded into the first inter-pass twiddle table when there is one
-  const bool fold_scale = ntt_scale_in_table(ntt_factor(cfg_, log_n), scale != nullptr, post3 != nullptr);
-  hipError_t err = get_plan(log_n, omega, fold_scale ? scale : nullptr, stream, &pl);
-  if (err != hipSuccess) return err;
-  if (log_n == 0) {
-    if (in != out) err = hipMemcpyAsync(out, in, sizeof(fp_words), hipMemcpyDeviceToDevice, stream);
+  if (log_n == 0) {   // one element: itself, times the plain scale
+    hipError_t err = in != out ? hipMemcpyAsync(out, in, sizeof(fp_words), hipMemcpyDeviceToDevice, stream) : hipSuccess;
     if (err == hipSuccess && scale && !post3) scale_kernel<<<1, 64, 0, stream>>>(out, *scale, 1);
     return err;
   }
-  PassArgs a{};
-  auto set_prepost = [&](bool first, bool last) {
-    a.pre3 = 0;
-    a.post3 = 0;
-    if (first && pre3) {
-      a.pre3 = 1;
-      for (int i = 0; i < 3; i++) std::memcpy(a.pre[i], pre3[i].l, 32);
-    }
-    if (last && post3) {
-      a.post3 = 1;
-      for (int i = 0; i < 3; i++) std::memcpy(a.post[i], post3[i].l, 32);
-    } else if (last && scale && !fold_scale) {
-      a.post3 = 1;
-      for (int i = 0; i < 3; i++) std::memcpy(a.post[i], scale->l, 32);
-    }
-  };
-  // multi-pass plans: the first pass writes the intermediate (`scratch` for an in-place call, else `out`), a middle pass works
-  // in place there, the last one writes `out`
-  fp_words* mid = in == out ? scratch : out;
-  for (int i = 0; i < pl->npass; i++) {
-    const bool first = i == 0, last = i == pl->npass - 1;
-    a.in = first ? in : mid;
-    a.out = last ? out : mid;
-    a.in_len = first ? (uint32_t)std::min<size_t>(in_len, (size_t)1 << log_n) : 1u << log_n;
-    set_prepost(first, last);
-    err = launch_pass(cfg_, *pl, i, a, stream);
-    if (err != hipSuccess) return err;
-  }
-  return hipSuccess;
+  // nbatch = 0: a lone transform keeps the latency shape whatever ntt.batch_min says
+  return run(Job{&out, 1, 0, in == out ? nullptr : &in, in_len, scratch, scale, pre3, post3, nullptr}, log_n, omega, stream);
 }
 
 hipError_t ntt_scale(fp_words* a, const words8& s, size_t n, hipStream_t stream) {

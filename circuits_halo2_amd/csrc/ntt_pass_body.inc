@@ -6,8 +6,8 @@
   side_kernel_prio();
   extern __shared__ uint4 lds[];
   typedef Fr29 P;
-  const fp_words* __restrict__ p_in = p.nbatch ? p.in_b[blockIdx.y] : p.in;
-  fp_words* __restrict__ p_out = p.nbatch ? p.out_b[blockIdx.y] : p.out;
+  const fp_words* __restrict__ p_in = p.in_b[blockIdx.y];
+  fp_words* __restrict__ p_out = p.out_b[blockIdx.y];
   const uint32_t R = 1u << p.log_r, T = 1u << p.log_t;
   const uint32_t E = R << p.log_t, H = (R >> 1) + 8;  // twiddles + 6 converted constants
   LdsTile d{lds, lds + E, reinterpret_cast<uint32_t*>(lds + 2 * E)};
@@ -134,36 +134,27 @@
 
   // write back: one closing product per element (or, with nothing to multiply by, a product-free reduction), then the
   // canonical 32-byte store
+  auto close_and_store = [&](f29 v, size_t go) {
+    if (p.tw_pass) {
+      v = f29_mul<P>(v, f29_load_r256<P>(p.tw_pass + go));
+      if (p.post3) v = f29_mul<P>(v, lds_get(w, CONST0 + 3 + (uint32_t)(go % 3)));
+    } else if (p.post3) {
+      v = f29_mul<P>(v, lds_get(w, CONST0 + 3 + (uint32_t)(go % 3)));
+    } else {
+      v = p.fold29 ? f29_mont_step<P>(v) : f29_reduce_small<P>(v);
+    }
+    f29_store_canonical<P>(p_out + go, v);
+  };
   if (p.kind == 0) {
     for (uint32_t e = tid; e < E; e += nthr) {
       uint32_t t = e & (T - 1), r = e >> p.log_t;
-      size_t go = base + t + ((size_t)r << p.log_b);
-      f29 v = lds_get(d, e);
-      if (p.tw_pass) {
-        v = f29_mul<P>(v, f29_load_r256<P>(p.tw_pass + go));
-        if (p.post3) v = f29_mul<P>(v, lds_get(w, CONST0 + 3 + (uint32_t)(go % 3)));
-      } else if (p.post3) {
-        v = f29_mul<P>(v, lds_get(w, CONST0 + 3 + (uint32_t)(go % 3)));
-      } else {
-        v = p.fold29 ? f29_mont_step<P>(v) : f29_reduce_small<P>(v);
-      }
-      f29_store_canonical<P>(p_out + go, v);
+      close_and_store(lds_get(d, e), base + t + ((size_t)r << p.log_b));
     }
   } else {
     for (uint32_t e = tid; e < E; e += nthr) {
       uint32_t r = e & (R - 1), t = e >> p.log_r;
       uint32_t b = b0 + t;
       uint32_t bp = (b >> p.sig_lo) + ((b & ((1u << p.sig_lo) - 1)) << p.sig_hi);
-      size_t go = ((size_t)bp << p.log_r) + r;
-      f29 v = lds_get(d, (r << p.log_t) + t);
-      if (p.tw_pass) {
-        v = f29_mul<P>(v, f29_load_r256<P>(p.tw_pass + go));
-        if (p.post3) v = f29_mul<P>(v, lds_get(w, CONST0 + 3 + (uint32_t)(go % 3)));
-      } else if (p.post3) {
-        v = f29_mul<P>(v, lds_get(w, CONST0 + 3 + (uint32_t)(go % 3)));
-      } else {
-        v = p.fold29 ? f29_mont_step<P>(v) : f29_reduce_small<P>(v);
-      }
-      f29_store_canonical<P>(p_out + go, v);
+      close_and_store(lds_get(d, (r << p.log_t) + t), ((size_t)bp << p.log_r) + r);
     }
   }

@@ -62,6 +62,14 @@ inline NttFactors ntt_factor(const NttConfig& cfg, uint32_t log_n) {
 // (as does every plan when the caller brings three post factors of its own)
 inline bool ntt_scale_in_table(const NttFactors& f, bool has_scale, bool has_post3) { return has_scale && !has_post3 && f.npass > 1; }
 
+// `count` transforms of 2^log_n points each go through the batched launches (one launch per pass for up to NTT_BATCH_MAX vectors)
+// up to this size: below it every launch of a lone transform sits at its ~5 us latency floor, and a 2^20 transform fills the
+// chip on its own, so from 2^19 on the transforms run one after the other
+static constexpr uint32_t NTT_BATCHED_MAX_LOG = 18;
+inline bool ntt_batched(uint32_t log_n) { return log_n >= 1 && log_n <= NTT_BATCHED_MAX_LOG; }
+// an in-place transform of several passes needs a scratch vector of 2^log_n elements: its first pass writes the intermediate
+inline bool ntt_needs_scratch(const NttConfig& cfg, uint32_t log_n, bool in_place) { return in_place && ntt_factor(cfg, log_n).npass > 1; }
+
 // pass `i` (0 = first launched) of a plan: the DFT over one index of the factorisation
 struct NttPassGeom {
   uint32_t log_r;            // log2 R  (DFT length of this pass)
@@ -97,6 +105,32 @@ inline NttPassGeom ntt_pass_geom(const NttFactors& f, int i) {
     }
   }
   return g;
+}
+
+// what rides on pass `i` of a job: the first pass reads the caller's source (the data itself for an in-place job; `in_len`
+// elements, zero beyond) with the pre factors and the load table, a middle pass works in place in the intermediate (the
+// scratch vector of an in-place job, else the data), the last pass writes the data and its store takes the caller's three
+// post factors, or the plain scale when no table holds it
+enum NttBuf : uint32_t { NTT_SOURCE, NTT_DATA, NTT_MID };
+enum NttPost : uint32_t { NTT_POST_NONE, NTT_POST_CALLER, NTT_POST_SCALE };
+struct NttPassRide {
+  uint32_t in_len;
+  bool pre3, pre_tab;
+  NttPost post;
+  NttBuf in, out;
+};
+inline NttPassRide ntt_pass_ride(const NttFactors& f, int i, size_t in_len, bool has_scale, bool has_pre3, bool has_post3, bool has_pre_tab) {
+  const NttPassGeom g = ntt_pass_geom(f, i);
+  const bool first = g.first, last = g.last;
+  const size_t n = (size_t)1 << (f.l[0] + f.l[1] + f.l[2]);
+  NttPassRide r{};
+  r.in_len = (uint32_t)(first ? std::min(in_len, n) : n);
+  r.pre3 = first && has_pre3;
+  r.pre_tab = first && has_pre_tab;
+  r.post = !last ? NTT_POST_NONE : has_post3 ? NTT_POST_CALLER : has_scale && !ntt_scale_in_table(f, has_scale, has_post3) ? NTT_POST_SCALE : NTT_POST_NONE;
+  r.in = first ? NTT_SOURCE : NTT_MID;
+  r.out = last ? NTT_DATA : NTT_MID;
+  return r;
 }
 
 // leading stages of a zero-padded FIRST pass that can be skipped: rows r >= in_len >> log_b are zero

@@ -332,7 +332,6 @@ void destroy_context(Context* c) {
   c->stage_a.release();
   c->stage_b.release();
   c->scratch.release();
-  for (auto& kv : c->ntt_scratch) kv.second.release();
   for (auto& kv : c->stream_scratch) kv.second.release();
   for (auto& kv : c->lookup_work) kv.second.buf.release();
   if (c->h_mail) (void)hipHostFree(c->h_mail);
@@ -453,15 +452,15 @@ int ntt_dev(const fp_words* in, size_t in_len, fp_words* out, uint32_t log_n, co
             const words8* scale, const words8* pre3, const words8* post3, hipStream_t s) {
   Context& c = *g_ctx;
   if (log_n > 28) return fail(SG_ERR_INVALID, "log_n exceeds the 2-adicity (28) of BN254 Fr");
-  fp_words* scratch = nullptr;
-  if (in == out && log_n > c.ntt.config().max_single_log) {
-    DevBuf<uint8_t>& buf = c.ntt_scratch[s];
-    hipError_t e = buf.reserve((size_t)32 << log_n);
+  // the scratch vector of a lone transform is the stream's own (slot 13: the batched transforms' slot 3 keeps its size), so
+  // that transforms enqueued on a side stream never share it with work in flight on another stream
+  uint8_t* scratch = nullptr;
+  if (ntt_needs_scratch(c.ntt.config(), log_n, in == out)) {
+    hipError_t e = scratch_for(s, 13, (size_t)32 << log_n, &scratch);
     if (e != hipSuccess) return hip_fail("ntt scratch", e);
-    scratch = reinterpret_cast<fp_words*>(buf.p);
   }
   // plans are generated on the same stream the transform runs on
-  hipError_t e = c.ntt.transform(in, in_len, out, scratch, log_n, omega, scale, pre3, post3, s);
+  hipError_t e = c.ntt.transform(in, in_len, out, reinterpret_cast<fp_words*>(scratch), log_n, omega, scale, pre3, post3, s);
   if (e != hipSuccess) return hip_fail("ntt", e);
   return SG_OK;
 }

@@ -7,6 +7,7 @@ arbitrary coset values.  tests/test_coset_cases_cpu.py ties both to halo2's exte
 without a GPU.  How many cosets there are is the caller's choice: 1 .. 8, at most 2^ext."""
 import numpy as np
 
+import ntt_cases
 from oracle import oracle as O
 from oracle import pyref as PR
 
@@ -14,7 +15,7 @@ R = PR.R
 MAX_COSETS = 8
 KS = (3, 5, 7, 8, 9)           # 8 rows (less than a wave), 32, 128 (two blocks per workgroup), 256 (one workgroup), 512
 PAIRS = ((1, 1), (1, 2), (2, 3), (2, 4), (3, 5), (3, 6), (3, 7), (3, 8), (4, 8))     # (ext, n_cosets)
-LONG = (19, 1, 2)              # above k = 18 the 2^k transforms of the blocks run one by one
+LONG = (ntt_cases.BATCHED_MAX_LOG + 1, 1, 2)     # above the batched plans the 2^k transforms of the blocks run one by one
 
 
 def domain_args(ext, n_cosets):

@@ -47,18 +47,17 @@ int main() {
     }
     const NttFactors f = ntt_factor(cfg, log_n);
     const bool in_table = ntt_scale_in_table(f, scale != 0, post3 != 0);
-    std::printf("npass=%d l=%u,%u,%u scale_in_table=%d", f.npass, f.l[0], f.l[1], f.l[2], in_table ? 1 : 0);
+    // (scratch: whether an in-place call of this size needs the scratch vector)
+    std::printf("npass=%d l=%u,%u,%u scale_in_table=%d batched=%d scratch=%d", f.npass, f.l[0], f.l[1], f.l[2], in_table ? 1 : 0,
+                ntt_batched(log_n) ? 1 : 0, ntt_needs_scratch(cfg, log_n, true) ? 1 : 0);
     for (int i = 0; i < f.npass; i++) {
       const NttPassGeom g = ntt_pass_geom(f, i);
-      // what the engine's callers of launch_pass fill in: the first pass reads the caller's (shorter) input with its factors,
-      // the last pass's store takes the post factors, or the plain scale when no table holds it
-      const uint32_t len = g.first ? std::min(in_len, 1u << log_n) : 1u << log_n;
-      const NttPassShape s = ntt_pass_shape(cfg, g, log_n, len, nbatch);
-      const bool post = g.last && (post3 || (scale && !in_table));
+      const NttPassRide r = ntt_pass_ride(f, i, in_len, scale != 0, pre3 != 0, post3 != 0, pre_tab != 0);
+      const NttPassShape s = ntt_pass_shape(cfg, g, log_n, r.in_len, nbatch);
       std::printf(" | kind=%c log_r=%u log_b=%u sig=%u,%u skip=%u big=%d log_t=%u E=%zu r4=%u threads=%u grid=%u,%u lds=%zu pre3=%d pre_tab=%d "
                   "post3=%d fold29=%u tw_pass=%d",
                   g.kind ? 'X' : 'Y', g.log_r, g.log_b, g.sig_lo, g.sig_hi, s.skip, s.big ? 1 : 0, s.log_t, s.elems, s.radix4, s.threads,
-                  s.grid_x, s.grid_y, s.lds_bytes, g.first && pre3 ? 1 : 0, g.first && pre_tab ? 1 : 0, post ? 1 : 0, g.fold29, g.tw_pass);
+                  s.grid_x, s.grid_y, s.lds_bytes, r.pre3 ? 1 : 0, r.pre_tab ? 1 : 0, r.post != NTT_POST_NONE ? 1 : 0, g.fold29, g.tw_pass);
     }
     std::printf("\n");
   }

@@ -9,6 +9,7 @@ import functools
 LDS_BUDGET = 160 * 1024
 BATCH_MAX = 32
 MAX_PASS_LOG = 11
+BATCHED_MAX_LOG = 18          # several transforms of one size share their launches up to 2^18 points; above, one after the other
 NO_LIMIT = 0x7FFFFFFF
 
 DEFAULTS = {"ntt.max_single_log": 11, "ntt.max_multi_log": 9, "ntt.tile_log": 9, "ntt.threads": 256, "ntt.big_tile_log": 10,
@@ -118,12 +119,14 @@ def plan(params, log_n, in_len=None, nbatch=0, scale=False, pre3=False, post3=Fa
         passes.append(dict(g, **s, big=big, big_by_batch=big and by_batch, big_by_size=big and by_size, want_r4=want_r4,
                            in_len=in_len if first else n, grid_y=nbatch or 1, pre3=bool(first and pre3), pre_tab=bool(first and pre_tab),
                            post3=bool(last and (post3 or (scale and not in_table)))))
-    return dict(npass=npass, l=l, scale_in_table=in_table, passes=passes)
+    # batched: a call with several vectors of this size goes through the batched launches; scratch: an in-place call needs a scratch vector
+    return dict(npass=npass, l=l, scale_in_table=in_table, batched=1 <= log_n <= BATCHED_MAX_LOG, scratch=npass > 1, passes=passes)
 
 
 def plan_line(p):
     """the plan as tests/cpp/ntt_plan_check.cpp prints it"""
-    out = f"npass={p['npass']} l={p['l'][0]},{p['l'][1]},{p['l'][2]} scale_in_table={int(p['scale_in_table'])}"
+    out = (f"npass={p['npass']} l={p['l'][0]},{p['l'][1]},{p['l'][2]} scale_in_table={int(p['scale_in_table'])} batched={int(p['batched'])} "
+           f"scratch={int(p['scratch'])}")
     for s in p["passes"]:
         out += (f" | kind={s['kind']} log_r={s['log_r']} log_b={s['log_b']} sig={s['sig'][0]},{s['sig'][1]} skip={s['skip']} big={int(s['big'])} "
                 f"log_t={s['log_t']} E={s['E']} r4={s['r4']} threads={s['threads']} grid={s['grid_x']},{s['grid_y']} lds={s['lds']} "
@@ -174,7 +177,7 @@ def transforms_of(case):
     raise AssertionError(op)
 
 
-NARROWED_K = 19
+NARROWED_K = BATCHED_MAX_LOG + 1
 COSETS, COSET_EXT = 5, 3       # EvaluationDomain(6, k): five cosets of an extended domain of 2^(k + 3) rows
 
 

@@ -78,6 +78,33 @@ def test_the_solve_matrix_inverts_the_vandermonde_matrix():
                 assert sum(m[t][b] * (g[b] - 1) * pow(g[b], u, cc.R) for b in range(nc)) % cc.R == int(t == u), (ext, nc, t, u)
 
 
+def test_the_librarys_coset_arithmetic_is_the_restated_one(tmp_path):
+    """csrc/coset_plan.h (what coset_tables_for uploads), through tests/cpp/coset_plan_check.cpp and plain g++: at every shape of
+    the grid the shifts, their inverses and the solve matrix are coset_cases.shifts, their modular inverses and
+    coset_cases.solve_matrix, word for word (the 32 bytes in memory); equal gammas are refused as a singular matrix, a coset
+    inside the domain as such"""
+    import os
+    import subprocess
+    from oracle import pyref as PR
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "coset_plan_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(root, "circuits_halo2_amd", "csrc"),
+                           os.path.join(root, "tests", "cpp", "coset_plan_check.cpp"), "-o", exe])
+    word = lambda x: PR.fr_to_bytes(x % cc.R).hex()
+    shapes = [s for s, _ in cc.shapes()]
+    lines = [f"{k} {ext} {nc} {word(PR.ZETA)} {word(PR.omega_for(k + ext))}" for k, ext, nc in shapes]
+    lines += [f"5 1 2 {word(PR.ZETA)} {word(1)}", f"5 1 2 {word(1)} {word(PR.omega_for(6))}"]
+    got = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, check=True).stdout.split("\n")[:-1]
+    assert len(got) == len(lines)
+    for (k, ext, nc), line in zip(shapes, got):
+        c = cc.shifts(k, ext, nc)
+        m = cc.solve_matrix(k, ext, nc)
+        want = ("ok shift=" + ",".join(word(x) for x in c) + " inv_shift=" + ",".join(word(pow(x, -1, cc.R)) for x in c)
+                + " m=" + ",".join(word(m[t][b]) for t in range(nc) for b in range(nc)))
+        assert line == want, (k, ext, nc)
+    assert got[len(shapes):] == ["singular", "inside_domain"]
+
+
 def test_the_fills_are_what_they_say():
     fills = dict(cc.value_fills())
     assert list(fills) == ["random", "zero", "max_word", "minus_one", "one_hot_last_row"]

@@ -227,6 +227,27 @@ def _run(gpu, O, case):
     return out
 
 
+def test_a_transform_of_one_element_is_that_element_times_the_scale(gpu):
+    """log_n = 0 runs no pass at all: by the definition the element itself (sg_ntt_fr_dev), times the divisor (sg_intt_fr_dev, and
+    every vector of sg_ntt_fr_batch_dev with a divisor)"""
+    import torch
+    from circuits_halo2_amd import ffi
+    L, r = ffi.lib(), _R()
+    one, d = fr_np([1]), 0x1234567
+    xs = [r - 1, 0x89ABCDEF0123, 0]
+    zero, stream = C.c_uint32(0), ffi.current_stream_ptr()
+    plain, inverse, batch = [_dev(fr_np([x])) for x in xs], [_dev(fr_np([x])) for x in xs], [_dev(fr_np([x])) for x in xs]
+    for a, b in zip(plain, inverse):
+        ffi.check(L.sg_ntt_fr_dev(ffi.dev_ptr(a), ffi.ptr(one), zero, stream))
+        ffi.check(L.sg_intt_fr_dev(ffi.dev_ptr(b), ffi.ptr(one), ffi.ptr(fr_np([d])), zero, stream))
+    ffi.check(L.sg_ntt_fr_batch_dev(_ptrs(batch), C.c_size_t(len(batch)), ffi.ptr(one), ffi.ptr(fr_np([d])), zero, stream))
+    torch.cuda.synchronize()
+    for x, a, b, c in zip(xs, plain, inverse, batch):
+        _same(a, fr_np([x]), f"sg_ntt_fr_dev, log_n = 0, x = {x:#x}")
+        _same(b, fr_np([x * d % r]), f"sg_intt_fr_dev, log_n = 0, x = {x:#x}")
+        _same(c, fr_np([x * d % r]), f"sg_ntt_fr_batch_dev, log_n = 0, x = {x:#x}")
+
+
 @pytest.mark.parametrize("case", CASES, ids=[c["name"] for c in CASES])
 def test_ntt_case_against_the_oracle(gpu, O, case):
     import torch
