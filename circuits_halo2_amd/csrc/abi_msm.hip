@@ -1,5 +1,8 @@
-// C ABI, MSM family: sg_msm_*, the SRS cache, sg_commit* and the commit combiner (summa_gpu.hip holds the core).
+// C ABI, MSM family: sg_msm_*, the SRS cache, sg_commit* and the commit combiner's entry points (summa_gpu.hip holds the core).
+// Glue: what a commitment decides on the host is commit_plan.h's, the combiner's logic commit_combiner.h's (both HIP-free).
 #include "abi_internal.h"
+#include "commit_combiner.h"
+#include "commit_plan.h"
 
 using namespace sg;
 namespace {
@@ -17,6 +20,22 @@ int srs_for_commit(uint64_t handle, size_t n, Srs* out) {
   if (!find_srs(handle, out)) return fail(SG_ERR_INVALID, "unknown SRS handle");
   if (n > ((size_t)1 << out->k)) return fail(SG_ERR_INVALID, "sg_commit: polynomial longer than the SRS");
   return SG_OK;
+}
+// what commit_plan.h's rules ask of an SRS
+SrsTables tables_of(const Srs& s) {
+  SrsTables t;
+  t.k = s.k;
+  for (int b = 0; b < 3; b++) t.tab[b] = {s.tab[b].table != nullptr, s.tab[b].c, s.tab[b].n};
+  return t;
+}
+// the jobs behind a handle of sg_msm_g1_many_begin (a copy, as find_srs); take: the handle ends here
+bool find_many(uint64_t handle, ManyJobs* out, bool take = false) {
+  std::lock_guard<std::mutex> lk(g_sh.mu);
+  auto it = g_sh.many.find(handle);
+  if (it == g_sh.many.end()) return false;
+  *out = it->second;
+  if (take) g_sh.many.erase(it);
+  return true;
 }
 // 2^k points of g and of g_lagrange into device memory of the cache's own, under a new handle: from host memory, or (from_device)
 // by device-to-device copies on `st` (e.g. out of the receive buffers of an RCCL broadcast)
@@ -81,34 +100,23 @@ int sg_msm_g1_dev(const void* d_scalars, const void* d_bases, size_t n, void* st
 // engines (two streams) while a third stream carries the copies: chunk i's job runs while chunk i + 1 is still travelling,
 // and one job's latency chains run under the other's accumulation.  The K partial points are added on the host.
 //   [S0 B0] front(0) { back(i) [S i+1 B i+1] finish(i-1) front(i+1) } ... finish, sum
-// -- chunk i + 1 crosses the link while chunk i's accumulation runs.  K: "msm.host_chunks" (0 = by size: 2 from 2^18 pairs; more
-// chunks lose: every job brings its own latency chains, and small kernels beside an accumulation run slowly).
-static constexpr size_t MSM_HOST_SPLIT_MIN = (size_t)1 << 18;
+// -- chunk i + 1 crosses the link while chunk i's accumulation runs.  The order and what a failure leaves of it:
+// run_chunk_pipeline (commit_plan.h), which also holds K's rule (host_chunk_count) and the chunks' bounds.
 static int msm_host_chunked(const uint8_t* scalars, const uint8_t* bases_host, const g1_affine_mem* d_bases_resident, size_t n,
                             uint8_t out_affine[64]) {
   Context& c = *g_ctx;
-  hipError_t e = c.stage_a.reserve(n ? n * 32 : 1);
-  if (e == hipSuccess && bases_host) e = c.stage_b.reserve(n ? n * 64 : 1);
-  if (e != hipSuccess) return hip_fail("staging buffer", e);
-  const fp_words* d_s = reinterpret_cast<const fp_words*>(c.stage_a.p);
-  const g1_affine_mem* d_b = bases_host ? reinterpret_cast<const g1_affine_mem*>(c.stage_b.p) : d_bases_resident;
-  uint32_t K = (uint32_t)g_sh.param[kRowHostChunks].load();
-  if (K == 0) K = n < MSM_HOST_SPLIT_MIN ? 1u : 2u;   // measured at 2^20 (profiles/r04_sweeps/host_chunks.txt): 2 is the best for both entry points
-  K = std::min<uint32_t>(K, 8u);
-  if (n < 2 * (size_t)K) K = 1;
+  const uint32_t K = host_chunk_count(g_sh.param[kRowHostChunks].load(), n);
   if (K == 1) {
-    if (n) {
-      CHECK_HIP(hipMemcpyAsync(c.stage_a.p, scalars, n * 32, hipMemcpyHostToDevice, c.stream), "H2D copy");
-      if (bases_host) CHECK_HIP(hipMemcpyAsync(c.stage_b.p, bases_host, n * 64, hipMemcpyHostToDevice, c.stream), "H2D copy");
-    }
-    e = c.msm.run(d_s, d_b, n, c.stream, out_affine, nullptr);
+    TRY(upload(c.stage_a, scalars, n * 32, c.stream));
+    if (bases_host) TRY(upload(c.stage_b, bases_host, n * 64, c.stream));
+    const hipError_t e = c.msm.run(reinterpret_cast<const fp_words*>(c.stage_a.p),
+                                   bases_host ? reinterpret_cast<const g1_affine_mem*>(c.stage_b.p) : d_bases_resident, n, c.stream, out_affine, nullptr);
     if (e != hipSuccess) return hip_fail("msm", e);
     return SG_OK;
   }
-  MsmEngine* eng[2] = {&c.msm, &c.msm_b};
-  hipStream_t st[2] = {c.stream, c.bstream[0]}, copy = c.bstream[1];
-  std::vector<size_t> lo(K + 1);
-  for (uint32_t i = 0; i <= K; i++) lo[i] = n * i / K;
+  hipError_t e = c.stage_a.reserve(n * 32);
+  if (e == hipSuccess && bases_host) e = c.stage_b.reserve(n * 64);
+  if (e != hipSuccess) return hip_fail("staging buffer", e);
   std::vector<uint8_t> part(64 * (size_t)K, 0);
   std::vector<hipEvent_t> ev_s(K, nullptr), ev_b(K, nullptr);
   struct Events {
@@ -123,64 +131,53 @@ static int msm_host_chunked(const uint8_t* scalars, const uint8_t* bases_host, c
     CHECK_HIP(hipEventCreateWithFlags(&ev_s[i], hipEventDisableTiming), "event");
     if (bases_host) CHECK_HIP(hipEventCreateWithFlags(&ev_b[i], hipEventDisableTiming), "event");
   }
+  struct Ops {
+    Context& c;
+    const uint8_t *scalars, *bases_host;
+    const fp_words* d_s;
+    const g1_affine_mem* d_b;
+    std::vector<size_t> lo;
+    std::vector<hipEvent_t>&ev_s, &ev_b;
+    uint8_t* part;
+    MsmEngine* eng[2];
+    hipStream_t st[2], copy;
+    size_t len(uint32_t i) const { return lo[i + 1] - lo[i]; }
+    hipError_t copy_scalars(uint32_t i) {
+      const hipError_t e = hipMemcpyAsync(c.stage_a.p + lo[i] * 32, scalars + lo[i] * 32, len(i) * 32, hipMemcpyHostToDevice, copy);
+      return e == hipSuccess ? hipEventRecord(ev_s[i], copy) : e;
+    }
+    hipError_t copy_bases(uint32_t i) {
+      if (!bases_host) return hipSuccess;
+      const hipError_t e = hipMemcpyAsync(c.stage_b.p + lo[i] * 64, bases_host + lo[i] * 64, len(i) * 64, hipMemcpyHostToDevice, copy);
+      return e == hipSuccess ? hipEventRecord(ev_b[i], copy) : e;
+    }
+    hipError_t front(uint32_t i) {
+      const hipError_t e = hipStreamWaitEvent(st[i & 1], ev_s[i], 0);
+      return e == hipSuccess ? eng[i & 1]->enqueue_front(d_s + lo[i], d_b + lo[i], len(i), st[i & 1], part + 64 * i, nullptr) : e;
+    }
+    hipError_t back(uint32_t i) {
+      const hipError_t e2 = bases_host ? hipStreamWaitEvent(st[i & 1], ev_b[i], 0) : hipSuccess;
+      const hipError_t e3 = eng[i & 1]->enqueue_back();    // (always: an engine left with an open job would poison the lane's next call)
+      // (the wait failed but the job went out: closed here, for the driver finishes no job whose back reports a failure)
+      if (e2 != hipSuccess && e3 == hipSuccess) (void)eng[i & 1]->finish();
+      return e2 != hipSuccess ? e2 : e3;
+    }
+    hipError_t finish(uint32_t i) { return eng[i & 1]->finish(); }
+  } ops{c, scalars, bases_host, reinterpret_cast<const fp_words*>(c.stage_a.p),
+        bases_host ? reinterpret_cast<const g1_affine_mem*>(c.stage_b.p) : d_bases_resident, host_chunk_bounds(n, K), ev_s, ev_b, part.data(),
+        {&c.msm, &c.msm_b}, {c.stream, c.bstream[0]}, c.bstream[1]};
   // the staging buffers may still be read by earlier work of the lane's stream: the other two streams start behind it
   CHECK_HIP(hipEventRecord(c.ev_in, c.stream), "event");
-  CHECK_HIP(hipStreamWaitEvent(st[1], c.ev_in, 0), "stream wait");
-  CHECK_HIP(hipStreamWaitEvent(copy, c.ev_in, 0), "stream wait");
-  hipError_t err = hipSuccess;          // the first failure; from the first front on, every open job is still closed in order
-  auto copy_scalars = [&](uint32_t i) {
-    if (err != hipSuccess) return;
-    err = hipMemcpyAsync(c.stage_a.p + lo[i] * 32, scalars + lo[i] * 32, (lo[i + 1] - lo[i]) * 32, hipMemcpyHostToDevice, copy);
-    if (err == hipSuccess) err = hipEventRecord(ev_s[i], copy);
-  };
-  auto copy_bases = [&](uint32_t i) {
-    if (err != hipSuccess || !bases_host) return;
-    err = hipMemcpyAsync(c.stage_b.p + lo[i] * 64, bases_host + lo[i] * 64, (lo[i + 1] - lo[i]) * 64, hipMemcpyHostToDevice, copy);
-    if (err == hipSuccess) err = hipEventRecord(ev_b[i], copy);
-  };
-  int state[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // per chunk: 0 nothing, 1 front enqueued, 2 back enqueued, 3 finished
-  auto front = [&](uint32_t i) {
-    if (err != hipSuccess) return;
-    err = hipStreamWaitEvent(st[i & 1], ev_s[i], 0);
-    if (err == hipSuccess) err = eng[i & 1]->enqueue_front(d_s + lo[i], d_b + lo[i], lo[i + 1] - lo[i], st[i & 1], part.data() + 64 * i, nullptr);
-    if (err == hipSuccess) state[i] = 1;
-  };
-  auto back = [&](uint32_t i) {
-    if (state[i] != 1) return;
-    hipError_t e2 = bases_host ? hipStreamWaitEvent(st[i & 1], ev_b[i], 0) : hipSuccess;
-    const hipError_t e3 = eng[i & 1]->enqueue_back();    // (always: an engine left with an open job would poison the lane's next call)
-    state[i] = e3 == hipSuccess ? 2 : 3;
-    if (err == hipSuccess) err = e2 != hipSuccess ? e2 : e3;
-  };
-  auto finish = [&](uint32_t i) {
-    if (state[i] != 2) return;
-    const hipError_t e2 = eng[i & 1]->finish();
-    state[i] = 3;
-    if (err == hipSuccess) err = e2;
-  };
+  CHECK_HIP(hipStreamWaitEvent(ops.st[1], c.ev_in, 0), "stream wait");
+  CHECK_HIP(hipStreamWaitEvent(ops.copy, c.ev_in, 0), "stream wait");
   // every job of the call is "one of several in flight" from the start: a first accumulation launched at three waves per SIMD
   // (a job that believes it has the device to itself) would leave the second job's front end no registers to run in
   struct InFlight {
     InFlight() { msm_hold_in_flight(true); }
     ~InFlight() { msm_hold_in_flight(false); }
   } in_flight_guard;
-  copy_scalars(0);
-  copy_bases(0);
-  front(0);
-  for (uint32_t i = 0; i < K; i++) {
-    back(i);                              // (waits for chunk i's sort; then its accumulation is on the device ...)
-    if (i + 1 < K) {
-      copy_scalars(i + 1);                // ... and runs while the next chunk crosses the link (a copy from pageable memory blocks the host)
-      copy_bases(i + 1);
-      if (i >= 1) finish(i - 1);          // the engine chunk i + 1 runs on
-      front(i + 1);
-    }
-  }
-  for (uint32_t i = 0; i < K; i++) {       // whatever is still open (the last two jobs; everything after a failure)
-    back(i);
-    finish(i);
-  }
-  if (err != hipSuccess) return hip_fail("msm (host chunks)", err);
+  e = run_chunk_pipeline(K, ops);
+  if (e != hipSuccess) return hip_fail("msm (host chunks)", e);
   return sg_g1_sum_affine(part.data(), K, out_affine);
 }
 
@@ -218,16 +215,9 @@ static int msm_batch_locked(const void* const* d_scalars, const void* const* d_b
   // inputs are ordered on the caller's stream
   CHECK_HIP(hipEventRecord(c.ev_in, pick_stream(stream)), "event");
   for (auto& bs : c.bstream) CHECK_HIP(hipStreamWaitEvent(bs, c.ev_in, 0), "stream wait");
-  // consecutive MSMs of equal length are fused into one job (all kernels span the whole
-  // group); groups alternate between the two engines
-  struct Group { size_t first, count; };
-  std::vector<Group> groups;
-  for (size_t i = 0; i < count;) {
-    size_t lim = tab ? eng[0]->max_fused_fixed(*tab, n[i]) : eng[0]->max_fused(n[i]), g = 1;
-    while (i + g < count && n[i + g] == n[i] && g < lim) g++;
-    groups.push_back({i, g});
-    i += g;
-  }
+  // consecutive MSMs of equal length are fused into one job; groups alternate between the two engines
+  const std::vector<FusedGroup> groups =
+      fused_groups(n, count, [&](size_t len) { return tab ? eng[0]->max_fused_fixed(*tab, len) : eng[0]->max_fused(len); });
   hipError_t e = hipSuccess;
   for (size_t gi = 0; gi < groups.size() && e == hipSuccess; gi++) {
     const int k = (int)(gi & 1);
@@ -235,7 +225,7 @@ static int msm_batch_locked(const void* const* d_scalars, const void* const* d_b
       e = eng[k]->finish();
       if (e != hipSuccess) break;
     }
-    const Group& g = groups[gi];
+    const FusedGroup& g = groups[gi];
     if (tab) {  // d_bases then holds one window table per MSM (all with tab's plan)
       uint64_t diff_mask = 0;
       for (size_t m = 0; diff && m < g.count; m++) diff_mask |= (uint64_t)(diff[g.first + m] ? 1 : 0) << m;
@@ -425,22 +415,19 @@ int sg_srs_device_ptrs(uint64_t handle, const void** d_g, const void** d_g_lagra
   if (k) *k = srs.k;
   return SG_OK;
 }
-// basis 2 = a Lagrange column taken in difference form (same commitment as basis 1): possible when the prefix-sum table
-// exists and the column has the full 2^k rows
-static bool diff_form_ready(const Srs& s, size_t n) { return s.tab[2].table != nullptr && n == ((size_t)1 << s.k); }
+// one commitment against the basis and table resolve_basis (commit_plan.h) names
 static hipError_t commit_run(const Srs& s, int basis, const fp_words* d_scalars, size_t n, hipStream_t stream,
                              uint8_t out_affine[64], MsmTimings* tm = nullptr) {
   MsmEngine& eng = g_ctx->msm;
-  const bool diff = basis == 2 && diff_form_ready(s, n);
-  if (basis == 2 && !diff) basis = 1;
-  if (s.tab[basis].table && n) {
+  const BasisChoice ch = resolve_basis(tables_of(s), basis, n);
+  if (ch.fixed && n) {
     const fp_words* sc[1] = {d_scalars};
-    hipError_t e = eng.enqueue_front_fixed(sc, s.tab[basis], 1, n, stream, out_affine, tm, nullptr, diff ? 1u : 0u);
+    hipError_t e = eng.enqueue_front_fixed(sc, s.tab[ch.table], 1, n, stream, out_affine, tm, nullptr, ch.diff ? 1u : 0u);
     if (e == hipSuccess) e = eng.enqueue_back();
     if (e == hipSuccess) e = eng.finish();
     return e;
   }
-  return eng.run(d_scalars, basis ? s.g_lagrange : s.g, n, stream, out_affine, tm);
+  return eng.run(d_scalars, ch.basis ? s.g_lagrange : s.g, n, stream, out_affine, tm);
 }
 int sg_commit_dev_timed(uint64_t srs_handle, int basis, const void* d_scalars, size_t n, void* stream,
                         uint8_t out_affine[64], sg_msm_timings* timings) {
@@ -470,44 +457,12 @@ int sg_commit_batch_dev(uint64_t srs_handle, int basis, const void* const* d_sca
   Srs s;
   TRY(srs_for_commit(srs_handle, n, &s));
   std::vector<size_t> ns(count, n);
-  const bool diff = basis == 2 && diff_form_ready(s, n);
-  if (basis == 2 && !diff) basis = 1;
-  const bool fixed = s.tab[basis].table != nullptr;
-  std::vector<const void*> bases(count, fixed ? (const void*)s.tab[basis].table : (const void*)(basis ? s.g_lagrange : s.g));
-  std::vector<uint8_t> flags(count, diff ? 1 : 0);
-  return msm_batch_locked(d_scalars, bases.data(), fixed ? &s.tab[basis] : nullptr, ns.data(), count, stream, out_affine, flags.data());
+  const BasisChoice ch = resolve_basis(tables_of(s), basis, n);
+  std::vector<const void*> bases(count, ch.fixed ? (const void*)s.tab[ch.table].table : (const void*)(ch.basis ? s.g_lagrange : s.g));
+  std::vector<uint8_t> flags(count, ch.diff ? 1 : 0);
+  return msm_batch_locked(d_scalars, bases.data(), ch.fixed ? &s.tab[ch.table] : nullptr, ns.data(), count, stream, out_affine, flags.data());
 }
-// the same with one basis per polynomial (0 = g, 1 = g_lagrange): e.g. the grand-product commitments (Lagrange)
-// and the random polynomial (coefficients) of one prover phase as ONE fused job
-// ---- commit combiner.  Proofs in flight on several host threads (circuits_halo2_amd/batch.py) each issue five commitment
-// jobs; alone, every job pays its own sort front-end, bucket reduction and host tail, and the jobs of different threads
-// compete for the chip.  A thread that has declared itself (sg_commit_combine_begin) hands its sg_commit_batch*_dev calls
-// to the combiner instead: the first caller to find no job running becomes the runner, waits a bounded time for the
-// other declared threads to arrive (they do: after one fused job all of them get their points at the same moment and
-// reach their next commitment together), takes EVERYTHING pending with the same SRS and length and runs it as ONE
-// fused job on a lane of its own; callers that arrive while a job runs form the next one.  No caller ever waits for a
-// thread that might not come -- only for a deadline -- so a failed or finished proof cannot block the others.
-struct CommitReq {
-  uint64_t srs;
-  size_t n, count;
-  const int* basis;
-  const void* const* scalars;
-  uint8_t* out;
-  hipEvent_t ready;      // recorded on the caller's stream after its inputs were enqueued
-  int rc = SG_OK;
-  bool done = false;
-  char err[256] = "";
-};
-struct Combiner {
-  std::mutex mu;
-  std::condition_variable cv;
-  std::deque<CommitReq*> pending;
-  int runners = 0;                       // fused jobs running now
-  int busy = 0;                          // requests inside those jobs
-  int members = 0;                       // threads between sg_commit_combine_begin and _end
-  std::atomic<uint64_t> jobs{0}, requests{0};   // statistics: fused jobs run, requests served
-  std::atomic<uint64_t> isolated{0};     // members re-run alone after their fused job failed as a whole
-};
+// ---- commit combiner (commit_combiner.h): what it needs of the device and of this library
 Combiner g_comb;
 thread_local bool t_combine = false;
 thread_local hipEvent_t t_ready = nullptr;
@@ -515,145 +470,46 @@ thread_local hipEvent_t t_ready = nullptr;
 static int commit_batch_mixed_core(uint64_t srs_handle, const int* basis, const void* const* d_scalars, size_t count, size_t n,
                                    void* stream, uint8_t* out_affine);
 
-// runs on the runner's thread: one fused job for all requests of `batch` (same SRS, same n)
-static void combiner_run_unguarded(const std::vector<CommitReq*>& batch);
-static void combiner_run(const std::vector<CommitReq*>& batch) {
-  try {
-    combiner_run_unguarded(batch);
-  } catch (const std::exception& e) {   // (allocation failures of the host vectors: every member learns of it)
-    for (CommitReq* r : batch) {
-      r->rc = SG_ERR_NOMEM;
-      std::snprintf(r->err, sizeof r->err, "commit combiner: %s", e.what());
-    }
-  }
-}
-static void combiner_run_unguarded(const std::vector<CommitReq*>& batch) {
-  std::vector<int> basis;
-  std::vector<const void*> scalars;
-  size_t total = 0;
-  for (CommitReq* r : batch) total += r->count;
-  basis.reserve(total);
-  scalars.reserve(total);
-  for (CommitReq* r : batch)
-    for (size_t i = 0; i < r->count; i++) {
-      basis.push_back(r->basis[i]);
-      scalars.push_back(r->scalars[i]);
-    }
-  std::vector<uint8_t> out(64 * total);
+// the members of `job` as one job on a lane of its own, whose stream waits for every member's inputs
+static int combiner_run_job(const CommitJob& job, char err[sizeof(CommitReq::err)]) {
   int rc;
   {
-    LaneHold hold;     // the job's own lane: its stream waits for every member's inputs
+    LaneHold hold;
     rc = hold.rc;
-    if (rc == SG_OK) {
-      for (CommitReq* r : batch) {
-        hipError_t e = hipStreamWaitEvent(g_ctx->stream, r->ready, 0);
-        if (e != hipSuccess) { rc = hip_fail("commit combiner: stream wait", e); break; }
-      }
+    for (size_t m = 0; m < job.n_members && rc == SG_OK; m++) {
+      const hipError_t e = hipStreamWaitEvent(g_ctx->stream, static_cast<hipEvent_t>(job.members[m]->ready), 0);
+      if (e != hipSuccess) rc = hip_fail("commit combiner: stream wait", e);
     }
-    if (rc == SG_OK && batch.size() > 1 && g_sh.param[kRowFailNextFusedJob].exchange(0)) rc = fail(SG_ERR_NOMEM, "commit combiner: injected failure of a fused job");
-    else if (rc == SG_OK) rc = commit_batch_mixed_core(batch[0]->srs, basis.data(), scalars.data(), total, batch[0]->n, g_ctx->stream, out.data());
+    if (rc == SG_OK) rc = commit_batch_mixed_core(job.srs, job.basis, job.scalars, job.polys, job.n, g_ctx->stream, job.out);
   }
-  size_t at = 0;
-  for (CommitReq* r : batch) {
-    r->rc = rc;
-    if (rc == SG_OK) std::memcpy(r->out, out.data() + 64 * at, 64 * r->count);
-    else std::snprintf(r->err, sizeof r->err, "%s", g_err);
-    at += r->count;
-  }
-  if (rc != SG_OK && batch.size() > 1) {
-    // The fused job failed AS A WHOLE -- out of device memory at this size, one member's bad pointer or stale handle.  One
-    // member's fault must not cost the others their proofs: every member gets a job of its own (same lane discipline:
-    // the job's stream waits for that member's inputs) and its own return value and message.
-    for (CommitReq* r : batch) {
-      LaneHold hold;
-      int rc1 = hold.rc;
-      if (rc1 == SG_OK) {
-        const hipError_t e = hipStreamWaitEvent(g_ctx->stream, r->ready, 0);
-        if (e != hipSuccess) rc1 = hip_fail("commit combiner: stream wait", e);
-      }
-      if (rc1 == SG_OK) rc1 = commit_batch_mixed_core(r->srs, r->basis, r->scalars, r->count, r->n, g_ctx->stream, r->out);
-      r->rc = rc1;
-      if (rc1 != SG_OK) std::snprintf(r->err, sizeof r->err, "%s", g_err);
-      else r->err[0] = 0;
-      g_comb.isolated.fetch_add(1);
-    }
-  }
-  g_comb.jobs.fetch_add(1);
-  g_comb.requests.fetch_add(batch.size());
+  if (rc != SG_OK) std::snprintf(err, sizeof(CommitReq::err), "%s", g_err);
+  return rc;
 }
-
 static int commit_combined(uint64_t srs_handle, const int* basis, const void* const* d_scalars, size_t count, size_t n,
                            void* stream, uint8_t* out_affine) {
   if (!t_ready) CHECK_HIP(hipEventCreateWithFlags(&t_ready, hipEventDisableTiming), "event");
   CHECK_HIP(hipEventRecord(t_ready, pick_stream(stream)), "event");
   CommitReq req{srs_handle, n, count, basis, d_scalars, out_affine, t_ready};
-  std::unique_lock<std::mutex> lk(g_comb.mu);
-  g_comb.pending.push_back(&req);
-  g_comb.cv.notify_all();                         // a runner waiting for stragglers counts again
-  while (!req.done) {
-    const bool mine_pending = std::find(g_comb.pending.begin(), g_comb.pending.end(), &req) != g_comb.pending.end();
-    if (!mine_pending || g_comb.runners >= g_sh.param[kRowCombineRunners].load()) {   // my request is inside a running job, or no runner slot is free
-      g_comb.cv.wait(lk);
-      continue;
-    }
-    g_comb.runners++;                             // this thread runs the next job
-    // the bounded wait shrinks with the company that can still come: a thread is a member for the whole of its proof, not
-    // only around its commitments, so at the tail of a batch the few proofs left would otherwise sit out the full wait
-    // (5 ms in batch.prove_batch) at every one of their five jobs for members that are busy elsewhere
-    const int may_come = std::max(1, g_comb.members - g_comb.busy - (int)g_comb.pending.size());
-    const int wait_us = std::min(g_sh.param[kRowCombineWaitUs].load(), 400 * may_come);
-    const auto deadline = std::chrono::steady_clock::now() + std::chrono::microseconds(wait_us);
-    // wait for company: until `target` requests are pending, or every declared thread that is not inside a running job
-    // has arrived, or the deadline
-    while ((int)g_comb.pending.size() < std::min(g_sh.param[kRowCombineTarget].load(), g_comb.members - g_comb.busy))
-      if (g_comb.cv.wait_until(lk, deadline) == std::cv_status::timeout) break;
-    // everything pending with the first request's SRS and length, up to MAX_FUSED polynomials
-    if (g_comb.pending.empty()) {   // another runner took everything meanwhile (this thread's request included)
-      g_comb.runners--;
-      g_comb.cv.notify_all();
-      continue;
-    }
-    std::vector<CommitReq*> batch;
-    size_t polys = 0;
-    CommitReq* first = g_comb.pending.front();
-    for (auto it = g_comb.pending.begin(); it != g_comb.pending.end();) {
-      CommitReq* r = *it;
-      if (r->srs == first->srs && r->n == first->n && polys + r->count <= MAX_FUSED) {
-        batch.push_back(r);
-        polys += r->count;
-        it = g_comb.pending.erase(it);
-      } else {
-        ++it;
-      }
-    }
-    g_comb.busy += (int)batch.size();
-    lk.unlock();
-    combiner_run(batch);
-    lk.lock();
-    for (CommitReq* r : batch) r->done = true;
-    g_comb.busy -= (int)batch.size();
-    g_comb.runners--;
-    g_comb.cv.notify_all();
-  }
-  if (req.rc != SG_OK) std::snprintf(g_err, sizeof g_err, "%s", req.err);
-  return req.rc;
+  const int rc = g_comb.submit(
+      req, combiner_run_job,
+      [](CombinerKnob k) {
+        return g_sh.param[k == CombinerKnob::runners ? kRowCombineRunners : k == CombinerKnob::wait_us ? kRowCombineWaitUs : kRowCombineTarget].load();
+      },
+      [] { return g_sh.param[kRowFailNextFusedJob].exchange(0) != 0; });
+  if (rc != SG_OK) std::snprintf(g_err, sizeof g_err, "%s", req.err);
+  return rc;
 }
 
 int sg_commit_combine_begin(void) {
   if (t_combine) return SG_OK;
   t_combine = true;
-  std::lock_guard<std::mutex> lk(g_comb.mu);
-  g_comb.members++;
+  g_comb.join();
   return SG_OK;
 }
 int sg_commit_combine_end(void) {
   if (!t_combine) return SG_OK;
   t_combine = false;
-  {
-    std::lock_guard<std::mutex> lk(g_comb.mu);
-    g_comb.members--;
-    g_comb.cv.notify_all();          // a runner waiting for this thread stops counting it
-  }
+  g_comb.leave();
   if (t_ready) {                     // this thread's requests have all returned: nothing waits on the event any more
     (void)hipEventDestroy(t_ready);
     t_ready = nullptr;
@@ -667,6 +523,8 @@ int sg_commit_combine_stats(uint64_t* jobs, uint64_t* requests) {
   return SG_OK;
 }
 
+// sg_commit_batch_dev with one basis per polynomial (0 = g, 1 = g_lagrange): e.g. the grand-product commitments (Lagrange)
+// and the random polynomial (coefficients) of one prover phase as ONE fused job
 int sg_commit_batch_mixed_dev(uint64_t srs_handle, const int* basis, const void* const* d_scalars, size_t count, size_t n,
                               void* stream, uint8_t* out_affine) {
   if (count && (!d_scalars || !out_affine || !basis)) return fail(SG_ERR_INVALID, "sg_commit_batch_mixed: bad argument");
@@ -681,47 +539,27 @@ static int commit_batch_mixed_core(uint64_t srs_handle, const int* basis, const 
   LOCKED_CTX();
   Srs s;
   TRY(srs_for_commit(srs_handle, n, &s));
-  // fixed-base only when both tables exist with one plan; otherwise the generic fused path over g / g_lagrange
-  const bool fixed = s.tab[0].table && s.tab[1].table && s.tab[0].c == s.tab[1].c && s.tab[0].n == s.tab[1].n;
-  // difference form (basis 2) needs the prefix-sum table on the same plan; otherwise such a column is an ordinary Lagrange one
-  const bool diff_ok = fixed && diff_form_ready(s, n) && s.tab[2].c == s.tab[0].c && s.tab[2].n == s.tab[0].n;
+  const MixedChoice m = resolve_mixed(tables_of(s), basis, count, n);
   std::vector<size_t> ns(count, n);
   std::vector<const void*> bases(count);
-  std::vector<uint8_t> flags(count, 0);
-  bool all_sparse = count > 0;
-  for (size_t i = 0; i < count; i++) {
-    const int want = basis[i] & ~SG_BASIS_SPARSE;
-    all_sparse = all_sparse && (basis[i] & SG_BASIS_SPARSE);
-    const int b = want == 2 ? (diff_ok ? 2 : 1) : want;
-    flags[i] = b == 2;
-    bases[i] = fixed ? (const void*)s.tab[b].table : (const void*)(b ? s.g_lagrange : s.g);
-  }
-  // A job whose columns are all witness-like (mostly zeros and small values: few entries, some of them in heavy buckets) is a
-  // latency chain of one task length whatever its size: tasks of 8 instead of 16 halve it (a proof's first commitment job
-  // 1.07 -> 1.00 ms) where dense jobs lose by them (profiles/r04_sweeps/task_length_by_phase.txt).  A hint, never semantics.
+  for (size_t i = 0; i < count; i++) bases[i] = m.fixed ? (const void*)s.tab[m.b[i]].table : (const void*)(m.b[i] ? s.g_lagrange : s.g);
+  // the task length of a small all-sparse job (sparse_hint_applies), for this job only
   struct SegRestore {
     Context& c;
     uint32_t seg;
     ~SegRestore() { msm_set(c, &MsmConfig::log_seg, (int)seg); }
   } seg_restore{*g_ctx, g_ctx->msm.config().log_seg};
-  // (only for jobs small enough for the 2-D reduction, which adds up to eight partial sums per bucket itself: a fused job of many
-  // proofs' columns goes through merge rounds, and shorter tasks would add one)
-  if (all_sparse && fixed && count <= 5 && g_ctx->msm.config().log_seg == 0 && n >= ((size_t)1 << 14))
-    msm_set(*g_ctx, &MsmConfig::log_seg, 3);
-  return msm_batch_locked(d_scalars, bases.data(), fixed ? &s.tab[0] : nullptr, ns.data(), count, stream, out_affine, flags.data());
+  if (sparse_hint_applies(m.all_sparse, m.fixed, count, g_ctx->msm.config().log_seg, n)) msm_set(*g_ctx, &MsmConfig::log_seg, 3);
+  return msm_batch_locked(d_scalars, bases.data(), m.fixed ? &s.tab[0] : nullptr, ns.data(), count, stream, out_affine, m.flags.data());
 }
 int sg_commit(uint64_t srs_handle, int basis, const uint8_t* scalars, size_t n, uint8_t out_affine[64]) {
   if (!out_affine || (n && !scalars) || basis < 0 || basis > 2) return fail(SG_ERR_INVALID, "sg_commit: bad argument");
   LOCKED_CTX();
   Srs sr;
   TRY(srs_for_commit(srs_handle, n, &sr));
-  {
-    // no window table for this basis (sg_srs_precompute not called): the generic MSM over the resident bases, in chunks, so that
-    // the scalars' upload and one job's latency chains run under another job's accumulation (msm_host_chunked)
-    const int b = (basis == 2 && !diff_form_ready(sr, n)) ? 1 : basis;
-    if (b != 2 && !sr.tab[b].table && n >= MSM_HOST_SPLIT_MIN)
-      return msm_host_chunked(scalars, nullptr, b ? sr.g_lagrange : sr.g, n, out_affine);
-  }
+  const SrsTables t = tables_of(sr);
+  if (commit_goes_in_chunks(t, basis, n))
+    return msm_host_chunked(scalars, nullptr, resolve_basis(t, basis, n).basis ? sr.g_lagrange : sr.g, n, out_affine);
   TRY(upload(g_ctx->stage_a, scalars, n * 32, g_ctx->stream));
   hipError_t e = commit_run(sr, basis, reinterpret_cast<const fp_words*>(g_ctx->stage_a.p), n, g_ctx->stream, out_affine);
   if (e != hipSuccess) return hip_fail("msm", e);
@@ -773,12 +611,7 @@ int sg_msm_g1_many_sums(uint64_t handle, const uint32_t* ranges, uint32_t count,
     if (ranges[2 * r] > ranges[2 * r + 1]) return fail(SG_ERR_INVALID, "sg_msm_g1_many_sums: a range that ends before it starts");
   LOCKED_CTX();
   ManyJobs m;
-  {
-    std::lock_guard<std::mutex> lk(g_sh.mu);
-    auto it = g_sh.many.find(handle);
-    if (it == g_sh.many.end()) return fail(SG_ERR_INVALID, "sg_msm_g1_many_sums: unknown handle");
-    m = it->second;
-  }
+  if (!find_many(handle, &m)) return fail(SG_ERR_INVALID, "sg_msm_g1_many_sums: unknown handle");
   ManyRanges rg{};
   for (uint32_t r = 0; r < count; r++) {
     if (ranges[2 * r + 1] > m.jobs) return fail(SG_ERR_INVALID, "sg_msm_g1_many_sums: a range beyond the last job");
@@ -802,13 +635,7 @@ int sg_msm_g1_many_sums(uint64_t handle, const uint32_t* ranges, uint32_t count,
 int sg_msm_g1_many_end(uint64_t handle) {
   LOCKED_CTX();
   ManyJobs gone;
-  {
-    std::lock_guard<std::mutex> lk(g_sh.mu);
-    auto it = g_sh.many.find(handle);
-    if (it == g_sh.many.end()) return fail(SG_ERR_INVALID, "sg_msm_g1_many_end: unknown handle");
-    gone = it->second;
-    g_sh.many.erase(it);
-  }
+  if (!find_many(handle, &gone, true)) return fail(SG_ERR_INVALID, "sg_msm_g1_many_end: unknown handle");
   // freed, not retired (as sg_srs_free does): a verifier that runs for days would otherwise pile up 16 KB per proof; begin and every
   // sums call waited for their kernels, so nothing reads S now
   (void)hipFree(gone.S);
