@@ -1,6 +1,7 @@
 // C ABI, Merkle sum tree family: the inclusion circuit's keygen columns and sg_mst_* -- leaves, levels and whole trees, entries from
 // names and decimal balances, the in-place update and the circuit's witness (summa_gpu.hip holds the core).
 #include "abi_internal.h"
+#include "mst_csv.h"
 #include "mst_entries.h"
 #include "mst_update_plan.h"
 
@@ -120,6 +121,55 @@ int sg_mst_entries_dev(const uint8_t* name_bytes, const uint64_t* name_off, cons
   CHECK_HIP(mst_entries_launch(d, reinterpret_cast<const uint64_t*>(d + at_name_off), d + at_digits,
                                reinterpret_cast<const uint64_t*>(d + at_digit_off), n, rows, n_currencies, d_usernames, d_balances, s),
             "sg_mst_entries");
+  return SG_OK;
+}
+// The same two arrays from the text of a snapshot CSV that already lies on the device (mst_csv.h has the rules and the passes,
+// mst_entries.hip the kernels).  Two calls, because the host sizes the outputs by the row count: the scan ends in one small
+// copy and a wait, and so does the split, whose problem word the host reads before anything is hashed.  What is wrong with
+// the arguments is refused before the device is touched; what is unusual about the text is reported, never refused.
+void sg_mst_csv_geometry(uint32_t* tile_bytes, uint32_t* row_cap) {
+  if (tile_bytes) *tile_bytes = MST_CSV_TILE;
+  if (row_cap) *row_cap = MST_CSV_ROW_CAP;
+}
+int sg_mst_csv_scan_dev(const void* d_bytes, uint64_t len, uint64_t body_off, void* d_tile_scratch, uint64_t* n_rows_out,
+                        uint32_t* flags_out, void* stream) {
+  if (!d_bytes || !d_tile_scratch || !n_rows_out || !flags_out) return fail(SG_ERR_INVALID, "sg_mst_csv_scan: null argument");
+  if (body_off > len || len - body_off >= (1ull << 32) || ((uintptr_t)d_tile_scratch & 3)) return refuse("sg_mst_csv_scan", "bad size");
+  const uint64_t body_len = len - body_off, n_tiles = mst_csv_tiles(body_len);
+  LOCKED_CTX();
+  hipStream_t s = pick_stream(stream);
+  uint32_t* tiles = static_cast<uint32_t*>(d_tile_scratch);
+  CHECK_HIP(mst_csv_scan_launch(static_cast<const uint8_t*>(d_bytes) + body_off, body_len, tiles, s), "sg_mst_csv_scan");
+  uint32_t result[2];
+  TRY(download(reinterpret_cast<uint8_t*>(result), tiles + n_tiles, sizeof result, s));
+  *n_rows_out = result[0];
+  *flags_out = result[1];
+  return SG_OK;
+}
+int sg_mst_csv_entries_dev(const void* d_bytes, uint64_t len, uint64_t body_off, const void* d_tile_scratch, uint32_t delimiter,
+                           uint32_t n_currencies, uint64_t n_rows, uint64_t rows, void* d_span_scratch, void* d_usernames,
+                           void* d_balances, uint64_t* problem_out, void* stream) {
+  if (!d_bytes || !d_tile_scratch || !d_span_scratch || !d_usernames || !d_balances || !problem_out)
+    return fail(SG_ERR_INVALID, "sg_mst_csv_entries: null argument");
+  const bool delimiter_ok = delimiter < 256 && delimiter != '\n' && delimiter != '\r' && !(delimiter >= '0' && delimiter <= '9') && !mst_csv_forbidden((uint8_t)delimiter);
+  // a row takes a byte of the body at least (its newline, or the last row's text)
+  const bool sizes_ok = body_off < len && len - body_off < (1ull << 32) && n_rows != 0 && n_rows <= len - body_off && rows >= n_rows &&
+                        rows < (1ull << 32) && !((uintptr_t)d_tile_scratch & 3) && !((uintptr_t)d_span_scratch & 7) && delimiter_ok;
+  if (const char* problem = shape_problem(n_currencies, 0, sizes_ok)) return refuse("sg_mst_csv_entries", problem);
+  const uint64_t body_len = len - body_off;
+  const uint8_t* body = static_cast<const uint8_t*>(d_bytes) + body_off;
+  uint64_t* words = static_cast<uint64_t*>(d_span_scratch);
+  uint64_t* d_problem = words + mst_csv_span_words(n_rows, n_currencies);
+  LOCKED_CTX();
+  hipStream_t s = pick_stream(stream);
+  CHECK_HIP(mst_csv_split_launch(body, body_len, static_cast<const uint32_t*>(d_tile_scratch), (uint8_t)delimiter, n_currencies, n_rows, words,
+                                 d_problem, s),
+            "sg_mst_csv_entries: split");
+  uint64_t problem = 0;
+  TRY(download(reinterpret_cast<uint8_t*>(&problem), d_problem, sizeof problem, s));
+  *problem_out = problem == MST_CSV_NO_PROBLEM ? 0 : problem;
+  if (*problem_out) return SG_OK;                            // the outputs stay unwritten
+  CHECK_HIP(mst_csv_entries_launch(body, words, n_rows, rows, n_currencies, d_usernames, d_balances, s), "sg_mst_csv_entries");
   return SG_OK;
 }
 // New balances for m leaves of a built tree, in place (mst.rs:169-204 for many leaves at once; witness.hip has the kernels).

@@ -27,11 +27,15 @@ EXPORTS = [
     "sg_fr_batch_invert_dev", "sg_fr_prefix_product_dev", "sg_fr_mul_dev", "sg_fr_kate_division_dev", "sg_fr_kate_division_batch_dev", "sg_fr_count_noncanonical_dev", "sg_fr_lincomb_dev", "sg_fr_lincomb_low_dev", "sg_permutation_product_dev",
     "sg_lookup_product_dev", "sg_grand_products_dev", "sg_quotient_permutation_dev", "sg_quotient_lookup_dev", "sg_quotient_gates_dev", "sg_mst_leaves_dev", "sg_mst_level_dev", "sg_mst_build_dev", "sg_mst_entries_dev", "sg_mst_inclusion_witness_dev", "sg_msm_g1_dev_timed", "sg_commit_dev_timed", "sg_fr_lincomb_sets_dev", "sg_quotient_numerator_cosets_dev", "sg_fr_flag_noncanonical_dev", "sg_lookup_permute_small_async_dev", "sg_lookup_permute_dev", "sg_lookup_permute_async_dev", "sg_grand_products_closing_dev", "sg_fr_kate_division_rem_dev", "sg_set_param", "sg_get_param", "sg_msm_launch_log", "sg_abi_version", "sg_time_ntt_dev",
     "sg_msm_g1_many_begin", "sg_msm_g1_many_sums", "sg_msm_g1_many_end", "sg_mst_update_dev",
+    "sg_mst_csv_geometry", "sg_mst_csv_scan_dev", "sg_mst_csv_entries_dev",
 ]
 # argument types of the entry points that declare them: ctypes then converts plain Python integers and refuses a wrong count
 ARGTYPES = {
     "sg_mst_update_dev": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                           C.c_void_p, C.c_void_p],
+    "sg_mst_csv_scan_dev": [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "sg_mst_csv_entries_dev": [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p,
+                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
 }
 
 

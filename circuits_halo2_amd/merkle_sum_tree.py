@@ -4,8 +4,10 @@ utils/csv_parser.rs, utils/operation_helpers.rs:10-12) with the hashing on the G
 
 Host logic kept here: CSV parsing, keccak256(username) -> field element, decimal balances ->
 field elements, zero-entry padding to 2^depth, Merkle-proof extraction (tree.rs:85-137).
-DeviceMerkleSumTree.from_entries / from_csv leave only the CSV parsing here: names and decimal balances
-become field elements on the device (sg_mst_entries_dev) and the tree stays in HBM; DeviceMerkleSumTree.update_leaf /
+DeviceMerkleSumTree.from_entries / from_csv_sorted leave only the CSV parsing here: names and decimal balances
+become field elements on the device (sg_mst_entries_dev) and the tree stays in HBM; DeviceMerkleSumTree.from_csv leaves the
+header line here and reads the rest of the file on the device too (sg_mst_csv_scan_dev / sg_mst_csv_entries_dev), unless the
+file is outside the device reader's subset of CSV text; DeviceMerkleSumTree.update_leaf /
 update_leaves / update_leaves_at change balances there in place (sg_mst_update_dev).
 """
 from __future__ import annotations
@@ -450,6 +452,13 @@ def pack_balances(flat):
     return text[~comma], digit_off
 
 
+# what sg_mst_csv_scan_dev and sg_mst_csv_entries_dev report of a file outside the device reader's subset (include/summa_gpu.h:
+# SG_MST_CSV_FLAG_*, SG_MST_CSV_ROW_*), in the words of csv_fallback_reason
+_CSV_FLAGS = ((0x40000000, "a quote, NUL or non-ASCII byte"), (0x80000000, "a carriage return without a line feed"))
+_CSV_ROW_PROBLEMS = {1: "longer than csv's field limit", 2: "empty", 3: "not n_currencies + 1 fields", 4: "an empty balance",
+                     5: "a balance that is not decimal digits", 6: "row starts out of order"}
+
+
 class DeviceMerkleSumTree(_Tree):
     """A Merkle sum tree whose leaves are already field elements on the device (a snapshot of 2^depth users: username
     field elements and balances as Montgomery Fr), built and KEPT in HBM: level-major node arrays as `sg_mst_build_dev`
@@ -461,15 +470,37 @@ class DeviceMerkleSumTree(_Tree):
     integer balances: the leaves' field elements are made on the device (sg_mst_entries_dev) and nothing comes back.  Such
     a tree also knows its entries by name -- `entries`, `get_entry`, `index_of_username`, `cryptocurrencies`, `is_sorted`, and
     the `entry` of a Merkle proof carries the name, as MerkleSumTree's do; after the plain constructor `entries` is None.
+    `from_csv` reads the file's text on the device where it can (`csv_ingest`); such a tree parses the file on the host only
+    when its entries are first asked for by name, which `root`, `public_inputs_many`, `update_leaves_at` and the provers never do.
 
     `update_leaf`, `update_leaves` and `update_leaves_at` change balances in place (sg_mst_update_dev): the leaves and the nodes
     above them are re-hashed on the device, in the arrays the tree was built from (`d_balances` of the plain constructor is
     written too), and nothing comes back but the root when it is next asked for."""
 
-    entries = None            # [(name, balances)] padded with (None, [0] * n_currencies): trees built from entries only
+    _entries = None           # [(name, balances)] padded with (None, [0] * n_currencies): trees built from entries only
     _name_index = None        # {name: first index}, made by the first update_leaves
     is_sorted = False
     cryptocurrencies = ()
+    csv_ingest = None         # from_csv: "device" (the file's text was read on the device) or "host" (parse_csv_to_entries)
+    csv_fallback_reason = None    # ... and why the host read it
+    _csv_lazy = None          # a device-read tree whose entries nobody has asked for: (path, {leaf index: balances set since})
+
+    @property
+    def entries(self):
+        """None for a tree built from field elements.  A tree whose CSV the device read parses the file for them only now, on the
+        host: the proving paths never ask."""
+        if self._entries is None and self._csv_lazy is not None:
+            path, changed = self._csv_lazy
+            parsed, _ = parse_csv_to_entries(path, self.n_currencies)
+            parsed += [(None, [0] * self.n_currencies)] * ((1 << self.depth) - len(parsed))
+            for i, bal in changed.items():
+                parsed[i] = (parsed[i][0], bal)
+            self._entries, self._csv_lazy = parsed, None
+        return self._entries
+
+    @entries.setter
+    def entries(self, value):
+        self._entries, self._csv_lazy = value, None
 
     def __init__(self, d_usernames, d_balances, depth: int, n_currencies: int):
         import torch
@@ -512,6 +543,75 @@ class DeviceMerkleSumTree(_Tree):
         tree.cryptocurrencies = []
         return tree
 
+    @classmethod
+    def from_csv(cls, path: str, n_currencies: int, n_bytes: int = 8):
+        """mst.rs:74-87 with the file's text read where the tree is built (sg_mst_csv_scan_dev, sg_mst_csv_entries_dev): the
+        host parses the header line alone, the device finds the rows and fields and hashes and folds them in place.  The
+        device takes a strict subset of CSV text (include/summa_gpu.h) and judges no data: any other file goes the way every
+        file went before, parse_csv_to_entries and from_entries, which accepts or refuses it.  `csv_ingest` says which way
+        it was, `csv_fallback_reason` why the host's.  After the device's `entries` is made on first use, from the file."""
+        tree, reason = cls._from_csv_on_device(path, n_currencies)
+        if tree is None:
+            tree = super().from_csv(path, n_currencies, n_bytes)
+            tree.csv_ingest, tree.csv_fallback_reason = "host", reason
+        return tree
+
+    @classmethod
+    def _from_csv_on_device(cls, path: str, n_currencies: int):
+        """-> (tree, None), or (None, why the device does not take this file)"""
+        import torch
+        if not 1 <= n_currencies <= 64:
+            return None, "n_currencies outside 1..64"
+        data = np.fromfile(path, dtype=np.uint8)
+        line, eol, _ = data[:1 << 16].tobytes().partition(b"\n")
+        if not eol:
+            return None, "no line end in the first 64 KiB"
+        body_off, size = len(line) + 1, int(data.size)
+        line = line[:-1] if line.endswith(b"\r") else line
+        if not line.isascii() or any(c in line for c in b'"\r\0'):
+            return None, "header line: a quote, carriage return, NUL or non-ASCII byte"
+        delim = ";" if b";" in line else ","
+        header = line.decode().split(delim)
+        crypto = [tuple(h.split("_")[1:]) for h in header[1:]]
+        if (len(header) - 1 != n_currencies or header[0] != "username"
+                or any(len(h.split("_")) != 3 or h.split("_")[0] != "balance" for h in header[1:])):
+            return None, "header line: not username and n_currencies balance_<name>_<chain> columns"
+        if body_off == size:
+            return None, "no rows"
+        if size - body_off >= 1 << 32:
+            return None, "a body of 4 GiB or more"
+        L = ffi.lib()
+        tile, cap = C.c_uint32(0), C.c_uint32(0)
+        L.sg_mst_csv_geometry(C.byref(tile), C.byref(cap))
+        pad = -body_off % 16                                  # the body on a 16-byte boundary: the kernels' wide loads
+        d_file = torch.empty(pad + size, dtype=torch.uint8, device="cuda")
+        d_file[pad:].copy_(torch.from_numpy(data))
+        d_text = d_file[pad:]
+        d_tiles = torch.empty(-(-(size - body_off) // tile.value) + 2, dtype=torch.int32, device="cuda")
+        n_rows, flags = C.c_uint64(0), C.c_uint32(0)
+        stream = ffi.current_stream_ptr()
+        ffi.check(L.sg_mst_csv_scan_dev(ffi.dev_ptr(d_text), size, body_off, ffi.dev_ptr(d_tiles), C.byref(n_rows), C.byref(flags), stream))
+        if flags.value:
+            return None, " and ".join(text for bit, text in _CSV_FLAGS if flags.value & bit)
+        n = n_rows.value
+        if n == 0:
+            return None, "no rows"
+        depth = max(0, (n - 1).bit_length())
+        rows = 1 << depth
+        d_users = torch.empty(32 * rows, dtype=torch.uint8, device="cuda")
+        d_bals = torch.empty(32 * rows * n_currencies, dtype=torch.uint8, device="cuda")
+        d_spans = torch.empty(n + 2 + 2 * n * (1 + n_currencies), dtype=torch.int64, device="cuda")
+        problem = C.c_uint64(0)
+        ffi.check(L.sg_mst_csv_entries_dev(ffi.dev_ptr(d_text), size, body_off, ffi.dev_ptr(d_tiles), ord(delim), n_currencies, n, rows,
+                                           ffi.dev_ptr(d_spans), ffi.dev_ptr(d_users), ffi.dev_ptr(d_bals), C.byref(problem), stream))
+        if problem.value:
+            return None, f"row {problem.value >> 8}: {_CSV_ROW_PROBLEMS.get(problem.value & 0xff, 'outside the subset')}"
+        tree = cls(d_users, d_bals, depth, n_currencies)       # same stream; synchronized when it returns
+        tree._csv_lazy = (path, {})
+        tree.cryptocurrencies = crypto
+        tree.csv_ingest = "device"
+        return tree, None
+
     def update_leaf(self, username: str, new_balances):
         """mst.rs:169-204: new balances for one user; the leaf and its `depth` ancestors are re-hashed in place on the device.
         Returns the new root (hash, balances)."""
@@ -553,7 +653,9 @@ class DeviceMerkleSumTree(_Tree):
         digit_bytes, digit_off = pack_balances(flat)
         self._update_dev(np.array(order, dtype=np.uint32), digit_bytes, digit_off)
         self._root = None
-        if self.entries is not None:
+        if self._csv_lazy is not None:                        # entries nobody has read yet: kept for when somebody does
+            self._csv_lazy[1].update((i, flat[nc * j:nc * j + nc]) for j, i in enumerate(order))
+        elif self.entries is not None:
             for j, i in enumerate(order):
                 self.entries[i] = (self.entries[i][0], flat[nc * j:nc * j + nc])
         return self.root()

@@ -558,6 +558,41 @@ int sg_mst_build_dev(const void* d_usernames, const void* d_leaf_balances, uint3
  * (sg_host_register) are read in stream order and stay as they are until the stream has passed the call. */
 int sg_mst_entries_dev(const uint8_t* name_bytes, const uint64_t* name_off, const uint8_t* digit_bytes, const uint64_t* digit_off,
                        size_t n, size_t rows, uint32_t n_currencies, void* d_usernames, void* d_balances, void* stream);
+/* The same two arrays from the text of a snapshot CSV, read on the device.  DEVICE input: the file's bytes d_bytes[0 .. len); the
+ * body -- every line behind the header, which the caller parses itself -- is d_bytes[body_off .. len), fewer than 2^32 bytes
+ * (kernels read it 16 bytes a lane where body_off leaves it on a 16-byte boundary, byte by byte elsewhere).  The reader takes a
+ * strict subset of CSV text and REPORTS what lies outside it, so that the caller can hand such a file to a full parser; it
+ * never judges the data itself.  In the subset: no byte '"', 0x00 or >= 0x80; every '\r' directly before a '\n'; rows are
+ * what lies between '\n' (one '\r' before it stripped; a last row without '\n' counts, and one blank line at the very end is no row, as
+ * for Python's csv); no empty row elsewhere; exactly n_currencies delimiters a row; every field behind the first one or more of '0'..'9' (the first, the
+ * username, may be empty); no row longer than row_cap bytes.
+ * sg_mst_csv_geometry: tile_bytes, the bytes a workgroup scans (4096), and row_cap (131072).
+ * sg_mst_csv_scan_dev: *n_rows_out = the rows of the body (0 for an empty one), *flags_out = 0 or SG_MST_CSV_FLAG_* or-ed.
+ *   d_tile_scratch: 4 * (ceil(body bytes / tile_bytes) + 2) bytes, 4-byte aligned; sg_mst_csv_entries_dev reads it.  The call waits for
+ *   the stream (one 8-byte copy).  With a flag up n_rows means nothing and sg_mst_csv_entries_dev must not follow.
+ * sg_mst_csv_entries_dev: after a scan without flags and with its n_rows >= 1.  d_span_scratch: 8 * (n_rows + 2 + 2 * n_rows *
+ *   (1 + n_currencies)) bytes, 8-byte aligned.  It finds every row's fields, waits for the stream (one 8-byte copy) and sets
+ *   *problem_out: 0, or row << 8 | SG_MST_CSV_ROW_* of the lowest row outside the subset (rows count from 0 behind the header;
+ *   of several problems in that row the lowest code), and then writes nothing more.  With *problem_out == 0 d_usernames (rows x 32 B) and
+ *   d_balances (rows x n_currencies x 32 B) are filled in stream order exactly as sg_mst_entries_dev fills them from the same
+ *   names and fields; rows >= n_rows, rows n_rows.. are zeroed.
+ * SG_ERR_INVALID, before the device is touched: a null pointer; a misaligned scratch; body_off > len (for the entries also
+ * body_off == len); a body of 2^32 bytes or more; n_currencies outside 1..64; n_rows == 0 or more than the body's bytes; rows <
+ * n_rows or rows >= 2^32; a delimiter (a byte's value) above 255 or that is '\n', '\r', a digit, or one of the bytes above. */
+#define SG_MST_CSV_FLAG_BYTE 0x40000000u    /* a byte '"', 0x00 or >= 0x80 */
+#define SG_MST_CSV_FLAG_BARE_CR 0x80000000u /* a '\r' that no '\n' follows, the body's last byte included */
+#define SG_MST_CSV_ROW_TOO_LONG 1
+#define SG_MST_CSV_ROW_EMPTY 2
+#define SG_MST_CSV_ROW_DELIMITERS 3    /* a field short or a field long */
+#define SG_MST_CSV_ROW_EMPTY_BALANCE 4
+#define SG_MST_CSV_ROW_NOT_DECIMAL 5
+#define SG_MST_CSV_ROW_START 6         /* n_rows is not the scan's */
+void sg_mst_csv_geometry(uint32_t* tile_bytes, uint32_t* row_cap);
+int sg_mst_csv_scan_dev(const void* d_bytes, uint64_t len, uint64_t body_off, void* d_tile_scratch, uint64_t* n_rows_out,
+                        uint32_t* flags_out, void* stream);
+int sg_mst_csv_entries_dev(const void* d_bytes, uint64_t len, uint64_t body_off, const void* d_tile_scratch, uint32_t delimiter,
+                           uint32_t n_currencies, uint64_t n_rows, uint64_t rows, void* d_span_scratch, void* d_usernames,
+                           void* d_balances, uint64_t* problem_out, void* stream);
 /* MerkleSumTree::update_leaf (mst.rs:169-204) for m leaves at once, in place on the device: new balances for the leaves
  * leaf_indices[0 .. m) of a tree sg_mst_build_dev built from d_usernames / d_leaf_balances into d_node_hashes / d_node_balances.
  * HOST inputs: the indices (strictly increasing, each below 2^depth) and their m * n_currencies balances as decimal fields,
@@ -670,6 +705,7 @@ int sg_msm_launch_log(uint32_t* out_words, size_t cap_records, size_t* n_records
  *   4: sg_get_param returns the value in effect of every parameter, its default until it is set (revision 3: 0 for a per-lane one
  *     never set); sg_set_param and sg_get_param refuse the same names, and setting a per-lane parameter no longer binds a device
  *     (still 4: sg_lookup_permute_dev and sg_lookup_permute_async_dev added; nothing changed meaning, nothing removed or resized)
+ *     (still 4: sg_mst_csv_geometry, sg_mst_csv_scan_dev and sg_mst_csv_entries_dev added)
  * A binding built against revision r must refuse a library whose sg_abi_version() < r. */
 #define SG_ABI_VERSION 4
 int sg_abi_version(void);

@@ -138,6 +138,34 @@ extern "C" {
         d_node_balances: *mut c_void,
         stream: *mut c_void,
     ) -> c_int;
+    // `MerkleSumTree::from_csv` with the file's bytes already on the device: the rows and flags of the body behind the header
+    // line (one wait), then the inputs of sg_mst_build_dev from the text itself, or the lowest row outside the reader's subset
+    // of CSV (a second wait; nothing is hashed then, and the caller parses the file on the host).  Scratch sizes: summa_gpu.h
+    pub fn sg_mst_csv_geometry(tile_bytes: *mut u32, row_cap: *mut u32);
+    pub fn sg_mst_csv_scan_dev(
+        d_bytes: *const c_void,
+        len: u64,
+        body_off: u64,
+        d_tile_scratch: *mut c_void,
+        n_rows_out: *mut u64,
+        flags_out: *mut u32,
+        stream: *mut c_void,
+    ) -> c_int;
+    pub fn sg_mst_csv_entries_dev(
+        d_bytes: *const c_void,
+        len: u64,
+        body_off: u64,
+        d_tile_scratch: *const c_void,
+        delimiter: u32,
+        n_currencies: u32,
+        n_rows: u64,
+        rows: u64,
+        d_span_scratch: *mut c_void,
+        d_usernames: *mut c_void,
+        d_balances: *mut c_void,
+        problem_out: *mut u64,
+        stream: *mut c_void,
+    ) -> c_int;
 }
 
 /// `sg_graph` of include/summa_gpu.h: the plain-struct image of halo2's `GraphEvaluator` (what `pk.ev` holds)

@@ -92,6 +92,7 @@ def build_from_csv(path, k=13, nc=2, user=0, timings=None):
     DeviceMerkleSumTree.from_csv(path, nc)
     t0 = time.perf_counter(); tree = DeviceMerkleSumTree.from_csv(path, nc)       # synchronized when it returns
     t["mst_from_csv_ms"] = (time.perf_counter() - t0) * 1e3
+    t["csv_ingest"] = tree.csv_ingest                         # "device", or "host" for a file outside the device reader's subset
     t0 = time.perf_counter()
     asg = api.MstInclusionCircuit.init(tree.generate_proof(user), tree.depth, nc).synthesize(k)
     t["witness_assignment_host_ms"] = (time.perf_counter() - t0) * 1e3
