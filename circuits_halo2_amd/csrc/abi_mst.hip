@@ -1,7 +1,9 @@
 // C ABI, Merkle sum tree family: the inclusion circuit's keygen columns and sg_mst_* -- leaves, levels and whole trees, entries from
 // names and decimal balances, the in-place update and the circuit's witness (summa_gpu.hip holds the core).
 #include "abi_internal.h"
+#include "../../include/summa_snapshot.h"
 #include "mst_csv.h"
+#include "mst_sort.h"
 #include "mst_entries.h"
 #include "mst_update_plan.h"
 
@@ -170,6 +172,81 @@ int sg_mst_csv_entries_dev(const void* d_bytes, uint64_t len, uint64_t body_off,
   *problem_out = problem == MST_CSV_NO_PROBLEM ? 0 : problem;
   if (*problem_out) return SG_OK;                            // the outputs stay unwritten
   CHECK_HIP(mst_csv_entries_launch(body, words, n_rows, rows, n_currencies, d_usernames, d_balances, s), "sg_mst_csv_entries");
+  return SG_OK;
+}
+// The sorted flavour (include/summa_snapshot.h; mst_sort.h has the rules and the work space, mst_sort.cuh the kernels): the split
+// as above with its problem word in the sort's work space, where the lengths step puts the longest name beside it -- one copy
+// and one wait for both, and the host launches as many passes as that name has bytes.  The name spans are zeroed before the
+// split, so that a row it reports without writing them has an empty name for the lengths step.  The spans in leaf order go
+// into a second block of the span scratch, laid out as the first, and the hashing kernels run over it as they stand.
+void ss_mst_sort_geometry(uint32_t* name_cap, uint32_t* tile_rows) {
+  if (name_cap) *name_cap = MST_SORT_NAME_CAP;
+  if (tile_rows) *tile_rows = MST_SORT_TILE;
+}
+int ss_mst_sort_scratch(uint64_t n_rows, uint64_t* bytes_out) {
+  if (!bytes_out) return fail(SG_ERR_INVALID, "ss_mst_sort_scratch: null argument");
+  if (n_rows == 0 || n_rows >= (1ull << 32)) return refuse("ss_mst_sort_scratch", "bad size");
+  *bytes_out = 4 * mst_sort_work_words(n_rows);
+  return SG_OK;
+}
+int ss_mst_csv_entries_sorted_dev(const void* d_bytes, uint64_t len, uint64_t body_off, const void* d_tile_scratch, uint32_t delimiter,
+                                  uint32_t n_currencies, uint64_t n_rows, uint64_t rows, void* d_span_scratch, void* d_sort_scratch,
+                                  void* d_order, void* d_name_spans, void* d_usernames, void* d_balances, uint64_t* problem_out,
+                                  void* stream) {
+  if (!d_bytes || !d_tile_scratch || !d_span_scratch || !d_sort_scratch || !d_order || !d_name_spans || !d_usernames || !d_balances ||
+      !problem_out)
+    return fail(SG_ERR_INVALID, "ss_mst_csv_entries_sorted: null argument");
+  const bool delimiter_ok = delimiter < 256 && delimiter != '\n' && delimiter != '\r' && !(delimiter >= '0' && delimiter <= '9') && !mst_csv_forbidden((uint8_t)delimiter);
+  const bool sizes_ok = body_off < len && len - body_off < (1ull << 32) && n_rows != 0 && n_rows <= len - body_off && rows >= n_rows &&
+                        rows < (1ull << 32) && !((uintptr_t)d_tile_scratch & 3) && !((uintptr_t)d_span_scratch & 7) && delimiter_ok &&
+                        !((uintptr_t)d_sort_scratch & 15) && !((uintptr_t)d_order & 3) && !((uintptr_t)d_name_spans & 3);
+  if (const char* problem = shape_problem(n_currencies, 0, sizes_ok)) return refuse("ss_mst_csv_entries_sorted", problem);
+  const uint64_t body_len = len - body_off;
+  const uint8_t* body = static_cast<const uint8_t*>(d_bytes) + body_off;
+  uint64_t* words = static_cast<uint64_t*>(d_span_scratch);
+  uint64_t* sorted_words = words + mst_csv_span_words(n_rows, n_currencies);
+  uint32_t* work = static_cast<uint32_t*>(d_sort_scratch);
+  const MstCsvSpans spans = mst_csv_spans(words, n_rows, n_currencies);
+  LOCKED_CTX();
+  hipStream_t s = pick_stream(stream);
+  CHECK_HIP(hipMemsetAsync(work, 0, 4 * MST_SORT_FRONT_WORDS, s), "ss_mst_csv_entries_sorted: work space");
+  CHECK_HIP(hipMemsetAsync(spans.name_begin, 0, 16 * n_rows, s), "ss_mst_csv_entries_sorted: name spans");   // name_end follows
+  CHECK_HIP(mst_csv_split_launch(body, body_len, static_cast<const uint32_t*>(d_tile_scratch), (uint8_t)delimiter, n_currencies, n_rows, words,
+                                 reinterpret_cast<uint64_t*>(work + MST_SORT_AT_PROBLEM), s),
+            "ss_mst_csv_entries_sorted: split");
+  CHECK_HIP(mst_sort_lengths_launch(words, n_rows, n_currencies, work, s), "ss_mst_csv_entries_sorted: lengths");
+  uint64_t result[2] = {0, 0};                               // the problem word, then the longest name in the low half
+  TRY(download(reinterpret_cast<uint8_t*>(result), work, sizeof result, s));
+  *problem_out = result[0] == MST_CSV_NO_PROBLEM ? 0 : result[0];
+  if (*problem_out) return SG_OK;                            // the outputs stay unwritten
+  CHECK_HIP(mst_sort_launch(body, words, n_rows, n_currencies, (uint32_t)result[1], work, static_cast<uint32_t*>(d_order),
+                            static_cast<uint32_t*>(d_name_spans), sorted_words, s),
+            "ss_mst_csv_entries_sorted: sort");
+  CHECK_HIP(mst_csv_entries_launch(body, sorted_words, n_rows, rows, n_currencies, d_usernames, d_balances, s), "ss_mst_csv_entries_sorted");
+  return SG_OK;
+}
+// The queries travel in one work space of the caller's stream: the offsets, the answers, then the bytes.
+int ss_mst_find_names(const void* d_bytes, uint64_t len, uint64_t body_off, const void* d_name_spans, uint64_t n_rows,
+                      const uint8_t* name_bytes, const uint64_t* name_off, size_t m, uint32_t* index_out, void* stream) {
+  if (!d_bytes || !d_name_spans || !name_bytes || !name_off || !index_out) return fail(SG_ERR_INVALID, "ss_mst_find_names: null argument");
+  if (m == 0 || m >= (1ull << 32) || n_rows == 0 || n_rows >= (1ull << 32) || body_off > len || len - body_off >= (1ull << 32) ||
+      ((uintptr_t)d_name_spans & 3))
+    return refuse("ss_mst_find_names", "bad size");
+  if (name_off[0] != 0) return refuse("ss_mst_find_names", "offsets do not start at 0");
+  for (size_t j = 0; j < m; j++)
+    if (name_off[j + 1] < name_off[j]) return refuse("ss_mst_find_names", "offsets decrease");
+  const size_t query_len = name_off[m], at_out = 8 * (m + 1), at_bytes = (at_out + 4 * m + 7) & ~(size_t)7;
+  LOCKED_CTX();
+  hipStream_t s = pick_stream(stream);
+  uint8_t* d = nullptr;
+  CHECK_HIP(scratch_for(s, 14, at_bytes + query_len + 1, &d), "ss_mst_find_names: work space");
+  CHECK_HIP(hipMemcpyAsync(d, name_off, 8 * (m + 1), hipMemcpyHostToDevice, s), "ss_mst_find_names: offsets");
+  if (query_len) CHECK_HIP(hipMemcpyAsync(d + at_bytes, name_bytes, query_len, hipMemcpyHostToDevice, s), "ss_mst_find_names: names");
+  CHECK_HIP(mst_find_names_launch(static_cast<const uint8_t*>(d_bytes) + body_off, len - body_off, static_cast<const uint32_t*>(d_name_spans),
+                                  (uint32_t)n_rows, d + at_bytes, reinterpret_cast<const uint64_t*>(d), m,
+                                  reinterpret_cast<uint32_t*>(d + at_out), s),
+            "ss_mst_find_names");
+  TRY(download(reinterpret_cast<uint8_t*>(index_out), d + at_out, 4 * m, s));   // waits for the stream
   return SG_OK;
 }
 // New balances for m leaves of a built tree, in place (mst.rs:169-204 for many leaves at once; witness.hip has the kernels).

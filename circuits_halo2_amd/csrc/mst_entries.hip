@@ -1,7 +1,8 @@
 // The leaves' inputs of a Merkle sum tree from what an exchange has -- usernames and decimal balances -- on the device: the
 // GPU counterpart of `Entry::new` over a whole snapshot (mst_entries.h has the arithmetic and the references).  Both
 // kernels trust their offsets: sg_mst_entries_dev (abi_mst.hip) validates them on the host before it launches, and the
-// CSV reader's passes below (mst_csv.h has their rules) validate the spans they make before anything is hashed.
+// CSV reader's passes below (mst_csv.h has their rules) validate the spans they make before anything is hashed.  The sort of
+// those spans by name and the lookup by name are mst_sort.cuh, included at the end.
 #include "mst_entries.h"
 #include "mst_csv.h"
 
@@ -262,3 +263,5 @@ hipError_t mst_csv_split_launch(const uint8_t* d_body, uint64_t body_len, const 
 }
 
 }  // namespace sg
+
+#include "mst_sort.cuh"   // the sorted flavour: the names' order, the spans in leaf order, lookup by name

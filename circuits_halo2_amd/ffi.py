@@ -193,6 +193,28 @@ def verifier_lib():
     return L
 
 
+# C ABI of the sorted snapshot (include/summa_snapshot.h), exported by the same library; errors go through sg_last_error
+SNAPSHOT_EXPORTS = ["ss_mst_sort_geometry", "ss_mst_sort_scratch", "ss_mst_csv_entries_sorted_dev", "ss_mst_find_names"]
+SNAPSHOT_ARGTYPES = {
+    "ss_mst_sort_geometry": [C.c_void_p, C.c_void_p],
+    "ss_mst_sort_scratch": [C.c_uint64, C.c_void_p],
+    "ss_mst_csv_entries_sorted_dev": [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "ss_mst_find_names": [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                          C.c_void_p],
+}
+
+
+def snapshot_lib():
+    L = lib()
+    if not getattr(L, "_ss_ready", False):
+        for name in SNAPSHOT_EXPORTS:
+            getattr(L, name).argtypes = SNAPSHOT_ARGTYPES[name]
+        L.ss_mst_sort_geometry.restype = None
+        L._ss_ready = True
+    return L
+
+
 def check_prover(rc: int):
     if rc != SG_OK:
         raise SummaGpuError(rc, prover_lib().sp_last_error().decode())

@@ -4,10 +4,12 @@ utils/csv_parser.rs, utils/operation_helpers.rs:10-12) with the hashing on the G
 
 Host logic kept here: CSV parsing, keccak256(username) -> field element, decimal balances ->
 field elements, zero-entry padding to 2^depth, Merkle-proof extraction (tree.rs:85-137).
-DeviceMerkleSumTree.from_entries / from_csv_sorted leave only the CSV parsing here: names and decimal balances
+DeviceMerkleSumTree.from_entries leaves only the CSV parsing here: names and decimal balances
 become field elements on the device (sg_mst_entries_dev) and the tree stays in HBM; DeviceMerkleSumTree.from_csv leaves the
 header line here and reads the rest of the file on the device too (sg_mst_csv_scan_dev / sg_mst_csv_entries_dev), unless the
-file is outside the device reader's subset of CSV text; DeviceMerkleSumTree.update_leaf /
+file is outside the device reader's subset of CSV text; DeviceMerkleSumTree.from_csv_sorted does the same and sorts the names
+there as well (ss_mst_csv_entries_sorted_dev), and such a tree finds a user by name on the device (ss_mst_find_names);
+DeviceMerkleSumTree.update_leaf /
 update_leaves / update_leaves_at change balances there in place (sg_mst_update_dev).
 """
 from __future__ import annotations
@@ -456,7 +458,9 @@ def pack_balances(flat):
 # SG_MST_CSV_FLAG_*, SG_MST_CSV_ROW_*), in the words of csv_fallback_reason
 _CSV_FLAGS = ((0x40000000, "a quote, NUL or non-ASCII byte"), (0x80000000, "a carriage return without a line feed"))
 _CSV_ROW_PROBLEMS = {1: "longer than csv's field limit", 2: "empty", 3: "not n_currencies + 1 fields", 4: "an empty balance",
-                     5: "a balance that is not decimal digits", 6: "row starts out of order"}
+                     5: "a balance that is not decimal digits", 6: "row starts out of order",
+                     7: "name too long for the device sort"}      # include/summa_snapshot.h: from_csv_sorted alone
+_ABSENT = 0xFFFFFFFF          # SS_MST_FIND_ABSENT
 
 
 class DeviceMerkleSumTree(_Tree):
@@ -472,6 +476,12 @@ class DeviceMerkleSumTree(_Tree):
     the `entry` of a Merkle proof carries the name, as MerkleSumTree's do; after the plain constructor `entries` is None.
     `from_csv` reads the file's text on the device where it can (`csv_ingest`); such a tree parses the file on the host only
     when its entries are first asked for by name, which `root`, `public_inputs_many`, `update_leaves_at` and the provers never do.
+    `from_csv_sorted` does the same and sorts the names on the device too (mst.rs:89-100; names of up to 64 bytes).  Such a tree
+    keeps the file's text, the file row of every leaf and the span of every leaf's name in HBM -- the file's size plus 12 bytes a
+    row (4 of `d_order`, 8 of `d_name_spans`), beside roughly 200 MB of nodes at 2^20 users and two currencies -- and, while its
+    entries are unparsed, answers by name from there (ss_mst_find_names: one binary search per name over the text):
+    `index_of_username`, `indices_of_usernames`, `update_leaf` / `update_leaves` and the `entry` of `generate_proof` do not parse
+    the file.  `entries` still does, once, and puts the rows in leaf order through `d_order`.
 
     `update_leaf`, `update_leaves` and `update_leaves_at` change balances in place (sg_mst_update_dev): the leaves and the nodes
     above them are re-hashed on the device, in the arrays the tree was built from (`d_balances` of the plain constructor is
@@ -484,6 +494,7 @@ class DeviceMerkleSumTree(_Tree):
     csv_ingest = None         # from_csv: "device" (the file's text was read on the device) or "host" (parse_csv_to_entries)
     csv_fallback_reason = None    # ... and why the host read it
     _csv_lazy = None          # a device-read tree whose entries nobody has asked for: (path, {leaf index: balances set since})
+    _sorted_dev = None        # a device-sorted tree: {"text", "size", "body_off", "delim", "n", "d_order", "d_name_spans"}
 
     @property
     def entries(self):
@@ -492,6 +503,8 @@ class DeviceMerkleSumTree(_Tree):
         if self._entries is None and self._csv_lazy is not None:
             path, changed = self._csv_lazy
             parsed, _ = parse_csv_to_entries(path, self.n_currencies)
+            if self._sorted_dev is not None:                  # the device's order: one copy and no host sort
+                parsed = [parsed[i] for i in self._sorted_dev["d_order"].cpu().tolist()]
             parsed += [(None, [0] * self.n_currencies)] * ((1 << self.depth) - len(parsed))
             for i, bal in changed.items():
                 parsed[i] = (parsed[i][0], bal)
@@ -557,8 +570,22 @@ class DeviceMerkleSumTree(_Tree):
         return tree
 
     @classmethod
-    def _from_csv_on_device(cls, path: str, n_currencies: int):
-        """-> (tree, None), or (None, why the device does not take this file)"""
+    def from_csv_sorted(cls, path: str, n_currencies: int, n_bytes: int = 8):
+        """mst.rs:89-100 with the file's text read and its names sorted where the tree is built (sg_mst_csv_scan_dev,
+        ss_mst_csv_entries_sorted_dev): `from_csv` with the leaves ordered by the usernames' bytes, equal names in file order.
+        The device takes the reader's subset of CSV text and names of at most 64 bytes; any other file goes the way every
+        file went before (parse_csv_to_entries, a host sort, from_entries).  `csv_ingest` and `csv_fallback_reason` as for
+        `from_csv`."""
+        tree, reason = cls._from_csv_on_device(path, n_currencies, sorted_leaves=True)
+        if tree is None:
+            tree = super().from_csv_sorted(path, n_currencies, n_bytes)
+            tree.csv_ingest, tree.csv_fallback_reason = "host", reason
+        return tree
+
+    @classmethod
+    def _from_csv_on_device(cls, path: str, n_currencies: int, sorted_leaves: bool = False):
+        """-> (tree, None), or (None, why the device does not take this file); sorted_leaves: the leaves in the order of the
+        names' bytes"""
         import torch
         if not 1 <= n_currencies <= 64:
             return None, "n_currencies outside 1..64"
@@ -600,17 +627,80 @@ class DeviceMerkleSumTree(_Tree):
         rows = 1 << depth
         d_users = torch.empty(32 * rows, dtype=torch.uint8, device="cuda")
         d_bals = torch.empty(32 * rows * n_currencies, dtype=torch.uint8, device="cuda")
-        d_spans = torch.empty(n + 2 + 2 * n * (1 + n_currencies), dtype=torch.int64, device="cuda")
         problem = C.c_uint64(0)
-        ffi.check(L.sg_mst_csv_entries_dev(ffi.dev_ptr(d_text), size, body_off, ffi.dev_ptr(d_tiles), ord(delim), n_currencies, n, rows,
-                                           ffi.dev_ptr(d_spans), ffi.dev_ptr(d_users), ffi.dev_ptr(d_bals), C.byref(problem), stream))
+        if sorted_leaves:
+            S = ffi.snapshot_lib()
+            sort_bytes = C.c_uint64(0)
+            ffi.check(S.ss_mst_sort_scratch(n, C.byref(sort_bytes)))
+            d_spans = torch.empty(2 * (n + 1 + 2 * n * (1 + n_currencies)), dtype=torch.int64, device="cuda")
+            d_sort = torch.empty(sort_bytes.value, dtype=torch.uint8, device="cuda")
+            d_order = torch.empty(n, dtype=torch.int32, device="cuda")
+            d_name_spans = torch.empty(2 * n, dtype=torch.int32, device="cuda")
+            ffi.check(S.ss_mst_csv_entries_sorted_dev(ffi.dev_ptr(d_text), size, body_off, ffi.dev_ptr(d_tiles), ord(delim), n_currencies, n,
+                                                      rows, ffi.dev_ptr(d_spans), ffi.dev_ptr(d_sort), ffi.dev_ptr(d_order),
+                                                      ffi.dev_ptr(d_name_spans), ffi.dev_ptr(d_users), ffi.dev_ptr(d_bals),
+                                                      C.byref(problem), stream))
+        else:
+            d_spans = torch.empty(n + 2 + 2 * n * (1 + n_currencies), dtype=torch.int64, device="cuda")
+            ffi.check(L.sg_mst_csv_entries_dev(ffi.dev_ptr(d_text), size, body_off, ffi.dev_ptr(d_tiles), ord(delim), n_currencies, n, rows,
+                                               ffi.dev_ptr(d_spans), ffi.dev_ptr(d_users), ffi.dev_ptr(d_bals), C.byref(problem), stream))
         if problem.value:
             return None, f"row {problem.value >> 8}: {_CSV_ROW_PROBLEMS.get(problem.value & 0xff, 'outside the subset')}"
         tree = cls(d_users, d_bals, depth, n_currencies)       # same stream; synchronized when it returns
+        if sorted_leaves:
+            tree.is_sorted = True
+            tree._sorted_dev = {"text": d_text, "size": size, "body_off": body_off, "delim": delim, "n": n, "d_order": d_order,
+                                "d_name_spans": d_name_spans}
         tree._csv_lazy = (path, {})
         tree.cryptocurrencies = crypto
         tree.csv_ingest = "device"
         return tree, None
+
+    def _finds_on_device(self) -> bool:
+        """a device-sorted tree whose entries are still unparsed: names are looked up in the text in HBM"""
+        return self._entries is None and self._csv_lazy is not None and self._sorted_dev is not None
+
+    def index_of_username(self, username: str) -> int:
+        """mst.rs:207-223; on a device-sorted tree whose entries are unparsed a binary search on the device, no parse"""
+        if self._finds_on_device():
+            return self.indices_of_usernames([username])[0]
+        return super().index_of_username(username)
+
+    def indices_of_usernames(self, usernames):
+        """`index_of_username` of every name, a repeated name's first leaf: one device call (ss_mst_find_names) on a
+        device-sorted tree whose entries are unparsed.  KeyError("Username not found") if any name is missing."""
+        usernames = list(usernames)
+        if not self._finds_on_device():
+            return [self.index_of_username(name) for name in usernames]
+        if not usernames:
+            return []
+        names = [name.encode() for name in usernames]
+        name_off = np.zeros(len(names) + 1, dtype=np.uint64)
+        np.cumsum(np.fromiter(map(len, names), dtype=np.uint64, count=len(names)), out=name_off[1:])
+        name_bytes = np.frombuffer(b"".join(names) or b"\0", dtype=np.uint8)       # only empty names: a buffer to point at all the same
+        found = np.zeros(len(names), dtype=np.uint32)
+        d = self._sorted_dev
+        ffi.check(ffi.snapshot_lib().ss_mst_find_names(ffi.dev_ptr(d["text"]), d["size"], d["body_off"], ffi.dev_ptr(d["d_name_spans"]),
+                                                       d["n"], ffi.ptr(name_bytes), ffi.ptr(name_off), len(names), ffi.ptr(found),
+                                                       ffi.current_stream_ptr()))
+        if (found == _ABSENT).any():
+            raise KeyError("Username not found")
+        return [int(i) for i in found]
+
+    def _entry_from_text(self, index: int):
+        """entry `index` of a device-sorted tree whose entries are unparsed, from the row's text in HBM: two small copies"""
+        nc, d = self.n_currencies, self._sorted_dev
+        if index >= d["n"]:
+            return (None, [0] * nc)
+        begin, end = (int(x) & 0xFFFFFFFF for x in d["d_name_spans"][2 * index:2 * index + 2].cpu().tolist())
+        lo, text = d["body_off"] + begin, b""
+        want = end - begin + 1 + 24 * nc
+        while b"\n" not in text[end - begin:] and lo + len(text) < d["size"]:       # the row ends at its line end or the file's
+            text = bytes(d["text"][lo:min(d["size"], lo + want)].cpu().numpy())
+            want *= 4
+        row = text[end - begin + 1:].split(b"\n")[0].rstrip(b"\r")
+        balances = [int(x) for x in row.split(d["delim"].encode())]
+        return (text[:end - begin].decode(), self._csv_lazy[1].get(index, balances))
 
     def update_leaf(self, username: str, new_balances):
         """mst.rs:169-204: new balances for one user; the leaf and its `depth` ancestors are re-hashed in place on the device.
@@ -621,6 +711,9 @@ class DeviceMerkleSumTree(_Tree):
         """`update_leaf` for every (username, [balances]) of `updates` as one device call (sg_mst_update_dev): the leaves, then
         the distinct ancestors level by level.  A username that appears twice keeps its last balances, which is what the
         updates applied one after another leave.  Everything is checked first: a refused batch leaves the tree as it was."""
+        updates = list(updates)
+        if self._finds_on_device():       # the names are found where the text lies: no parse
+            return self.update_leaves_at(self.indices_of_usernames([name for name, _ in updates]), [bal for _, bal in updates])
         if self.entries is None:
             raise KeyError("Username not found")
         if self._name_index is None:      # names never change: the first index of each, as index_of_username finds it
@@ -718,7 +811,9 @@ class DeviceMerkleSumTree(_Tree):
         h, b, users, bals = self._rows(hash_nodes, bal_nodes, [index, index ^ 1] if self.depth else [index])
         nc = self.n_currencies
         entry = (_mont_to_int(users[0]), [_mont_to_int(bals[0][32 * c:32 * c + 32]) for c in range(nc)])
-        if self.entries is not None:
+        if self._finds_on_device():
+            entry = self._entry_from_text(index)
+        elif self.entries is not None:
             entry = self.entries[index]
         pre_mid = [np.concatenate([b[l], h[1 + 2 * l], h[2 + 2 * l]]) for l in range(max(0, self.depth - 1))]
         pre_leaf = np.concatenate([users[1], bals[1]]) if self.depth else None

@@ -1,0 +1,74 @@
+/* summa_snapshot.h -- C ABI of a snapshot sorted and looked up by username on the device, exported by the same shared library
+ * as include/summa_gpu.h.
+ *
+ * The reference's sorted constructor (zk_prover/src/merkle_sum_tree/mst.rs:89-100) orders its leaves by the usernames' bytes so
+ * that index_of_username is a binary search (mst.rs:207-223).  sg_mst_csv_scan_dev / sg_mst_csv_entries_dev (summa_gpu.h) read a
+ * snapshot CSV where its text lies, in file order; the two calls below do the same with the leaves in sorted order and answer
+ * "which leaf is this user's" from the text, so that a sorted snapshot is built, looked up by name and updated by name without
+ * the host reading a row.
+ *
+ * Order: names compare byte by byte, a proper prefix first; equal names keep file order (a stable sort, as Rust's sort_by and
+ * Python's list.sort).  The device sorts names of at most name_cap = 64 bytes (a UUID has 36, a hex SHA-256 64): a longer one
+ * is REPORTED as row problem SS_MST_CSV_ROW_NAME_TOO_LONG, behind the six of summa_gpu.h, so that the caller can hand such a
+ * file to a host sort; the lookup takes queries of any length.
+ *
+ * Conventions as in summa_gpu.h: 0 or a negative sg_status; sg_last_error() (thread-local) explains a failure; `stream` is the
+ * caller's hipStream_t (NULL: the default stream), and device work is ordered on it. */
+#ifndef SUMMA_SNAPSHOT_H
+#define SUMMA_SNAPSHOT_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "summa_gpu.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define SS_MST_CSV_ROW_NAME_TOO_LONG 7 /* a username of more than name_cap bytes */
+#define SS_MST_FIND_ABSENT 0xFFFFFFFFu
+
+/* ss_mst_sort_geometry: name_cap, the longest name the device sorts (64), and tile_rows, the rows a workgroup ranks in one pass
+ * of the sort (2048).  Either pointer may be NULL.
+ * ss_mst_sort_scratch: *bytes_out = the size of d_sort_scratch for n_rows rows.  SG_ERR_INVALID: a null pointer, n_rows == 0 or
+ * n_rows >= 2^32.  Neither touches a device. */
+void ss_mst_sort_geometry(uint32_t* name_cap, uint32_t* tile_rows);
+int ss_mst_sort_scratch(uint64_t n_rows, uint64_t* bytes_out);
+
+/* sg_mst_csv_entries_dev with the leaves in sorted order: after sg_mst_csv_scan_dev without flags and with its n_rows >= 1, with
+ * the d_tile_scratch it filled.  DEVICE inputs and the preconditions on the text are that call's (summa_gpu.h).
+ *   d_span_scratch  16 * (n_rows + 1 + 2 * n_rows * (1 + n_currencies)) bytes, 8-byte aligned: the spans in file order, then in
+ *                   leaf order (twice what sg_mst_csv_entries_dev asks for its one block; the contents are the library's own)
+ *   d_sort_scratch  ss_mst_sort_scratch(n_rows) bytes, 16-byte aligned (the contents are the library's own)
+ * It finds every row's fields and the longest name, waits for the stream (one 16-byte copy) and sets *problem_out: 0, or
+ * row << 8 | code of the lowest row outside what the device takes, SG_MST_CSV_ROW_* or SS_MST_CSV_ROW_NAME_TOO_LONG (of several
+ * problems in that row the lowest code), and then writes nothing more.  With *problem_out == 0 it launches as many passes of the
+ * sort as the longest name has bytes, and three outputs are filled in stream order:
+ *   d_order       n_rows x uint32, 4-byte aligned: the file row (from 0 behind the header) of leaf i
+ *   d_name_spans  n_rows x 2 x uint32, 4-byte aligned: begin and end of leaf i's name as offsets into the body (under 4 GiB)
+ *   d_usernames (rows x 32 B), d_balances (rows x n_currencies x 32 B): exactly what sg_mst_entries_dev fills from the same
+ *                 entries sorted stably by the names' bytes; rows >= n_rows, rows n_rows.. are zeroed
+ * SG_ERR_INVALID, before the device is touched: what sg_mst_csv_entries_dev refuses, and a null or misaligned d_sort_scratch,
+ * d_order or d_name_spans. */
+int ss_mst_csv_entries_sorted_dev(const void* d_bytes, uint64_t len, uint64_t body_off, const void* d_tile_scratch, uint32_t delimiter,
+                                  uint32_t n_currencies, uint64_t n_rows, uint64_t rows, void* d_span_scratch, void* d_sort_scratch,
+                                  void* d_order, void* d_name_spans, void* d_usernames, void* d_balances, uint64_t* problem_out,
+                                  void* stream);
+
+/* index_of_username for m names at once, over the text and the d_name_spans of ss_mst_csv_entries_sorted_dev (DEVICE: d_bytes,
+ * len, body_off, d_name_spans and n_rows as given to it and filled by it).  HOST inputs, laid out as the names of
+ * sg_mst_entries_dev: query j is name_bytes[name_off[j] .. name_off[j+1]), name_off: m + 1 x uint64, name_off[0] = 0; any
+ * length, 0 included -- a query longer than name_cap is simply not found.  HOST output: index_out[j] = the lowest leaf whose
+ * name equals query j, or SS_MST_FIND_ABSENT (one thread per query: a lower-bound binary search that compares bytes in the
+ * text).  The text and the spans are read in stream order -- the call sees work enqueued earlier on `stream` -- and the call
+ * waits for the stream before it returns; the host buffers have been read by then.
+ * SG_ERR_INVALID, before the device is touched: a null pointer; m == 0; n_rows == 0 or >= 2^32; body_off > len or a body of 2^32
+ * bytes or more; a misaligned d_name_spans; offsets that do not start at 0 or that decrease. */
+int ss_mst_find_names(const void* d_bytes, uint64_t len, uint64_t body_off, const void* d_name_spans, uint64_t n_rows,
+                      const uint8_t* name_bytes, const uint64_t* name_off, size_t m, uint32_t* index_out, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif
