@@ -277,7 +277,7 @@ class BatchResult:
 
 
 def prove_batch(tree, user_indices, params, pk, levels: int, flavour: str = "evm", in_flight: int = 2, prove=None,
-                make_circuit=None, combine: bool | None = None) -> BatchResult:
+                make_circuit=None, combine: bool | None = None, audit=None) -> BatchResult:
     """Inclusion proofs for this rank's share of `user_indices` (dealt round-robin over the process group).
 
     tree: MerkleSumTree of the snapshot (every rank holds it -- it is the input data); flavour "evm" =
@@ -289,7 +289,11 @@ def prove_batch(tree, user_indices, params, pk, levels: int, flavour: str = "evm
     fused by the library's commit combiner (include/summa_gpu.h: sg_commit_combine_begin) -- one sort front-end, bucket
     reduction and host tail per job for all of them.  It pays once enough proofs are in flight for full jobs to form
     while one is running (profiles/r03_sweeps/commit_combiner.txt: 4 in flight 184 -> 174 proofs/s, 8: 189 -> 217,
-    16: 179 -> 227)."""
+    16: 179 -> 227).
+    audit: a `RangeAudit` of `tree` as it is now (DeviceMerkleSumTree.range_audit).  Every dealt user whose circuit fails a range
+    check goes straight to `errors` with the first failing check, e.g. "range check: sibling at level 3, currency 0", and
+    neither `make_circuit` nor `prove` is called for that user; all others are proved as before.  The root's flag skips nobody:
+    the circuit does not check the root's sums.  None: nothing changes."""
     import os
     if combine is None:
         env = os.environ.get("SUMMA_COMBINE_COMMITS")
@@ -328,6 +332,11 @@ def prove_batch(tree, user_indices, params, pk, levels: int, flavour: str = "evm
         res = BatchResult()
         if prove is None:
             res.wait_sleep_us = ffi.get_param("host.wait_sleep_us")
+        if audit is not None and mine:
+            from .merkle_sum_tree import range_check_text
+            failures = audit.first_failures(mine)
+            res.errors.update((i, range_check_text(f)) for i, f in zip(mine, failures) if f is not None)
+            mine = [i for i, f in zip(mine, failures) if f is None]
         if make_circuit is None:
             if hasattr(tree, "d_h"):      # a device-resident snapshot: the witness never visits the host
                 if len(mine) >= 8 and len(set(mine)) == len(mine) and hasattr(pk, "circuit_shape"):

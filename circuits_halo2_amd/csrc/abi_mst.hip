@@ -1,9 +1,10 @@
 // C ABI, Merkle sum tree family: the inclusion circuit's keygen columns and sg_mst_* -- leaves, levels and whole trees, entries from
-// names and decimal balances, the in-place update and the circuit's witness (summa_gpu.hip holds the core).
+// names and decimal balances, the in-place update, the range audit and the circuit's witness (summa_gpu.hip holds the core).
 #include "abi_internal.h"
 #include "../../include/summa_snapshot.h"
 #include "mst_csv.h"
 #include "mst_sort.h"
+#include "mst_audit.h"
 #include "mst_entries.h"
 #include "mst_update_plan.h"
 
@@ -247,6 +248,35 @@ int ss_mst_find_names(const void* d_bytes, uint64_t len, uint64_t body_off, cons
                                   reinterpret_cast<uint32_t*>(d + at_out), s),
             "ss_mst_find_names");
   TRY(download(reinterpret_cast<uint8_t*>(index_out), d + at_out, 4 * m, s));   // waits for the stream
+  return SG_OK;
+}
+// The range audit of a built tree (include/summa_snapshot.h; mst_audit.h has the rules and the work space, mst_audit.cuh the
+// kernels): four launches behind one small memset, then one 16-byte copy and the call's only wait.
+int ss_mst_range_audit_scratch(uint32_t depth, uint64_t* bytes_out) {
+  if (!bytes_out) return fail(SG_ERR_INVALID, "ss_mst_range_audit_scratch: null argument");
+  if (depth > MST_AUDIT_MAX_DEPTH) return refuse("ss_mst_range_audit_scratch", "depth above 30");
+  *bytes_out = mst_audit_scratch_bytes(depth);
+  return SG_OK;
+}
+int ss_mst_range_audit_dev(const void* d_node_balances, uint32_t depth, uint32_t n_currencies, uint32_t n_bytes, void* d_node_flags,
+                           void* d_leaf_reasons, void* d_bad_leaves, uint64_t bad_cap, void* d_scratch, uint64_t* summary_out,
+                           void* stream) {
+  const std::string problem = mst_audit_problem(d_node_balances, depth, n_currencies, n_bytes, d_node_flags, d_leaf_reasons, d_bad_leaves,
+                                                bad_cap, d_scratch, summary_out);
+  if (!problem.empty()) return refuse("ss_mst_range_audit", problem.c_str());
+  uint32_t* work = static_cast<uint32_t*>(d_scratch);
+  LOCKED_CTX();
+  hipStream_t s = pick_stream(stream);
+  CHECK_HIP(hipMemsetAsync(work, 0, 4 * MST_AUDIT_FRONT_WORDS, s), "ss_mst_range_audit: work space");
+  CHECK_HIP(mst_audit_launch(d_node_balances, depth, n_currencies, n_bytes, static_cast<uint8_t*>(d_node_flags),
+                             static_cast<uint32_t*>(d_leaf_reasons), static_cast<uint32_t*>(d_bad_leaves), bad_cap, work, s),
+            "ss_mst_range_audit");
+  uint32_t result[MST_AUDIT_FRONT_WORDS];
+  TRY(download(reinterpret_cast<uint8_t*>(result), work, sizeof result, s));   // waits for the stream
+  summary_out[0] = result[MST_AUDIT_AT_BAD_NODES];
+  summary_out[1] = result[MST_AUDIT_AT_UNPROVABLE];
+  summary_out[2] = summary_out[1] < bad_cap ? summary_out[1] : bad_cap;
+  summary_out[3] = result[MST_AUDIT_AT_ROOT];
   return SG_OK;
 }
 // New balances for m leaves of a built tree, in place (mst.rs:169-204 for many leaves at once; witness.hip has the kernels).

@@ -463,6 +463,65 @@ _CSV_ROW_PROBLEMS = {1: "longer than csv's field limit", 2: "empty", 3: "not n_c
 _ABSENT = 0xFFFFFFFF          # SS_MST_FIND_ABSENT
 
 
+class RangeAudit:
+    """What `DeviceMerkleSumTree.range_audit` found (include/summa_snapshot.h: ss_mst_range_audit_dev), against top = 2^(8 n_bytes):
+      n_bad_nodes     nodes of the tree, the root included, with a balance >= top
+      n_unprovable    leaves whose circuit fails a range check
+      unprovable      numpy.uint32: those leaves in increasing order (with a `cap`, the first `cap` of them)
+      root_in_range, root_currency   the root's sums (the circuit leaves them to verification): the lowest offending currency or None
+      ok              no unprovable leaf and the root in range
+      d_node_flags    uint8 per node, level-major: 0, or 1 + the lowest currency whose balance is >= top
+      d_leaf_reasons  int32 per leaf: bit 0 the leaf's own balances, bit l + 1 the path's sibling at level l -- the circuit's range
+                      checks in the order of `synthesize`; 0: the user is provable
+    The two arrays are device tensors after `range_audit`; numpy arrays serve as well (the CPU tests make audits by hand).
+    An audit is a snapshot of a snapshot: after `update_leaves*` it is stale, and running it again is the remedy."""
+
+    def __init__(self, n_bytes, n_bad_nodes, n_unprovable, unprovable, root_flag, d_node_flags, d_leaf_reasons):
+        self.n_bytes, self.n_bad_nodes, self.n_unprovable = n_bytes, int(n_bad_nodes), int(n_unprovable)
+        self.unprovable = np.asarray(unprovable, dtype=np.uint32)
+        self.root_in_range = root_flag == 0
+        self.root_currency = int(root_flag) - 1 if root_flag else None
+        self.d_node_flags, self.d_leaf_reasons = d_node_flags, d_leaf_reasons
+        self.depth = int(d_leaf_reasons.shape[0]).bit_length() - 1
+
+    @property
+    def ok(self) -> bool:
+        return self.n_unprovable == 0 and self.root_in_range
+
+    @staticmethod
+    def _take(array, indices, dtype):
+        if isinstance(array, np.ndarray):
+            return array[np.asarray(indices, dtype=np.int64)].astype(dtype)
+        import torch
+        return array[torch.as_tensor(indices, dtype=torch.int64, device=array.device)].cpu().numpy().astype(dtype)
+
+    def reasons(self, indices) -> np.ndarray:
+        """the masks of some leaves as numpy.uint32: one gather and one copy"""
+        indices = [int(i) for i in indices]
+        if any(not 0 <= i < (1 << self.depth) for i in indices):
+            raise IndexError("Index out of bounds")
+        return self._take(self.d_leaf_reasons, indices, np.uint32) if indices else np.zeros(0, dtype=np.uint32)
+
+    def checks_of(self, index: int, mask: int):
+        """the failing range checks a mask names, in the circuit's order: [(what, level, node within its level)]"""
+        out = [("leaf", 0, index)] if mask & 1 else []
+        return out + [("sibling", l, (index >> l) ^ 1) for l in range(self.depth) if (mask >> (l + 1)) & 1]
+
+    def first_failures(self, indices):
+        """per leaf None (provable) or the first range check its circuit fails, (what, level, node, currency): two gathers"""
+        indices = [int(i) for i in indices]
+        firsts = [self.checks_of(i, int(m))[0] if m else None for i, m in zip(indices, self.reasons(indices))]
+        at = [_level_first(self.depth, f[1]) + f[2] for f in firsts if f is not None]
+        flags = iter(self._take(self.d_node_flags, at, np.int64)) if at else iter(())
+        return [None if f is None else f + (int(next(flags)) - 1,) for f in firsts]
+
+
+def range_check_text(failure) -> str:
+    """(what, level, node, currency) -> the words prove_batch files the user under"""
+    what, level, _, currency = failure
+    return f"range check: leaf, currency {currency}" if what == "leaf" else f"range check: sibling at level {level}, currency {currency}"
+
+
 class DeviceMerkleSumTree(_Tree):
     """A Merkle sum tree whose leaves are already field elements on the device (a snapshot of 2^depth users: username
     field elements and balances as Montgomery Fr), built and KEPT in HBM: level-major node arrays as `sg_mst_build_dev`
@@ -485,7 +544,10 @@ class DeviceMerkleSumTree(_Tree):
 
     `update_leaf`, `update_leaves` and `update_leaves_at` change balances in place (sg_mst_update_dev): the leaves and the nodes
     above them are re-hashed on the device, in the arrays the tree was built from (`d_balances` of the plain constructor is
-    written too), and nothing comes back but the root when it is next asked for."""
+    written too), and nothing comes back but the root when it is next asked for.
+
+    `range_audit` says which users of the snapshot can receive a valid inclusion proof at all -- whose circuit would fail a range
+    check, and at which one -- from the node balances in HBM (ss_mst_range_audit_dev); `explain_unprovable` names the balances."""
 
     _entries = None           # [(name, balances)] padded with (None, [0] * n_currencies): trees built from entries only
     _name_index = None        # {name: first index}, made by the first update_leaves
@@ -533,7 +595,7 @@ class DeviceMerkleSumTree(_Tree):
     def from_entries(cls, entries, n_currencies: int, n_bytes: int = 8, is_sorted: bool = False):
         """mst.rs:103-134 with the tree in HBM: `Entry::new` of every entry on the device (keccak256 of the name, the decimal
         balances folded in the field), zero entries up to 2^depth, then the constructor's build.  As in MerkleSumTree.from_entries
-        a balance that does not fit `n_bytes` only fails later, in the circuit's range check."""
+        a balance that does not fit `n_bytes` only fails later, in the circuit's range check (`range_audit` finds it sooner)."""
         import torch
         entries = list(entries)
         n = len(entries)
@@ -761,6 +823,49 @@ class DeviceMerkleSumTree(_Tree):
                                               self.n_currencies, ffi.dev_ptr(self.d_users), ffi.dev_ptr(self.d_bals),
                                               ffi.dev_ptr(self.d_h), ffi.dev_ptr(self.d_b), ffi.current_stream_ptr()))
         torch.cuda.current_stream().synchronize()
+
+    def range_audit(self, n_bytes: int = 8, cap=None) -> RangeAudit:
+        """Which users of this snapshot can receive a valid inclusion proof from a circuit of `n_bytes`: one device call
+        (ss_mst_range_audit_dev) on the current stream over `d_b`, one small copy for the summary and one for the list.  cap: list
+        at most that many unprovable leaves (None: all).  The result describes the tree as it is now: after `update_leaves*` it
+        is stale, and running the audit again is the remedy."""
+        import torch
+        if not 1 <= n_bytes <= 31:
+            raise ValueError("n_bytes outside 1..31")
+        if cap is not None and cap < 0:
+            raise ValueError("cap below 0")
+        S = ffi.snapshot_lib()
+        leaves = 1 << self.depth
+        bad_cap = leaves if cap is None else min(int(cap), leaves)
+        scratch_bytes = C.c_uint64(0)
+        ffi.check(S.ss_mst_range_audit_scratch(self.depth, C.byref(scratch_bytes)))
+        d_flags = torch.empty(2 * leaves - 1, dtype=torch.uint8, device="cuda")
+        d_reasons = torch.empty(leaves, dtype=torch.int32, device="cuda")
+        d_bad = torch.empty(bad_cap, dtype=torch.int32, device="cuda") if bad_cap else None
+        d_scratch = torch.empty(scratch_bytes.value // 4, dtype=torch.int32, device="cuda")
+        summary = (C.c_uint64 * 4)()
+        ffi.check(S.ss_mst_range_audit_dev(ffi.dev_ptr(self.d_b), self.depth, self.n_currencies, n_bytes, ffi.dev_ptr(d_flags),
+                                           ffi.dev_ptr(d_reasons), ffi.dev_ptr(d_bad) if bad_cap else None, bad_cap,
+                                           ffi.dev_ptr(d_scratch), summary, ffi.current_stream_ptr()))
+        listed = int(summary[2])
+        bad = d_bad[:listed].cpu().numpy().view(np.uint32) if listed else np.zeros(0, dtype=np.uint32)
+        return RangeAudit(n_bytes, summary[0], summary[1], bad, int(summary[3]), d_flags, d_reasons)
+
+    def explain_unprovable(self, audit: RangeAudit, index: int):
+        """What is wrong with user `index`: [(what, level, node, currency, value)] for every balance >= 2^(8 audit.n_bytes) that the
+        circuit of that user range-checks, in the circuit's order -- what: "leaf" (the user's own) or "sibling" (node `node` of
+        level `level` on the path); value: the balance as an integer.  Only the flagged nodes' rows are fetched.  [] for a
+        provable user.  `audit` must be of this tree as it is now."""
+        checks = audit.checks_of(index, int(audit.reasons([index])[0]))
+        if not checks:
+            return []
+        nc, top = self.n_currencies, 1 << (8 * audit.n_bytes)
+        _, rows, _, _ = self._rows([], [self.offsets[level] + node for _, level, node in checks], [])
+        out = []
+        for (what, level, node), row in zip(checks, rows):
+            values = [_mont_to_int(row[32 * c:32 * c + 32]) for c in range(nc)]
+            out += [(what, level, node, c, v) for c, v in enumerate(values) if v >= top]
+        return out
 
     def _rows(self, hash_nodes, balance_nodes, users):
         """one gather + one copy: rows of the hash array, of the balance array (n_currencies rows per node), leaf inputs"""

@@ -1,5 +1,5 @@
-/* summa_snapshot.h -- C ABI of a snapshot sorted and looked up by username on the device, exported by the same shared library
- * as include/summa_gpu.h.
+/* summa_snapshot.h -- C ABI of a snapshot sorted and looked up by username on the device, and of the range audit of a built
+ * tree, exported by the same shared library as include/summa_gpu.h.
  *
  * The reference's sorted constructor (zk_prover/src/merkle_sum_tree/mst.rs:89-100) orders its leaves by the usernames' bytes so
  * that index_of_username is a binary search (mst.rs:207-223).  sg_mst_csv_scan_dev / sg_mst_csv_entries_dev (summa_gpu.h) read a
@@ -11,6 +11,11 @@
  * Python's list.sort).  The device sorts names of at most name_cap = 64 bytes (a UUID has 36, a hex SHA-256 64): a longer one
  * is REPORTED as row problem SS_MST_CSV_ROW_NAME_TOO_LONG, behind the six of summa_gpu.h, so that the caller can hand such a
  * file to a host sort; the lookup takes queries of any length.
+ *
+ * Audit: the reference builds its tree from any balances (mst.rs:103-134 checks no range); the inclusion circuit range-checks,
+ * against 2^(8 n_bytes), the user's own leaf balances, the sibling leaf's and the sibling middle node's at every level above
+ * (circuits/merkle_sum_tree.rs:348-369, 424-438).  ss_mst_range_audit_dev answers, from the node balances where they lie, which
+ * nodes hold such a balance and which users' circuits fail for it, before a proof is spent on finding out.
  *
  * Conventions as in summa_gpu.h: 0 or a negative sg_status; sg_last_error() (thread-local) explains a failure; `stream` is the
  * caller's hipStream_t (NULL: the default stream), and device work is ordered on it. */
@@ -67,6 +72,33 @@ int ss_mst_csv_entries_sorted_dev(const void* d_bytes, uint64_t len, uint64_t bo
  * bytes or more; a misaligned d_name_spans; offsets that do not start at 0 or that decrease. */
 int ss_mst_find_names(const void* d_bytes, uint64_t len, uint64_t body_off, const void* d_name_spans, uint64_t n_rows,
                       const uint8_t* name_bytes, const uint64_t* name_off, size_t m, uint32_t* index_out, void* stream);
+
+/* ss_mst_range_audit_scratch: *bytes_out = the size of d_scratch for a tree of 2^depth leaves, 4 * (4 + tiles + groups) with
+ * tiles = ceil(2^depth / 64) and groups = ceil(tiles / 256).  SG_ERR_INVALID: a null pointer, depth > 30.  Touches no device. */
+int ss_mst_range_audit_scratch(uint32_t depth, uint64_t* bytes_out);
+
+/* The range audit of a built tree with top = 2^(8 n_bytes).  DEVICE input: d_node_balances, the level-major node balances of
+ * sg_mst_build_dev (2^(depth + 1) - 1 nodes x n_currencies x 32 B, Montgomery words), read only.  DEVICE outputs:
+ *   d_node_flags    2^(depth + 1) - 1 bytes, level-major as the nodes: 0 if every balance of the node is below top, else 1 + the
+ *                   lowest currency whose balance is not
+ *   d_leaf_reasons  2^depth x uint32, 4-byte aligned: bit 0 of leaf i's word iff its own flag is non-zero, bit l + 1 (0 <= l < depth)
+ *                   iff the flag of node (i >> l) ^ 1 of level l is -- the range checks of leaf i's circuit in the order of
+ *                   synthesize; 0: all of them pass.  The sums on the leaf's own path above it are not in the mask: the circuit does
+ *                   not check them, so a user below an overflowing middle node whose siblings are all in range is provable
+ *   d_bad_leaves    bad_cap x uint32, 4-byte aligned, NULL iff bad_cap == 0: the leaves with a non-zero word in increasing order,
+ *                   the first bad_cap of them (their places come from prefix sums over the data, never from the order in which
+ *                   workgroups finish); entries behind the listed ones stay unwritten
+ *   d_scratch       ss_mst_range_audit_scratch(depth) bytes, 4-byte aligned (the contents are the library's own)
+ * HOST output: summary_out[0] = the nodes with a non-zero flag, the root included; [1] = the leaves with a non-zero word;
+ * [2] = the leaves listed, min([1], bad_cap); [3] = the root's flag byte (the circuit leaves the root's sums to verification).
+ * d_node_balances is read in stream order -- the call sees work enqueued earlier on `stream` --, the device outputs are written
+ * in stream order, and the call waits for the stream once (one 16-byte copy) before it returns with the summary.
+ * SG_ERR_INVALID, before the device is touched and with summary_out as it was: a null pointer (d_bad_leaves: with bad_cap != 0);
+ * depth > 30; n_currencies 0 or above 64; n_bytes 0 or above 31; d_leaf_reasons, d_bad_leaves or d_scratch not 4-byte aligned;
+ * d_node_balances not 16-byte aligned. */
+int ss_mst_range_audit_dev(const void* d_node_balances, uint32_t depth, uint32_t n_currencies, uint32_t n_bytes, void* d_node_flags,
+                           void* d_leaf_reasons, void* d_bad_leaves, uint64_t bad_cap, void* d_scratch, uint64_t* summary_out,
+                           void* stream);
 
 #ifdef __cplusplus
 }
