@@ -66,6 +66,9 @@ SG_HD uint64_t mst_csv_rows(const uint8_t* body, uint64_t len, uint64_t newlines
   return e == 0 || body[e - 1] == '\n' ? newlines - 1 : newlines;
 }
 SG_HD uint64_t mst_csv_tiles(uint64_t body_len) { return (body_len + MST_CSV_TILE - 1) / MST_CSV_TILE; }
+// pass 2 is one workgroup of MST_CSV_SCAN_BLOCK lanes, a tile's word per lane and round: its rounds over a body
+static constexpr uint32_t MST_CSV_SCAN_BLOCK = 1024;
+SG_HD uint64_t mst_csv_scan_rounds(uint64_t body_len) { return (mst_csv_tiles(body_len) + MST_CSV_SCAN_BLOCK - 1) / MST_CSV_SCAN_BLOCK; }
 // the caller's work spaces: the tiles' words followed by the row count and the flags; row starts, then the spans (uint64 each)
 SG_HD uint64_t mst_csv_tile_words(uint64_t body_len) { return mst_csv_tiles(body_len) + 2; }
 SG_HD uint64_t mst_csv_span_words(uint64_t n_rows, uint32_t nc) { return n_rows + 1 + 2 * n_rows * (1 + (uint64_t)nc); }

@@ -100,7 +100,6 @@ hipError_t mst_csv_entries_launch(const uint8_t* d_body, const uint64_t* d_words
 
 // ------------------------------------------------------------------ the CSV reader's four passes (mst_csv.h)
 static constexpr uint32_t MST_CSV_BLOCK = MST_CSV_TILE / 16;    // a lane takes 16 bytes of the tile
-static constexpr uint32_t MST_CSV_SCAN_BLOCK = 1024;
 static_assert(MST_CSV_BLOCK == 256, "the passes' LDS arrays and wave counts are written for 256 lanes");
 
 // What a lane sees of its 16 bytes at body[pos ..): bit j of `newline`, `forbidden` and `bare_cr` is byte j's.  Bytes behind the

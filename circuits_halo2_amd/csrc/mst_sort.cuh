@@ -10,7 +10,7 @@
 namespace sg {
 
 static constexpr uint32_t MST_SORT_WAVES = MST_SORT_THREADS / 64;
-static constexpr uint32_t MST_SORT_SCAN_BLOCK = 1024;
+static_assert(MST_SORT_SCAN_ITEMS == 4, "a thread of the scan loads and stores one uint4 a step");
 
 // lengths, a row per thread: a name over the cap reports (row, 7) -- a row the split reported keeps its lower code under the
 // minimum, and one whose name span it left unwritten has the zeros the caller put there -- else the longest name grows
@@ -142,8 +142,8 @@ __global__ void __launch_bounds__(MST_SORT_SCAN_BLOCK) mst_sort_scan_kernel(uint
   if (!mst_sort_varies(head, pos)) return;
   __shared__ uint32_t s_w[MST_SORT_SCAN_BLOCK / 64];
   uint32_t carry = 0;
-  for (uint32_t base = 0; base < len; base += 4 * MST_SORT_SCAN_BLOCK) {
-    const uint32_t idx = base + threadIdx.x * 4;
+  for (uint32_t base = 0; base < len; base += MST_SORT_SCAN_ITEMS * MST_SORT_SCAN_BLOCK) {
+    const uint32_t idx = base + threadIdx.x * MST_SORT_SCAN_ITEMS;
     uint4 v = make_uint4(0, 0, 0, 0);
     if (idx < len) v = *reinterpret_cast<const uint4*>(hist + idx);
     uint32_t total;

@@ -46,6 +46,13 @@ SG_HD uint64_t mst_sort_side_words(uint64_t n_rows) { return (n_rows + 3) & ~3ul
 SG_HD uint64_t mst_sort_at_order(uint64_t n_rows, uint32_t side) { return MST_SORT_FRONT_WORDS + side * mst_sort_side_words(n_rows); }
 SG_HD uint64_t mst_sort_at_hist(uint64_t n_rows) { return mst_sort_at_order(n_rows, 2); }
 SG_HD uint64_t mst_sort_work_words(uint64_t n_rows) { return mst_sort_at_hist(n_rows) + MST_SORT_BINS * mst_sort_tiles(n_rows); }
+// A pass scans its histogram with one workgroup of MST_SORT_SCAN_BLOCK threads, MST_SORT_SCAN_ITEMS words a thread and step,
+// in [digit][tile] order: its steps over the histogram of n_rows.  A step's words are the tiles of some digits, not some tiles.
+static constexpr uint32_t MST_SORT_SCAN_BLOCK = 1024, MST_SORT_SCAN_ITEMS = 4;
+SG_HD uint64_t mst_sort_scan_steps(uint64_t n_rows) {
+  const uint64_t step = (uint64_t)MST_SORT_SCAN_ITEMS * MST_SORT_SCAN_BLOCK;
+  return (MST_SORT_BINS * mst_sort_tiles(n_rows) + step - 1) / step;
+}
 
 // the key byte of a name at position pos: zero behind its end
 SG_HD uint32_t mst_sort_digit(const uint8_t* body, uint64_t begin, uint64_t end, uint32_t pos) {

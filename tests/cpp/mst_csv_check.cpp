@@ -3,9 +3,11 @@
 // feeds "PATH N_CURRENCIES" lines on stdin.  The header is line 1 up to its '\n'; the delimiter is ';' if line 1 holds one,
 // else ','.  Answers, per file:
 //   body OFFSET DELIMITER(decimal) TILE ROW_CAP
+//   geom SCAN_BLOCK TILES SCAN_ROUNDS                     (pass 2's width, the body's tiles and the rounds of its scan)
 //   scan N_ROWS FLAGS(hex) PROBLEM_ROW PROBLEM_CODE       (the problem 0 0 where there is none, or where passes 3-4 did not run)
 //   span ROW NAME_BEGIN NAME_END BEGIN END ...            (one per row when nothing is wrong; offsets into the body)
 //   end
+// With arguments it reads no file: every argument is a body length, answered by its "geom" line alone.
 #include <cstdio>
 #include <fstream>
 #include <iostream>
@@ -15,7 +17,14 @@
 
 #include "mst_csv.h"
 
-int main() {
+static void geom(uint64_t body_len) {
+  std::printf("geom %u %llu %llu\n", sg::MST_CSV_SCAN_BLOCK, (unsigned long long)sg::mst_csv_tiles(body_len),
+              (unsigned long long)sg::mst_csv_scan_rounds(body_len));
+}
+
+int main(int argc, char** argv) {
+  for (int i = 1; i < argc; i++) geom(std::stoull(argv[i]));
+  if (argc > 1) return 0;
   std::string path;
   uint32_t nc;
   while (std::cin >> path >> nc) {
@@ -30,6 +39,7 @@ int main() {
     std::vector<uint8_t> body(text.begin() + body_off, text.end());
     const sg::MstCsvHost r = sg::mst_csv_host(body.data(), body.size(), delim, nc);
     std::printf("body %zu %u %u %u\n", body_off, delim, sg::MST_CSV_TILE, sg::MST_CSV_ROW_CAP);
+    geom(body.size());
     std::printf("scan %llu %x %llu %u\n", (unsigned long long)r.n_rows, r.flags, (unsigned long long)(r.problem >> 8),
                 (unsigned)(r.problem & 0xff));
     if (!r.flags && !r.problem && r.n_rows) {

@@ -3,11 +3,13 @@
 // to the first, gather.  tests/test_mst_sort_cpu.py writes files and feeds "PATH N_CURRENCIES" lines on stdin; header line and
 // delimiter as in mst_csv_check.cpp.  Answers, per file:
 //   body OFFSET DELIMITER(decimal) TILE_ROWS NAME_CAP
+//   geom SCAN_BLOCK SCAN_ITEMS BINS TILES SCAN_STEPS   (the scan's width, the rows' tiles and the steps of a pass's scan)
 //   sort N_ROWS FLAGS(hex) PROBLEM_ROW PROBLEM_CODE LONGEST PASSES_RUN
 //   order ROW ...                    (the file row of every leaf, when nothing is wrong)
 //   spans BEGIN END ...              (every leaf's name, offsets into the body)
 //   find INDEX ...                   (mst_find_name of every row's own name, then of two names that are absent)
 //   end
+// With arguments it reads no file: every argument is a row count, answered by its "geom" line alone.
 #include <cstdio>
 #include <fstream>
 #include <iostream>
@@ -17,7 +19,14 @@
 
 #include "mst_sort.h"
 
-int main() {
+static void geom(uint64_t n_rows) {
+  std::printf("geom %u %u %u %llu %llu\n", sg::MST_SORT_SCAN_BLOCK, sg::MST_SORT_SCAN_ITEMS, sg::MST_SORT_BINS,
+              (unsigned long long)sg::mst_sort_tiles(n_rows), (unsigned long long)sg::mst_sort_scan_steps(n_rows));
+}
+
+int main(int argc, char** argv) {
+  for (int i = 1; i < argc; i++) geom(std::stoull(argv[i]));
+  if (argc > 1) return 0;
   std::string path;
   uint32_t nc;
   while (std::cin >> path >> nc) {
@@ -32,6 +41,7 @@ int main() {
     std::vector<uint8_t> body(text.begin() + body_off, text.end());
     const sg::MstCsvHost csv = sg::mst_csv_host(body.data(), body.size(), delim, nc);
     std::printf("body %zu %u %u %u\n", body_off, delim, sg::MST_SORT_TILE, sg::MST_SORT_NAME_CAP);
+    geom(csv.n_rows);
     if (csv.flags || !csv.n_rows) {
       std::printf("sort %llu %x 0 0 0 0\nend\n", (unsigned long long)csv.n_rows, csv.flags);
       continue;

@@ -2,8 +2,12 @@
 csrc/mst_csv.h run serially) and on the device (test_gpu_mst_csv.py).  ACCEPTED: files inside the reader's subset -- it must take
 every one and find the fields `parse_csv_to_entries` finds.  REFUSED: files outside it, each with what the reader must
 report: a flag of the scan, or the lowest offending row and its code.  `tile` and `cap` are the reader's geometry
-(MST_CSV_TILE, MST_CSV_ROW_CAP): newlines and carriage returns are placed at the tile edges by the length of a name."""
+(MST_CSV_TILE, MST_CSV_ROW_CAP): newlines and carriage returns are placed at the tile edges by the length of a name.
+LARGE_ACCEPTED and LARGE_REFUSED, lists of their own, name generated files of 4 and 9 MiB (`large`): the bodies at which the
+reader's one-workgroup scan takes exactly one full round, a second and a third."""
+import functools
 import os
+import random
 
 from conftest import GOLDEN
 
@@ -82,6 +86,98 @@ def refused(tile: int, cap: int):
         "two_bad_rows_in_two_tiles": bad_row(1, ROW_EMPTY_BALANCE, h + few(0, 1) + "e,,2\n" + "n" * tile + ",1,2\n" + "x,1,2,3\n"),
     }
     return [(name,) + case for name, case in cases.items()]
+
+
+# ----------------------------------------------------------------------------- bodies beyond one round of the scan
+# Pass 2 is one workgroup that takes SCAN_BLOCK tiles' words a round (MST_CSV_SCAN_BLOCK of csrc/mst_csv.h, restated; the
+# check program prints it): a body over SCAN_BLOCK * tile bytes -- 4 MiB -- carries the newlines before a round into the next.
+SCAN_BLOCK = 1024
+ALPHABET = "abcdefghijklmnopqrstuvwxyzABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789"
+_LETTERS = bytes(ord(ALPHABET[b % len(ALPHABET)]) for b in range(256))
+
+
+def tiles_of(body_len: int, tile: int) -> int:
+    return -(-body_len // tile)
+
+
+def scan_rounds(body_len: int, tile: int) -> int:
+    return -(-tiles_of(body_len, tile) // SCAN_BLOCK)
+
+
+def large_rows(tile: int, body_len: int, open_end: bool = False):
+    """The rows (line ends included) of a body of exactly body_len bytes.  Names of 900 to 1100 ALPHABET letters, so that a few
+    thousand rows fill it and every round of the scan holds hundreds of newlines; every 37th row is short; one row longer than
+    a tile lies across the edge between tile SCAN_BLOCK - 1 and tile SCAN_BLOCK where the body goes on behind it; the last
+    row, stretched to end the body exactly, is longer than a tile as well.  Balances are distinct per row."""
+    rng = random.Random(20240611)
+    edge = SCAN_BLOCK * tile
+    rows, pos, crossed = [], 0, body_len < edge + 2 * tile
+    fields = lambda i: f",{1000 * i + 1},{1000 * i + 2}\n"
+    while body_len - pos > tile + 1200:
+        i = len(rows)
+        if not crossed and pos + 1200 > edge - 2000:
+            name, crossed = "X" * (tile + 100), True                 # starts in tile SCAN_BLOCK - 1, ends in tile SCAN_BLOCK
+            assert edge - tile < pos < edge < pos + len(name)
+        elif i % 37 == 5:
+            name = f"s{i}"
+        else:
+            name = rng.randbytes(rng.randint(900, 1100)).translate(_LETTERS).decode()
+        rows.append(name + fields(i))
+        pos += len(rows[-1])
+    tail = fields(len(rows))
+    if open_end:
+        tail = tail[:-1]
+    rows.append("Z" * (body_len - pos - len(tail)) + tail)
+    assert sum(map(len, rows)) == body_len and tile < len(rows[-1]) < 2 * tile and crossed
+    return rows
+
+
+def _shorter(row: str, by: int) -> str:
+    """the row with its name cut by `by` letters"""
+    name, rest = row.split(",", 1)
+    assert len(name) > by
+    return name[:-by] + "," + rest
+
+
+LARGE_ACCEPTED = ["tiles_1024", "tiles_1025", "tiles_1025_open_end", "tiles_2049"]
+# each a copy of tiles_1025 with one edit that only the scan's second round, or a flag kept through it, can report
+LARGE_REFUSED = ["quote_in_the_last_tile", "bare_cr_in_tile_1024", "quote_in_tile_3_only", "12a_in_the_last_row", "bad_rows_in_two_rounds"]
+
+
+@functools.lru_cache(maxsize=None)
+def large(name: str, tile: int):
+    """(text, n_currencies, flag or None, (row, code) or None) of a LARGE_ACCEPTED or LARGE_REFUSED case: the last two None
+    for an accepted one.  tiles_1024 ends with the last byte of tile 1023, a newline; tiles_1025 is that one byte longer, its
+    last newline alone in tile 1024; tiles_2049 takes a third round of 281 tiles, with a thousand newlines of its own."""
+    h, edge = header(2), SCAN_BLOCK * tile
+    if name in LARGE_ACCEPTED:
+        body_len = {"tiles_1024": edge, "tiles_1025": edge + 1, "tiles_1025_open_end": edge + 1, "tiles_2049": 2 * edge + 280 * tile + 777}[name]
+        return h + "".join(large_rows(tile, body_len, open_end=name.endswith("open_end"))), 2, None, None
+    rows = large_rows(tile, edge + 1)
+    last = len(rows) - 1
+    if name == "quote_in_the_last_tile":
+        rows[last] = rows[last][:-1] + '"'                           # tile 1024 is this one byte
+        return h + "".join(rows), 2, FLAG_BYTE, None
+    if name == "bare_cr_in_tile_1024":
+        rows[last] = rows[last][:-1] + "\r"
+        return h + "".join(rows), 2, FLAG_BARE_CR, None
+    if name == "quote_in_tile_3_only":
+        body = "".join(rows)
+        at = 3 * tile + 5
+        while not (body[at].isalnum() and body[at + 1].isalnum()):    # inside a name
+            at += 1
+        assert at < 4 * tile
+        return h + body[:at] + '"' + body[at + 1:], 2, FLAG_BYTE, None
+    if name == "12a_in_the_last_row":                                # 'x,12a,2' ends tile 1023, its newline is tile 1024
+        rows[last] = _shorter(rows[last], 8)
+        return h + "".join(rows + ["x,12a,2\n"]), 2, None, (last + 1, ROW_NOT_DECIMAL)
+    if name == "bad_rows_in_two_rounds":                             # the lower row wins, though the later row's code is lower
+        rows[last] = _shorter(rows[last], 8)
+        low = len(rows) // 2
+        assert len(rows[low]) > 900 and sum(map(len, rows[:low + 1])) < edge - tile
+        rows[low] = rows[low][:len(rows[low]) - 7].replace(",", "c") + ",12a,2\n"       # as long as it was
+        return h + "".join(rows + ["x,1,2,3\n"]), 2, None, (low, ROW_NOT_DECIMAL)
+    raise KeyError(name)
 
 
 def write_case(directory, name: str, content) -> str:

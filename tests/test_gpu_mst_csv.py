@@ -4,7 +4,12 @@ sg_mst_csv_scan_dev / sg_mst_csv_entries_dev), over the two fixed lists of mst_c
 A file inside the reader's subset is taken on the device and gives, bit for bit, the four arrays that today's path --
 parse_csv_to_entries, then from_entries -- gives, the root of the host-mirrored tree, and lazily the same entries.  A file
 outside it goes to the host with a reason, and ends as today's path ends on it: the same root or the same exception.  The two
-entry points are also called directly, with the body at odd addresses and guard words behind every buffer they write."""
+entry points are also called directly, with the body at odd addresses and guard words behind every buffer they write.
+
+The last part runs the lists LARGE_ACCEPTED and LARGE_REFUSED: bodies of 1024, 1025 and 2329 tiles, at which the one-workgroup
+scan of the tiles' newline counts (mst_csv_scan_kernel) takes one full round of MST_CSV_SCAN_BLOCK tiles, a second and a third.
+The host mirror scans with one serial loop, so the sum carried from round to round, the barrier between rounds, the flags kept
+over them and every word behind the 1024th are the device's alone: the scratch of the scan is compared word for word."""
 import ctypes as C
 import functools
 import os
@@ -147,6 +152,11 @@ def test_refused_files_end_as_todays_path_ends(gpu, files, name, tmp_path):
         path, nc = cases.write_case(tmp_path, name, HEADER_CASES[name][0]), HEADER_CASES[name][1]
     else:
         path, nc = files[name]
+    ends_as_todays_path_ends(path, nc, name)
+
+
+def ends_as_todays_path_ends(path, nc, name):
+    from circuits_halo2_amd.merkle_sum_tree import DeviceMerkleSumTree
     none, reason = DeviceMerkleSumTree._from_csv_on_device(path, nc)
     assert none is None and isinstance(reason, str) and reason
     want, _ = outcome(lambda: todays_tree(path, nc))
@@ -224,9 +234,10 @@ def _guarded(n_bytes):
     return torch.full((n_bytes + 64,), GUARD, dtype=torch.uint8, device="cuda")
 
 
-def run_reader(path, nc, shift):
+def run_reader(path, nc, shift, scanned=None):
     """scan + entries over the file placed so that its body lies `shift` bytes behind a 16-byte boundary -> (n, flags, problem,
-    users, balances); every buffer the entry points write ends in 64 guard bytes that must come back untouched"""
+    users, balances); every buffer the entry points write ends in 64 guard bytes that must come back untouched.  scanned: a
+    list that gets the tile scratch as the scan left it (the words of mst_csv_tile_words, as uint32)"""
     import torch
     from circuits_halo2_amd import ffi
     L = ffi.lib()
@@ -245,6 +256,8 @@ def run_reader(path, nc, shift):
     stream = ffi.current_stream_ptr()
     ffi.check(L.sg_mst_csv_scan_dev(ffi.dev_ptr(text), size, body_off, ffi.dev_ptr(tiles), C.byref(n), C.byref(flags), stream))
     assert (tiles[4 * (n_tiles + 2):] == GUARD).all(), "the bytes behind the tile scratch changed"
+    if scanned is not None:
+        scanned.append(tiles[:4 * (n_tiles + 2)].cpu().numpy().view(np.uint32))
     if flags.value or n.value == 0:
         return n.value, flags.value, 0, None, None
     rows = 1 << max(0, (n.value - 1).bit_length())
@@ -325,3 +338,90 @@ def test_wrong_arguments_leave_the_device_untouched(gpu, files):
     assert problem.value == 0
     _same(users[:32 * 16].cpu().numpy(), want_users, "usernames")
     _same(bals[:32 * 16 * 2].cpu().numpy(), want_bals, "balances")
+
+
+# ============================================================================= bodies beyond one round of the scan
+@pytest.fixture(scope="module")
+def large_files(tmp_path_factory):
+    """{case name: (path, n_currencies, flag, problem)} for LARGE_ACCEPTED and LARGE_REFUSED, generated from their fixed seeds"""
+    d = tmp_path_factory.mktemp("mst_csv_gpu_large")
+    out = {}
+    for name in cases.LARGE_ACCEPTED + cases.LARGE_REFUSED:
+        text, nc, flag, problem = cases.large(name, TILE)
+        out[name] = (cases.write_case(d, name, text), nc, flag, problem)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _todays_four(path, nc):
+    """today's path, once per file: the four arrays and the number of rows"""
+    t = todays_tree(path, nc)
+    arrays = {what: getattr(t, what).cpu().numpy() for what in ("d_users", "d_bals", "d_h", "d_b")}
+    for a in arrays.values():
+        a.setflags(write=False)
+    return arrays, sum(e[0] is not None for e in t.entries)
+
+
+def _body(path):
+    data = np.fromfile(path, dtype=np.uint8)
+    return data[data.tobytes().index(b"\n") + 1:]
+
+
+def _scan_must_be(words, body, flags):
+    """the scratch the scan leaves: before every tile the newlines of the tiles in front of it, then the rows, then the flags"""
+    n_tiles = -(-body.size // TILE)
+    padded = np.zeros(n_tiles * TILE, dtype=np.uint8)
+    padded[:body.size] = body
+    counts = (padded.reshape(n_tiles, TILE) == ord("\n")).sum(axis=1, dtype=np.uint64)
+    before = np.concatenate([[0], np.cumsum(counts)])
+    rows = int(before[-1]) + (0 if body[-1] == ord("\n") else 1)     # no large file ends in a blank line
+    assert words.size == n_tiles + 2 and n_tiles > cases.SCAN_BLOCK - 1
+    bad = np.flatnonzero(words[:n_tiles] != before[:-1])
+    assert bad.size == 0, f"{bad.size} of {n_tiles} tiles have a wrong count of newlines before them, first tile {bad[0]}: " \
+                          f"{words[bad[0]]} for {before[bad[0]]}"
+    assert (int(words[n_tiles]), int(words[n_tiles + 1])) == (rows, flags)
+    return rows
+
+
+LARGE_RUNS = [(name, 0) for name in cases.LARGE_ACCEPTED] + [("tiles_1025", 3)]      # shift 3: the byte loads
+
+
+@pytest.mark.parametrize("name,shift", LARGE_RUNS, ids=[f"{name}-{shift}" for name, shift in LARGE_RUNS])
+def test_large_bodies_through_the_entry_points(gpu, large_files, name, shift):
+    """the scan's scratch word for word against numpy's cumulative sum, then usernames and balances against today's path"""
+    path, nc, _, _ = large_files[name]
+    want, want_n = _todays_four(path, nc)
+    body = _body(path)
+    assert cases.scan_rounds(body.size, TILE) == {"tiles_1024": 1, "tiles_2049": 3}.get(name, 2)
+    scanned = []
+    n, flags, problem, users, bals = run_reader(path, nc, shift, scanned)
+    assert _scan_must_be(scanned[0], body, 0) == want_n
+    assert (n, flags, problem) == (want_n, 0, 0)
+    _same(users, want["d_users"], f"{name} shift {shift}: usernames")
+    _same(bals, want["d_bals"], f"{name} shift {shift}: balances")
+
+
+@pytest.mark.parametrize("name", ["tiles_1025", "tiles_2049"])
+def test_large_bodies_from_csv(gpu, large_files, name):
+    from circuits_halo2_amd.merkle_sum_tree import DeviceMerkleSumTree
+    path, nc, _, _ = large_files[name]
+    want, _ = _todays_four(path, nc)
+    tree = DeviceMerkleSumTree.from_csv(path, nc, 8)
+    assert tree.csv_ingest == "device" and tree.csv_fallback_reason is None
+    for what in ("d_users", "d_bals", "d_h", "d_b"):
+        _same(getattr(tree, what).cpu().numpy(), want[what], f"{name}: {what}")
+
+
+@pytest.mark.parametrize("name", cases.LARGE_REFUSED)
+def test_large_refusals_only_a_second_round_reports(gpu, large_files, name):
+    """a flag from the last tile, a flag from tile 3 kept through the second round, the last row's code, the lower of two rows
+    in two rounds -- from the entry points, and from_csv ends on the file as today's path ends"""
+    path, nc, flag, problem = large_files[name]
+    scanned = []
+    n, flags, word, _, _ = run_reader(path, nc, 0, scanned)
+    _scan_must_be(scanned[0], _body(path), flag or 0)
+    if flag is not None:
+        assert flags == flag
+    else:
+        assert flags == 0 and (word >> 8, word & 0xff) == problem
+    ends_as_todays_path_ends(path, nc, name)

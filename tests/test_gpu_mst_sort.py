@@ -5,7 +5,12 @@ A file the device takes gives the leaves in Python's stable order of the names' 
 `from_entries` over the host-sorted entries -- a path this change leaves alone and that is pinned to the oracle -- and for the
 small files the oracle's tree itself.  Such a tree finds, updates and proves users by name without parsing the file.  A file
 outside what the device sorts goes to the host with a reason and ends as today's path ends on it.  Both entry points are held
-to the stream-order contract of tests/test_gpu_stream_order.py, with its sequence."""
+to the stream-order contract of tests/test_gpu_stream_order.py, with its sequence.
+
+The part before the stream order runs the list LARGE: files of 32768 rows and more, at which the one-workgroup scan of a pass's
+histogram (mst_sort_scan_kernel) takes one full step of 4 x 1024 words, a second and a third -- its second call of the block
+scan, its carried sum, a [digit][tile] stride of 17, 33 and 97 -- and two files, high_bytes_65537 and rows_196609, in which
+the places of the rows depend on that sum (mst_sort_cases.steps_read).  The host mirror scans with one serial loop."""
 import ctypes as C
 import functools
 import os
@@ -119,7 +124,11 @@ def run_sort(path, nc):
 # ============================================================================= the entry point over the list
 @pytest.mark.parametrize("name", ACCEPTED)
 def test_order_spans_and_leaf_inputs(gpu, files, name):
-    path, nc = files[name]
+    order_spans_and_leaf_inputs(files[name], name)
+
+
+def order_spans_and_leaf_inputs(file, name):
+    path, nc = file
     ref = reference(path, nc)
     got = run_sort(path, nc)
     names = [e[0].encode() for e in ref["entries"]]
@@ -315,14 +324,18 @@ def test_find_present_duplicate_and_absent_names(gpu, files, monkeypatch):
 
 
 def test_update_by_name_equals_a_fresh_tree(gpu, files, monkeypatch):
+    update_by_name_equals_a_fresh_tree(files[f"random_{TILE + 1}"], (0, 1, 777, TILE // 2, TILE - 1, TILE), monkeypatch)
+
+
+def update_by_name_equals_a_fresh_tree(file, leaves, monkeypatch):
     from circuits_halo2_amd import merkle_sum_tree as M
-    path, nc = files[f"random_{TILE + 1}"]
+    path, nc = file
     ref = reference(path, nc)
     sorted_names = [e[0] for e in ref["sorted"]]
     first = {}
     for i, nm in enumerate(sorted_names):
         first.setdefault(nm, i)
-    picked = [sorted_names[i] for i in (0, 1, 777, TILE // 2, TILE - 1, TILE)]
+    picked = [sorted_names[i] for i in leaves]
     updates = [(nm, [10 ** 20 + 3 * j, 5 * j + 1]) for j, nm in enumerate(picked)] + [(picked[2], [42, 43])]      # a name twice: the last stays
     parses = _counting_parse(monkeypatch)
     tree = M.DeviceMerkleSumTree.from_csv_sorted(path, nc, 8)
@@ -337,6 +350,74 @@ def test_update_by_name_equals_a_fresh_tree(gpu, files, monkeypatch):
     for what in ("d_users", "d_bals", "d_h", "d_b"):
         _same(getattr(tree, what).cpu().numpy(), getattr(fresh, what).cpu().numpy(), what)
     assert tree.entries == fresh.entries and len(parses) == 1
+
+
+# ============================================================================= files beyond one step of a pass's scan
+@pytest.fixture(scope="module")
+def large_files(tmp_path_factory):
+    """{case name: (path, n_currencies)} for LARGE, generated from their fixed seeds"""
+    d = tmp_path_factory.mktemp("mst_sort_gpu_large")
+    return {name: (cases.write_case(d, name, cases.large(name, TILE)[0]), cases.large(name, TILE)[1]) for name in cases.LARGE}
+
+
+@pytest.mark.parametrize("name", cases.LARGE)
+def test_large_order_spans_and_leaf_inputs(gpu, large_files, name):
+    """order, name spans, usernames and balances as for the small files; the scratch is ss_mst_sort_scratch's at these sizes"""
+    path, _ = large_files[name]
+    n = int(name.rsplit("_", 1)[1])
+    assert cases.scan_steps(n, TILE) == {32768: 1, 32769: 2, 65537: 3, 196609: 7}[n]
+    if name == "hex64_32769":                                 # the CSV reader's scan takes its second round in the same call
+        assert -(-(os.path.getsize(path) - len(cases.header(2, eol="\r\n"))) // 4096) > 1024
+    order_spans_and_leaf_inputs(large_files[name], name)
+
+
+@pytest.mark.parametrize("name", ["rows_32769", "hex64_32769", "pool_300_32769", "high_bytes_65537", "rows_196609"])
+def test_large_from_csv_sorted(gpu, large_files, name):
+    from circuits_halo2_amd.merkle_sum_tree import DeviceMerkleSumTree
+    path, nc = large_files[name]
+    ref = reference(path, nc)
+    tree = DeviceMerkleSumTree.from_csv_sorted(path, nc, 8)
+    assert tree.csv_ingest == "device" and tree.csv_fallback_reason is None and tree.is_sorted and tree.depth == ref["depth"]
+    for what in ("d_users", "d_bals", "d_h", "d_b"):
+        _same(getattr(tree, what).cpu().numpy(), ref[what], f"{name}: {what}")
+
+
+def test_find_pool_names_across_all_tiles(gpu, large_files, monkeypatch):
+    """every name of the pool -> its first leaf, in one call of more than 256 queries and before any parse; absent names below,
+    between and above the pool's"""
+    from circuits_halo2_amd import merkle_sum_tree as M
+    path, nc = large_files["pool_300_32769"]
+    ref = reference(path, nc)
+    file_names = [e[0] for e in ref["entries"]]
+    sorted_names = [e[0] for e in ref["sorted"]]
+    first = {}
+    for i, nm in enumerate(sorted_names):
+        first.setdefault(nm, i)
+    pool = sorted(first, key=str.encode)
+    assert len(pool) == 300
+    parses = _counting_parse(monkeypatch)
+    tree = M.DeviceMerkleSumTree.from_csv_sorted(path, nc, 8)
+    assert tree.csv_ingest == "device"
+    queries = pool + file_names[:5] + file_names[-5:] + [sorted_names[-1], sorted_names[0]]     # the first and the last tile's, of file and leaves
+    assert len(queries) > 256
+    assert tree.indices_of_usernames(queries) == [first[nm] for nm in queries]
+    assert min(first.values()) == 0 and max(first.values()) > 15 * TILE                       # leaves of the first tile and of the 16th
+    between = [pool[k] + "\x01" for k in (0, 150, 298)] + [pool[150][:-1] + chr(ord(pool[150][-1]) - 1) + "~"]
+    absent = ["", "\x01", pool[0][:-1] if len(pool[0]) > 1 else "#"] + between + [pool[-1] + "0", "~", "\x7f" * CAP]
+    assert all(a not in first for a in absent)
+    for a in absent:
+        with pytest.raises(KeyError, match="Username not found"):
+            tree.indices_of_usernames(pool + [a])
+    assert parses == []
+
+
+def test_large_update_by_name_equals_a_fresh_tree(gpu, large_files, monkeypatch):
+    """users of the last tile -- the last leaves, and the name of the file's last row -- in a tree of 17 tiles"""
+    path, nc = large_files["rows_32769"]
+    ref = reference(path, nc)
+    n = len(ref["sorted"])
+    last_row = [e[0] for e in ref["sorted"]].index(ref["entries"][-1][0])
+    update_by_name_equals_a_fresh_tree(large_files["rows_32769"], (n - 1, n - 2, last_row, 16 * TILE - 1, TILE, 0), monkeypatch)
 
 
 # ============================================================================= stream order

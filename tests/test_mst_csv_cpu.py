@@ -2,7 +2,9 @@
 kernels compile, run by the header's own serial passes in tests/cpp/mst_csv_check.cpp, built by the host compiler under
 address / undefined sanitizers.  Two fixed lists of files (mst_csv_cases.py): every accepted one comes out with the fields
 Python's csv finds, byte for byte, and the balances `parse_csv_to_entries` returns; every refused one with the flag, or the
-lowest offending row and its code.  And what the two entry points refuse before they touch a device."""
+lowest offending row and its code.  The lists LARGE_ACCEPTED and LARGE_REFUSED the same, with the proof that they reach one,
+two and three rounds of the one-workgroup scan, whose width is restated in mst_csv_cases.py and compared with the header's
+here.  And what the two entry points refuse before they touch a device."""
 import csv
 import ctypes as C
 import os
@@ -30,7 +32,7 @@ def exe(tmp_path_factory):
 
 
 def ask(exe, files):
-    """[(path, nc)] -> per file {"body", "delim", "n", "flags", "problem": (row, code), "spans": [[begin, end, ..] per row]}"""
+    """[(path, nc)] -> per file {"body", "delim", "geom", "n", "flags", "problem": (row, code), "spans": [[begin, end, ..] per row]}"""
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="halt_on_error=1")
     text = "".join(f"{path} {nc}\n" for path, nc in files)
     r = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=120, env=env)
@@ -42,6 +44,8 @@ def ask(exe, files):
         if w[0] == "body":
             cur = {"body": int(w[1]), "delim": chr(int(w[2])), "spans": []}
             assert (int(w[3]), int(w[4])) == (TILE, CAP)
+        elif w[0] == "geom":
+            cur["geom"] = tuple(int(x) for x in w[1:])                  # (SCAN_BLOCK, tiles, rounds)
         elif w[0] == "scan":
             cur.update(n=int(w[1]), flags=int(w[2], 16), problem=(int(w[3]), int(w[4])))
         elif w[0] == "span":
@@ -77,7 +81,10 @@ def test_the_lists_hold_what_they_must():
 @pytest.mark.parametrize("case", ACCEPTED, ids=[c[0] for c in ACCEPTED])
 def test_accepted_files_come_out_as_csv_reads_them(answers, case):
     name, _, nc = case
-    a = answers[name]
+    comes_out_as_csv_reads_it(answers[name], name, nc)
+
+
+def comes_out_as_csv_reads_it(a, name, nc):
     with open(a["path"], "rb") as f:
         data = f.read()
     body = data[a["body"]:]
@@ -109,6 +116,69 @@ def test_a_body_without_rows(exe, tmp_path):
         files.append((cases.write_case(tmp_path, name, cases.header(2) + tail), 2))
     for a in ask(exe, files):
         assert a["n"] == 0 and a["flags"] == 0 and a["problem"] == (0, 0)
+
+
+# ============================================================================= bodies beyond one round of the scan
+def test_scan_geometry_is_the_headers(exe):
+    """MST_CSV_SCAN_BLOCK and mst_csv_scan_rounds as mst_csv_cases.py restates them, at the edges of one, two and three rounds"""
+    edge = cases.SCAN_BLOCK * TILE
+    lengths = [0, 1, TILE, TILE + 1, edge - 1, edge, edge + 1, 2 * edge, 2 * edge + 1, 3 * edge, 3 * edge + 1, (1 << 32) - 1]
+    out = subprocess.run([exe] + [str(n) for n in lengths], capture_output=True, text=True, timeout=60, check=True).stdout.split("\n")
+    want = [f"geom {cases.SCAN_BLOCK} {cases.tiles_of(n, TILE)} {cases.scan_rounds(n, TILE)}" for n in lengths]
+    assert out[:-1] == want and cases.SCAN_BLOCK == 1024
+    assert [cases.scan_rounds(n, TILE) for n in (0, 1, edge, edge + 1, 2 * edge + 1)] == [0, 1, 1, 2, 3]
+
+
+@pytest.fixture(scope="module")
+def large_answers(exe, tmp_path_factory):
+    """the program's answer for every large case, by name: one run"""
+    d = tmp_path_factory.mktemp("mst_csv_large")
+    names = cases.LARGE_ACCEPTED + cases.LARGE_REFUSED
+    files = [(cases.write_case(d, name, cases.large(name, TILE)[0]), cases.large(name, TILE)[1]) for name in names]
+    return {name: dict(a, path=path) for name, (path, _), a in zip(names, files, ask(exe, files))}
+
+
+def test_the_large_lists_reach_one_two_and_three_rounds(large_answers):
+    """exactly one full round (1024 tiles, the body's last byte a newline), two rounds by one byte, three rounds; the
+    program's tiles and rounds are the restated ones; every refused file is a two-round body"""
+    geom = {name: a["geom"] for name, a in large_answers.items()}
+    assert {g[0] for g in geom.values()} == {cases.SCAN_BLOCK}
+    for name, (_, tiles, rounds) in geom.items():
+        body_len = os.path.getsize(large_answers[name]["path"]) - large_answers[name]["body"]
+        assert (tiles, rounds) == (cases.tiles_of(body_len, TILE), cases.scan_rounds(body_len, TILE)), name
+    assert geom["tiles_1024"][1:] == (1024, 1) and geom["tiles_1025"][1:] == (1025, 2) and geom["tiles_1025_open_end"][1:] == (1025, 2)
+    assert geom["tiles_2049"][1] >= 2049 and geom["tiles_2049"][2] == 3
+    assert all(geom[name][1:] == (1025, 2) for name in cases.LARGE_REFUSED)
+    edge = cases.SCAN_BLOCK * TILE
+    for name in cases.LARGE_ACCEPTED:
+        with open(large_answers[name]["path"], "rb") as f:
+            body = f.read()[large_answers[name]["body"]:]
+        assert (body[-1:] == b"\n") == (not name.endswith("open_end")), name
+        rounds = [body[r * edge:(r + 1) * edge].count(b"\n") for r in range(geom[name][2])]
+        if name == "tiles_2049":
+            assert min(rounds) > 1000                             # every round holds many newlines, the prefixes behind the first depend on it
+        else:
+            assert rounds[0] > 1000 and rounds[1:] in ([], [1], [0])
+        long_rows = [r for r in body.split(b"\n") if len(r) > TILE]
+        starts = [body.index(r) for r in long_rows]
+        if len(body) > edge:                                      # a row longer than a tile with bytes in tile 1023 and in tile 1024
+            assert any(s < edge <= s + len(r) for s, r in zip(starts, long_rows)), name
+        assert any(len(r) < 20 for r in body.split(b"\n")[:-1]) and long_rows
+
+
+@pytest.mark.parametrize("name", cases.LARGE_ACCEPTED)
+def test_large_accepted_files_come_out_as_csv_reads_them(large_answers, name):
+    comes_out_as_csv_reads_it(large_answers[name], name, 2)
+
+
+@pytest.mark.parametrize("name", cases.LARGE_REFUSED)
+def test_large_refused_files_are_reported(large_answers, name):
+    _, _, flag, problem = cases.large(name, TILE)
+    a = large_answers[name]
+    if flag is not None:
+        assert a["flags"] == flag and a["spans"] == [], name
+    else:
+        assert a["flags"] == 0 and a["problem"] == problem and a["spans"] == [], name
 
 
 # ============================================================================= the entry points: refusals, no device needed

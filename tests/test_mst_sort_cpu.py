@@ -1,7 +1,9 @@
 """The device sort of a snapshot's usernames without a GPU: the rules, the work space and the tile edges of csrc/mst_sort.h, whose
 text the kernels compile, run by the header's own serial steps in tests/cpp/mst_sort_check.cpp (after the CSV reader's four
 passes), built by the host compiler under address / undefined sanitizers.  One fixed list of files (mst_sort_cases.py): every
-accepted one comes out in Python's stable order of the names' bytes, the refused one with its (row, 7).  And the geometry, the
+accepted one comes out in Python's stable order of the names' bytes, the refused one with its (row, 7).  The list LARGE the same,
+with the proof that it reaches one, two and three steps of a pass's one-workgroup scan, whose width is restated in
+mst_sort_cases.py and compared with the header's here, and that two of its files read a carried sum.  And the geometry, the
 exports of include/summa_snapshot.h, and what its two entry points refuse before they touch a device."""
 import ctypes as C
 import os
@@ -34,7 +36,7 @@ def exe(tmp_path_factory):
 
 
 def ask(exe, files):
-    """[(path, nc)] -> per file {"body", "n", "flags", "problem": (row, code), "longest", "passes", "order", "spans", "find"}"""
+    """[(path, nc)] -> per file {"body", "geom", "n", "flags", "problem": (row, code), "longest", "passes", "order", "spans", "find"}"""
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="halt_on_error=1")
     text = "".join(f"{path} {nc}\n" for path, nc in files)
     r = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=120, env=env)
@@ -46,6 +48,8 @@ def ask(exe, files):
         if w[0] == "body":
             cur = {"body": int(w[1]), "order": None, "spans": None, "find": None}
             assert (int(w[3]), int(w[4])) == (TILE, CAP)
+        elif w[0] == "geom":
+            cur["geom"] = tuple(int(x) for x in w[1:])                  # (SCAN_BLOCK, SCAN_ITEMS, BINS, tiles, steps)
         elif w[0] == "sort":
             cur.update(n=int(w[1]), flags=int(w[2], 16), problem=(int(w[3]), int(w[4])), longest=int(w[5]), passes=int(w[6]))
         elif w[0] in ("order", "spans", "find"):
@@ -74,7 +78,10 @@ def test_the_list_holds_what_it_must():
 @pytest.mark.parametrize("case", ACCEPTED, ids=[c[0] for c in ACCEPTED])
 def test_accepted_files_come_out_in_pythons_stable_order(answers, case):
     name, _, nc, _ = case
-    a = answers[name]
+    comes_out_in_pythons_stable_order(answers[name], name, nc)
+
+
+def comes_out_in_pythons_stable_order(a, name, nc):
     # the host's steps of today's from_csv_sorted succeed on the file: the parse, the sort, from_entries' checks (what is left
     # of it is hashing on the device: tests/test_gpu_mst_sort.py builds the tree)
     entries, _ = parse_csv_to_entries(a["path"], nc)
@@ -124,6 +131,78 @@ def test_a_lower_code_in_a_lower_row_wins(exe, tmp_path):
     assert got == [(1, 5), (1, 7), (1, 5), (1, 2)]
 
 
+# ============================================================================= files beyond one step of a pass's scan
+def test_scan_geometry_is_the_headers(exe):
+    """MST_SORT_SCAN_BLOCK, MST_SORT_SCAN_ITEMS and mst_sort_scan_steps as mst_sort_cases.py restates them, at the edges of one, two
+    and three steps"""
+    sizes = [1, TILE, TILE + 1, 16 * TILE - 1, 16 * TILE, 16 * TILE + 1, 32 * TILE, 32 * TILE + 1, 48 * TILE, 48 * TILE + 1, (1 << 32) - 1]
+    out = subprocess.run([exe] + [str(n) for n in sizes], capture_output=True, text=True, timeout=60, check=True).stdout.split("\n")
+    want = [f"geom {cases.SCAN_BLOCK} {cases.SCAN_ITEMS} {cases.BINS} {cases.tiles_of(n, TILE)} {cases.scan_steps(n, TILE)}" for n in sizes]
+    assert out[:-1] == want and (cases.SCAN_BLOCK, cases.SCAN_ITEMS, cases.BINS) == (1024, 4, 256)
+    assert [cases.scan_steps(n, TILE) for n in (1, 32768, 32769, 65536, 65537)] == [1, 1, 2, 2, 3]
+
+
+@pytest.fixture(scope="module")
+def large_answers(exe, tmp_path_factory):
+    """the program's answer for every large case, by name: one run"""
+    d = tmp_path_factory.mktemp("mst_sort_large")
+    files = [(cases.write_case(d, name, cases.large(name, TILE)[0]), cases.large(name, TILE)[1]) for name in cases.LARGE]
+    return {name: dict(a, path=path) for name, (path, _), a in zip(cases.LARGE, files, ask(exe, files))}
+
+
+def test_the_large_list_reaches_one_two_and_three_steps(large_answers):
+    """exactly one full step (32768 rows, 16 tiles), two steps by one row, three steps (65537 rows, 33 tiles); the program's tiles
+    and steps are the restated ones.  And which steps' words a row reads: with names of the reader's subset only those of the
+    first step up to 32 tiles, so the two files behind the list's first eight are the ones whose leaves depend on a carried sum."""
+    geom = {name: a["geom"] for name, a in large_answers.items()}
+    assert {g[:3] for g in geom.values()} == {(cases.SCAN_BLOCK, cases.SCAN_ITEMS, cases.BINS)}
+    names = {name: cases.names_of(cases.large(name, TILE)[0]) for name in cases.LARGE}
+    for name, a in large_answers.items():
+        assert a["n"] == len(names[name]) == int(name.rsplit("_", 1)[1])
+        assert geom[name][3:] == (cases.tiles_of(a["n"], TILE), cases.scan_steps(a["n"], TILE)), name
+    assert geom["rows_32768"][3:] == (16, 1) and geom["rows_32769"][3:] == (17, 2) and geom["rows_65537"][3:] == (33, 3)
+    assert all(geom[name][3:] == (17, 2) for name in cases.LARGE if name.endswith("_32769"))
+    assert geom["high_bytes_65537"][3:] == (33, 3) and geom["rows_196609"][3:] == (97, 7)
+    read = {name: cases.steps_read(names[name], TILE) for name in cases.LARGE}
+    assert all(read[name] == {0} for name in cases.LARGE[:8])
+    assert read["high_bytes_65537"] == {0, 1} and read["rows_196609"] == {0, 1, 2}
+    # hex64_32769 is past one round of the CSV reader's scan as well (mst_csv_cases.SCAN_BLOCK tiles of 4096 bytes)
+    hex64 = large_answers["hex64_32769"]
+    assert os.path.getsize(hex64["path"]) - hex64["body"] > 1024 * 4096 and hex64["longest"] == hex64["passes"] == CAP
+    pool = names["pool_300_32769"]
+    assert len(set(pool)) == 300 and all(len(set(pool[t * TILE:(t + 1) * TILE])) >= 295 for t in range(16))
+    skew, skew0 = names["skew_32769"], names["skew_tile0_32769"]
+    assert set(skew[:16 * TILE]) == {b"samenamea"} and skew[16 * TILE:] == [b"samenameb"]
+    assert set(skew0[TILE:]) == {b"samenamea"} and len(set(skew0[:TILE])) == len(cases.ALPHABET)
+    chain = [i for i, nm in enumerate(names["prefix_tail_32769"]) if nm == b"a" * len(nm)]
+    assert {len(names["prefix_tail_32769"][i]) for i in chain} == set(range(CAP + 1)) and {i // TILE for i in chain} == set(range(17))
+
+
+def test_a_scan_that_drops_its_carried_sum_shows_in_the_last_two_files_only():
+    """A model of the last pass (byte 0) with the kernel's stepped scan, once as it is and once with every step starting from 0:
+    the places differ exactly in the files whose rows read a word behind the first step.  This is why the list does not end
+    at 65537 rows of ALPHABET names: such a file takes three steps and none of its rows would notice a wrong carry."""
+    import numpy as np
+    step = cases.SCAN_ITEMS * cases.SCAN_BLOCK
+    for name in cases.LARGE:
+        names = cases.names_of(cases.large(name, TILE)[0])
+        n, tiles = len(names), cases.tiles_of(len(names), TILE)
+        src = sorted(range(n), key=lambda i: names[i][1:])            # the order the earlier passes leave
+        digit = np.array([names[i][0] if names[i] else 0 for i in src])
+        word = digit * tiles + np.arange(n) // TILE
+        hist = np.bincount(word, minlength=cases.BINS * tiles)
+        whole = np.cumsum(hist) - hist
+        stepped = whole - np.repeat(whole[::step], step)[:whole.size]  # every step's prefix sums without what was before it
+        reads_carried = bool((whole[word] != stepped[word]).any())
+        assert reads_carried == (name in ("high_bytes_65537", "rows_196609")), name
+        assert reads_carried == (cases.steps_read(names, TILE) != {0}), name
+
+
+@pytest.mark.parametrize("name", cases.LARGE)
+def test_large_files_come_out_in_pythons_stable_order(large_answers, name):
+    comes_out_in_pythons_stable_order(large_answers[name], name, 2)
+
+
 # ============================================================================= the entry points: exports, geometry, refusals
 def test_exports_are_the_headers_prototypes():
     text = open(os.path.join(ROOT, "include", "summa_snapshot.h")).read()
@@ -152,7 +231,7 @@ def test_scratch_size():
     for n in (0, 1 << 32):
         assert L.ss_mst_sort_scratch(n, C.byref(size)) == SG_ERR_INVALID and size.value == 77
     assert L.ss_mst_sort_scratch(5, None) == SG_ERR_INVALID
-    for n in (1, TILE, TILE + 1, 3 * TILE + 5):
+    for n in (1, TILE, TILE + 1, 3 * TILE + 5, 16 * TILE, 16 * TILE + 1, 32 * TILE + 1, 96 * TILE + 1):
         assert L.ss_mst_sort_scratch(n, C.byref(size)) == 0
         tiles = -(-n // TILE)
         assert size.value == 4 * (64 + 2 * (-(-n // 4) * 4) + 256 * tiles), n
