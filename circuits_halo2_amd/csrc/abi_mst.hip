@@ -1,10 +1,12 @@
 // C ABI, Merkle sum tree family: the inclusion circuit's keygen columns and sg_mst_* -- leaves, levels and whole trees, entries from
-// names and decimal balances, the in-place update, the range audit and the circuit's witness (summa_gpu.hip holds the core).
+// names and decimal balances, the in-place update, the range audit, the index and report of the names and the circuit's witness
+// (summa_gpu.hip holds the core).
 #include "abi_internal.h"
 #include "../../include/summa_snapshot.h"
 #include "mst_csv.h"
 #include "mst_sort.h"
 #include "mst_audit.h"
+#include "mst_names.h"
 #include "mst_entries.h"
 #include "mst_update_plan.h"
 
@@ -18,6 +20,31 @@ const char* shape_problem(uint32_t n_currencies, uint32_t depth, bool rest_ok = 
   return n_currencies == 0 || n_currencies > 64 || depth > kMaxDepth || !rest_ok ? "bad size" : nullptr;
 }
 int refuse(const char* who, const char* problem) { return fail(SG_ERR_INVALID, (std::string(who) + ": " + problem).c_str()); }
+// The lookup by name of `who`, ss_mst_find_names (d_order nullptr: the position found is the leaf) or ss_mst_find_leaves (the
+// position goes through d_order, in the kernel).  The queries travel in one work space of the caller's stream: the offsets, the
+// answers, then the bytes.
+int find_names(const std::string& who, const void* d_bytes, uint64_t len, uint64_t body_off, const void* d_name_spans, const void* d_order,
+               uint64_t n_rows, const uint8_t* name_bytes, const uint64_t* name_off, size_t m, uint32_t* index_out, void* stream) {
+  if (m == 0 || m >= (1ull << 32) || n_rows == 0 || n_rows >= (1ull << 32) || body_off > len || len - body_off >= (1ull << 32) ||
+      ((uintptr_t)d_name_spans & 3) || ((uintptr_t)d_order & 3))
+    return refuse(who.c_str(), "bad size");
+  if (name_off[0] != 0) return refuse(who.c_str(), "offsets do not start at 0");
+  for (size_t j = 0; j < m; j++)
+    if (name_off[j + 1] < name_off[j]) return refuse(who.c_str(), "offsets decrease");
+  const size_t query_len = name_off[m], at_out = 8 * (m + 1), at_bytes = (at_out + 4 * m + 7) & ~(size_t)7;
+  LOCKED_CTX();
+  hipStream_t s = pick_stream(stream);
+  uint8_t* d = nullptr;
+  CHECK_HIP(scratch_for(s, 14, at_bytes + query_len + 1, &d), (who + ": work space").c_str());
+  CHECK_HIP(hipMemcpyAsync(d, name_off, 8 * (m + 1), hipMemcpyHostToDevice, s), (who + ": offsets").c_str());
+  if (query_len) CHECK_HIP(hipMemcpyAsync(d + at_bytes, name_bytes, query_len, hipMemcpyHostToDevice, s), (who + ": names").c_str());
+  CHECK_HIP(mst_find_names_launch(static_cast<const uint8_t*>(d_bytes) + body_off, len - body_off, static_cast<const uint32_t*>(d_name_spans),
+                                  static_cast<const uint32_t*>(d_order), (uint32_t)n_rows, d + at_bytes,
+                                  reinterpret_cast<const uint64_t*>(d), m, reinterpret_cast<uint32_t*>(d + at_out), s),
+            who.c_str());
+  TRY(download(reinterpret_cast<uint8_t*>(index_out), d + at_out, 4 * m, s));   // waits for the stream
+  return SG_OK;
+}
 
 }  // namespace
 
@@ -226,28 +253,83 @@ int ss_mst_csv_entries_sorted_dev(const void* d_bytes, uint64_t len, uint64_t bo
   CHECK_HIP(mst_csv_entries_launch(body, sorted_words, n_rows, rows, n_currencies, d_usernames, d_balances, s), "ss_mst_csv_entries_sorted");
   return SG_OK;
 }
-// The queries travel in one work space of the caller's stream: the offsets, the answers, then the bytes.
 int ss_mst_find_names(const void* d_bytes, uint64_t len, uint64_t body_off, const void* d_name_spans, uint64_t n_rows,
                       const uint8_t* name_bytes, const uint64_t* name_off, size_t m, uint32_t* index_out, void* stream) {
   if (!d_bytes || !d_name_spans || !name_bytes || !name_off || !index_out) return fail(SG_ERR_INVALID, "ss_mst_find_names: null argument");
-  if (m == 0 || m >= (1ull << 32) || n_rows == 0 || n_rows >= (1ull << 32) || body_off > len || len - body_off >= (1ull << 32) ||
-      ((uintptr_t)d_name_spans & 3))
-    return refuse("ss_mst_find_names", "bad size");
-  if (name_off[0] != 0) return refuse("ss_mst_find_names", "offsets do not start at 0");
-  for (size_t j = 0; j < m; j++)
-    if (name_off[j + 1] < name_off[j]) return refuse("ss_mst_find_names", "offsets decrease");
-  const size_t query_len = name_off[m], at_out = 8 * (m + 1), at_bytes = (at_out + 4 * m + 7) & ~(size_t)7;
+  return find_names("ss_mst_find_names", d_bytes, len, body_off, d_name_spans, nullptr, n_rows, name_bytes, name_off, m, index_out, stream);
+}
+// The names beside a tree whose leaves stay in file order (include/summa_snapshot.h; mst_names.h has the rules, mst_names.cuh the
+// kernels).  The index is the sorted constructor up to the hashing: the split again -- sg_mst_csv_entries_dev declares its span
+// scratch the library's own, so nothing here depends on what that call left there --, the lengths, one copy and one wait for the
+// problem word and the longest name, the sort, and the split's name spans narrowed into d_leaf_name_spans.
+int ss_mst_csv_name_index_dev(const void* d_bytes, uint64_t len, uint64_t body_off, const void* d_tile_scratch, uint32_t delimiter,
+                              uint32_t n_currencies, uint64_t n_rows, void* d_span_scratch, void* d_sort_scratch, void* d_order,
+                              void* d_name_spans, void* d_leaf_name_spans, uint64_t* problem_out, void* stream) {
+  if (!d_bytes || !d_tile_scratch || !d_span_scratch || !d_sort_scratch || !d_order || !d_name_spans || !d_leaf_name_spans || !problem_out)
+    return fail(SG_ERR_INVALID, "ss_mst_csv_name_index: null argument");
+  const bool delimiter_ok = delimiter < 256 && delimiter != '\n' && delimiter != '\r' && !(delimiter >= '0' && delimiter <= '9') && !mst_csv_forbidden((uint8_t)delimiter);
+  const bool sizes_ok = body_off < len && len - body_off < (1ull << 32) && n_rows != 0 && n_rows <= len - body_off &&
+                        !((uintptr_t)d_tile_scratch & 3) && !((uintptr_t)d_span_scratch & 7) && delimiter_ok && !((uintptr_t)d_sort_scratch & 15) &&
+                        !((uintptr_t)d_order & 3) && !((uintptr_t)d_name_spans & 3) && !((uintptr_t)d_leaf_name_spans & 3);
+  if (const char* problem = shape_problem(n_currencies, 0, sizes_ok)) return refuse("ss_mst_csv_name_index", problem);
+  const uint64_t body_len = len - body_off;
+  const uint8_t* body = static_cast<const uint8_t*>(d_bytes) + body_off;
+  uint64_t* words = static_cast<uint64_t*>(d_span_scratch);
+  uint64_t* sorted_words = words + mst_csv_span_words(n_rows, n_currencies);
+  uint32_t* work = static_cast<uint32_t*>(d_sort_scratch);
+  const MstCsvSpans spans = mst_csv_spans(words, n_rows, n_currencies);
   LOCKED_CTX();
   hipStream_t s = pick_stream(stream);
-  uint8_t* d = nullptr;
-  CHECK_HIP(scratch_for(s, 14, at_bytes + query_len + 1, &d), "ss_mst_find_names: work space");
-  CHECK_HIP(hipMemcpyAsync(d, name_off, 8 * (m + 1), hipMemcpyHostToDevice, s), "ss_mst_find_names: offsets");
-  if (query_len) CHECK_HIP(hipMemcpyAsync(d + at_bytes, name_bytes, query_len, hipMemcpyHostToDevice, s), "ss_mst_find_names: names");
-  CHECK_HIP(mst_find_names_launch(static_cast<const uint8_t*>(d_bytes) + body_off, len - body_off, static_cast<const uint32_t*>(d_name_spans),
-                                  (uint32_t)n_rows, d + at_bytes, reinterpret_cast<const uint64_t*>(d), m,
-                                  reinterpret_cast<uint32_t*>(d + at_out), s),
-            "ss_mst_find_names");
-  TRY(download(reinterpret_cast<uint8_t*>(index_out), d + at_out, 4 * m, s));   // waits for the stream
+  CHECK_HIP(hipMemsetAsync(work, 0, 4 * MST_SORT_FRONT_WORDS, s), "ss_mst_csv_name_index: work space");
+  CHECK_HIP(hipMemsetAsync(spans.name_begin, 0, 16 * n_rows, s), "ss_mst_csv_name_index: name spans");   // name_end follows
+  CHECK_HIP(mst_csv_split_launch(body, body_len, static_cast<const uint32_t*>(d_tile_scratch), (uint8_t)delimiter, n_currencies, n_rows, words,
+                                 reinterpret_cast<uint64_t*>(work + MST_SORT_AT_PROBLEM), s),
+            "ss_mst_csv_name_index: split");
+  CHECK_HIP(mst_sort_lengths_launch(words, n_rows, n_currencies, work, s), "ss_mst_csv_name_index: lengths");
+  uint64_t result[2] = {0, 0};                               // the problem word, then the longest name in the low half
+  TRY(download(reinterpret_cast<uint8_t*>(result), work, sizeof result, s));
+  *problem_out = result[0] == MST_CSV_NO_PROBLEM ? 0 : result[0];
+  if (*problem_out) return SG_OK;                            // the outputs stay unwritten
+  CHECK_HIP(mst_sort_launch(body, words, n_rows, n_currencies, (uint32_t)result[1], work, static_cast<uint32_t*>(d_order),
+                            static_cast<uint32_t*>(d_name_spans), sorted_words, s),
+            "ss_mst_csv_name_index: sort");
+  CHECK_HIP(mst_names_leaf_spans_launch(words, n_rows, n_currencies, static_cast<uint32_t*>(d_leaf_name_spans), s),
+            "ss_mst_csv_name_index: leaf spans");
+  return SG_OK;
+}
+int ss_mst_find_leaves(const void* d_bytes, uint64_t len, uint64_t body_off, const void* d_name_spans, const void* d_order, uint64_t n_rows,
+                       const uint8_t* name_bytes, const uint64_t* name_off, size_t m, uint32_t* index_out, void* stream) {
+  if (!d_bytes || !d_name_spans || !d_order || !name_bytes || !name_off || !index_out)
+    return fail(SG_ERR_INVALID, "ss_mst_find_leaves: null argument");
+  return find_names("ss_mst_find_leaves", d_bytes, len, body_off, d_name_spans, d_order, n_rows, name_bytes, name_off, m, index_out, stream);
+}
+// The report of the names that occur more than once: three launches behind one small memset, then one 16-byte copy and the
+// call's only wait.
+int ss_mst_duplicate_names_scratch(uint64_t n_rows, uint64_t* bytes_out) {
+  if (!bytes_out) return fail(SG_ERR_INVALID, "ss_mst_duplicate_names_scratch: null argument");
+  if (n_rows == 0 || n_rows >= (1ull << 32)) return refuse("ss_mst_duplicate_names_scratch", "bad size");
+  *bytes_out = mst_names_scratch_bytes(n_rows);
+  return SG_OK;
+}
+int ss_mst_duplicate_names_dev(const void* d_bytes, uint64_t len, uint64_t body_off, const void* d_name_spans, const void* d_order,
+                               uint64_t n_rows, void* d_shadowed, void* d_first, uint64_t cap, void* d_scratch, uint64_t* summary_out,
+                               void* stream) {
+  const std::string problem = mst_names_problem(d_bytes, len, body_off, d_name_spans, d_order, n_rows, d_shadowed, d_first, cap, d_scratch,
+                                                summary_out);
+  if (!problem.empty()) return refuse("ss_mst_duplicate_names", problem.c_str());
+  uint32_t* work = static_cast<uint32_t*>(d_scratch);
+  LOCKED_CTX();
+  hipStream_t s = pick_stream(stream);
+  CHECK_HIP(hipMemsetAsync(work, 0, 4 * MST_NAMES_FRONT_WORDS, s), "ss_mst_duplicate_names: work space");
+  CHECK_HIP(mst_names_launch(static_cast<const uint8_t*>(d_bytes) + body_off, len - body_off, static_cast<const uint32_t*>(d_name_spans),
+                             static_cast<const uint32_t*>(d_order), n_rows, static_cast<uint32_t*>(d_shadowed),
+                             static_cast<uint32_t*>(d_first), cap, work, s),
+            "ss_mst_duplicate_names");
+  uint32_t result[MST_NAMES_FRONT_WORDS];
+  TRY(download(reinterpret_cast<uint8_t*>(result), work, sizeof result, s));   // waits for the stream
+  summary_out[0] = result[MST_NAMES_AT_REPEATED];
+  summary_out[1] = result[MST_NAMES_AT_SHADOWED];
+  summary_out[2] = summary_out[1] < cap ? summary_out[1] : cap;
   return SG_OK;
 }
 // The range audit of a built tree (include/summa_snapshot.h; mst_audit.h has the rules and the work space, mst_audit.cuh the

@@ -240,9 +240,10 @@ __global__ void __launch_bounds__(MST_SORT_THREADS) mst_sort_gather_kernel(const
   }
 }
 
-// find, a query per thread
+// find, a query per thread; with an order the position found answers as the file row that stands there
 __global__ void __launch_bounds__(MST_SORT_THREADS) mst_find_names_kernel(const uint8_t* __restrict__ body, uint64_t body_len,
-                                                                         const uint32_t* __restrict__ name_spans, uint32_t n,
+                                                                         const uint32_t* __restrict__ name_spans,
+                                                                         const uint32_t* __restrict__ order, uint32_t n,
                                                                          const uint8_t* __restrict__ query,
                                                                          const uint64_t* __restrict__ query_off, uint64_t m,
                                                                          uint32_t* __restrict__ out) {
@@ -250,7 +251,8 @@ __global__ void __launch_bounds__(MST_SORT_THREADS) mst_find_names_kernel(const 
   const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= m) return;
   const uint64_t lo = query_off[j], hi = query_off[j + 1];
-  out[j] = mst_find_name(body, body_len, name_spans, n, query + lo, hi - lo);
+  const uint32_t at = mst_find_name(body, body_len, name_spans, n, query + lo, hi - lo);
+  out[j] = order && at != MST_FIND_ABSENT ? order[at] : at;   // at < n where it is not MST_FIND_ABSENT
 }
 
 static unsigned blocks_for(uint64_t threads) { return (unsigned)((threads + MST_SORT_THREADS - 1) / MST_SORT_THREADS); }
@@ -282,9 +284,11 @@ hipError_t mst_sort_launch(const uint8_t* d_body, const uint64_t* d_words, uint6
   return hipGetLastError();
 }
 
-hipError_t mst_find_names_launch(const uint8_t* d_body, uint64_t body_len, const uint32_t* d_name_spans, uint32_t n_rows,
-                                 const uint8_t* d_query, const uint64_t* d_query_off, size_t m, uint32_t* d_out, hipStream_t stream) {
-  mst_find_names_kernel<<<blocks_for(m), MST_SORT_THREADS, 0, stream>>>(d_body, body_len, d_name_spans, n_rows, d_query, d_query_off, m, d_out);
+hipError_t mst_find_names_launch(const uint8_t* d_body, uint64_t body_len, const uint32_t* d_name_spans, const uint32_t* d_order,
+                                 uint32_t n_rows, const uint8_t* d_query, const uint64_t* d_query_off, size_t m, uint32_t* d_out,
+                                 hipStream_t stream) {
+  mst_find_names_kernel<<<blocks_for(m), MST_SORT_THREADS, 0, stream>>>(d_body, body_len, d_name_spans, d_order, n_rows, d_query, d_query_off,
+                                                                        m, d_out);
   return hipGetLastError();
 }
 

@@ -176,9 +176,11 @@ hipError_t mst_sort_lengths_launch(const uint64_t* d_words, uint64_t n_rows, uin
 // d_sorted_words, laid out as d_words is (its row starts stay unwritten)
 hipError_t mst_sort_launch(const uint8_t* d_body, const uint64_t* d_words, uint64_t n_rows, uint32_t nc, uint32_t longest,
                            uint32_t* d_work, uint32_t* d_order, uint32_t* d_name_spans, uint64_t* d_sorted_words, hipStream_t stream);
-// out[j] = mst_find_name of query j = d_query[d_query_off[j] .. d_query_off[j + 1])
-hipError_t mst_find_names_launch(const uint8_t* d_body, uint64_t body_len, const uint32_t* d_name_spans, uint32_t n_rows,
-                                 const uint8_t* d_query, const uint64_t* d_query_off, size_t m, uint32_t* d_out, hipStream_t stream);
+// out[j] = mst_find_name of query j = d_query[d_query_off[j] .. d_query_off[j + 1]); with d_order (n_rows u32, else nullptr) the
+// position found goes through it: out[j] = d_order[position]
+hipError_t mst_find_names_launch(const uint8_t* d_body, uint64_t body_len, const uint32_t* d_name_spans, const uint32_t* d_order,
+                                 uint32_t n_rows, const uint8_t* d_query, const uint64_t* d_query_off, size_t m, uint32_t* d_out,
+                                 hipStream_t stream);
 #endif
 
 }  // namespace sg

@@ -193,9 +193,10 @@ def verifier_lib():
     return L
 
 
-# C ABI of the sorted snapshot and the range audit (include/summa_snapshot.h), exported by the same library; errors go through
-# sg_last_error
+# C ABI of the sorted snapshot, the names beside a tree in file order and the range audit (include/summa_snapshot.h), exported by the
+# same library; errors go through sg_last_error
 SNAPSHOT_EXPORTS = ["ss_mst_sort_geometry", "ss_mst_sort_scratch", "ss_mst_csv_entries_sorted_dev", "ss_mst_find_names",
+                    "ss_mst_csv_name_index_dev", "ss_mst_find_leaves", "ss_mst_duplicate_names_scratch", "ss_mst_duplicate_names_dev",
                     "ss_mst_range_audit_scratch", "ss_mst_range_audit_dev"]
 SNAPSHOT_ARGTYPES = {
     "ss_mst_sort_geometry": [C.c_void_p, C.c_void_p],
@@ -204,6 +205,13 @@ SNAPSHOT_ARGTYPES = {
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "ss_mst_find_names": [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                           C.c_void_p],
+    "ss_mst_csv_name_index_dev": [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "ss_mst_find_leaves": [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t,
+                           C.c_void_p, C.c_void_p],
+    "ss_mst_duplicate_names_scratch": [C.c_uint64, C.c_void_p],
+    "ss_mst_duplicate_names_dev": [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                   C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p],
     "ss_mst_range_audit_scratch": [C.c_uint32, C.c_void_p],
     "ss_mst_range_audit_dev": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                C.c_void_p, C.c_void_p],

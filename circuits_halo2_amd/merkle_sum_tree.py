@@ -9,6 +9,8 @@ become field elements on the device (sg_mst_entries_dev) and the tree stays in H
 header line here and reads the rest of the file on the device too (sg_mst_csv_scan_dev / sg_mst_csv_entries_dev), unless the
 file is outside the device reader's subset of CSV text; DeviceMerkleSumTree.from_csv_sorted does the same and sorts the names
 there as well (ss_mst_csv_entries_sorted_dev), and such a tree finds a user by name on the device (ss_mst_find_names);
+DeviceMerkleSumTree.from_csv(name_index=True) sorts the names beside leaves that stay in file order (ss_mst_csv_name_index_dev,
+ss_mst_find_leaves), and `duplicate_names` reports the usernames that occur more than once (ss_mst_duplicate_names_dev);
 DeviceMerkleSumTree.update_leaf /
 update_leaves / update_leaves_at change balances there in place (sg_mst_update_dev).
 """
@@ -173,6 +175,34 @@ def _build_nodes(d_users, d_bals, depth: int, n_currencies: int):
     return d_h, d_b
 
 
+class DuplicateNames:
+    """What `duplicate_names` found: the usernames that occur more than once in the snapshot.  The reference accepts such a file
+    silently (mst.rs:103-134) and `index_of_username` finds the first row of a name only (mst.rs:207-223), so every later row
+    of that name is *shadowed*: a leaf that no lookup, `update_leaf` or `prove_batch` by name can reach, whose balances still sit
+    in the committed sums.
+      n_repeated_names   names that occur more than once
+      n_shadowed         shadowed leaves: the rows of those names but each one's first
+      shadowed           numpy.uint32: the shadowed leaves ordered by the names' bytes and, within a name, by file row (with a
+                         `cap`, the first `cap` of them)
+      first              numpy.uint32: beside each listed leaf the one that a lookup of its name finds
+      ok                 no name occurs twice"""
+
+    def __init__(self, n_repeated_names, n_shadowed, shadowed, first):
+        self.n_repeated_names, self.n_shadowed = int(n_repeated_names), int(n_shadowed)
+        self.shadowed, self.first = np.asarray(shadowed, dtype=np.uint32), np.asarray(first, dtype=np.uint32)
+
+    @property
+    def ok(self) -> bool:
+        return self.n_shadowed == 0
+
+    def groups(self):
+        """{first leaf: [its shadowed leaves]} of the listed leaves, in the list's order"""
+        out = {}
+        for leaf, head in zip(self.shadowed.tolist(), self.first.tolist()):
+            out.setdefault(head, []).append(leaf)
+        return out
+
+
 class _Tree:
     """What MerkleSumTree and DeviceMerkleSumTree share: everything that needs only `depth`, `n_currencies`, `entries` (None
     where a tree holds none), `is_sorted` and the class's `from_entries`."""
@@ -227,6 +257,36 @@ class _Tree:
             if name == username:
                 return i
         raise KeyError("Username not found")
+
+    def duplicate_names(self, cap=None) -> DuplicateNames:
+        """The usernames that occur more than once, from `entries` on the host: the leaves in the stable order of their names'
+        bytes, where a repeated name is a run and every leaf of a run but its first is shadowed.  cap: list at most that many
+        shadowed leaves (None: all).  Zero entries (the padding) carry no name and are not counted."""
+        if cap is not None and cap < 0:
+            raise ValueError("cap below 0")
+        if self.entries is None:
+            raise ValueError("a tree built from field elements holds no entries")
+        names = [(e[0].encode(), i) for i, e in enumerate(self.entries) if isinstance(e[0], str)]
+        names.sort(key=lambda pair: pair[0])                  # stable: equal names keep the leaves' order
+        shadowed, first, repeated = [], [], 0
+        for at in range(1, len(names)):
+            if names[at][0] != names[at - 1][0]:
+                continue
+            if not shadowed or shadowed[-1] != names[at - 1][1]:
+                repeated += 1
+                head = names[at - 1][1]
+            shadowed.append(names[at][1])
+            first.append(head)
+        listed = len(shadowed) if cap is None else min(int(cap), len(shadowed))
+        return DuplicateNames(repeated, len(shadowed), shadowed[:listed], first[:listed])
+
+    def _name_of_leaf(self, index: int):
+        return self.entries[index][0]
+
+    def named_groups(self, dups: DuplicateNames, limit: int = 16):
+        """[(username, [its leaves: the one a lookup finds, then the shadowed ones])] for the first `limit` repeated names of
+        `dups`' list"""
+        return [(self._name_of_leaf(head), [head] + leaves) for head, leaves in list(dups.groups().items())[:limit]]
 
     def _path(self, index: int):
         """tree.rs:85-137's walk from leaf `index` up to below the root: for every level (path bit, the sibling's number in
@@ -541,6 +601,16 @@ class DeviceMerkleSumTree(_Tree):
     entries are unparsed, answers by name from there (ss_mst_find_names: one binary search per name over the text):
     `index_of_username`, `indices_of_usernames`, `update_leaf` / `update_leaves` and the `entry` of `generate_proof` do not parse
     the file.  `entries` still does, once, and puts the rows in leaf order through `d_order`.
+    `from_csv(..., name_index=True)` gives a tree in FILE order -- the only order whose root equals a commitment made from the
+    same file by the reference -- the same ability: the names are sorted beside the leaves, which stay where they are
+    (ss_mst_csv_name_index_dev), the tree keeps the text, `d_order`, the sorted names' spans and the names' spans in file order
+    (the file's size plus 20 bytes a row), and the same lookups go through ss_mst_find_leaves, a repeated name to its first row
+    in file order as mst.rs:207-223 finds it.  `has_name_index` says whether a tree holds such an order, `name_index_reason` why
+    one that was asked for is missing.
+
+    `duplicate_names` reports the usernames that occur more than once -- the reference accepts such a file silently, and every
+    row of a name behind its first is a leaf no lookup, update or proof by name can reach -- from the sorted order in HBM where
+    the tree holds one (ss_mst_duplicate_names_dev, no parse), else from `entries`; `named_groups` reads the names.
 
     `update_leaf`, `update_leaves` and `update_leaves_at` change balances in place (sg_mst_update_dev): the leaves and the nodes
     above them are re-hashed on the device, in the arrays the tree was built from (`d_balances` of the plain constructor is
@@ -557,6 +627,8 @@ class DeviceMerkleSumTree(_Tree):
     csv_fallback_reason = None    # ... and why the host read it
     _csv_lazy = None          # a device-read tree whose entries nobody has asked for: (path, {leaf index: balances set since})
     _sorted_dev = None        # a device-sorted tree: {"text", "size", "body_off", "delim", "n", "d_order", "d_name_spans"}
+    _index_dev = None         # from_csv(name_index=True): the same record beside leaves in file order, plus "d_leaf_name_spans"
+    name_index_reason = None  # from_csv(name_index=True) without an index: why
 
     @property
     def entries(self):
@@ -576,6 +648,14 @@ class DeviceMerkleSumTree(_Tree):
     @entries.setter
     def entries(self, value):
         self._entries, self._csv_lazy = value, None
+
+    @property
+    def has_name_index(self) -> bool:
+        """the names' sorted order lies in HBM beside the tree: `from_csv_sorted` on the device, or `from_csv(name_index=True)`"""
+        return self._names_dev() is not None
+
+    def _names_dev(self):
+        return self._sorted_dev if self._sorted_dev is not None else self._index_dev
 
     def __init__(self, d_usernames, d_balances, depth: int, n_currencies: int):
         import torch
@@ -619,16 +699,22 @@ class DeviceMerkleSumTree(_Tree):
         return tree
 
     @classmethod
-    def from_csv(cls, path: str, n_currencies: int, n_bytes: int = 8):
+    def from_csv(cls, path: str, n_currencies: int, n_bytes: int = 8, name_index: bool = False):
         """mst.rs:74-87 with the file's text read where the tree is built (sg_mst_csv_scan_dev, sg_mst_csv_entries_dev): the
         host parses the header line alone, the device finds the rows and fields and hashes and folds them in place.  The
         device takes a strict subset of CSV text (include/summa_gpu.h) and judges no data: any other file goes the way every
         file went before, parse_csv_to_entries and from_entries, which accepts or refuses it.  `csv_ingest` says which way
-        it was, `csv_fallback_reason` why the host's.  After the device's `entries` is made on first use, from the file."""
-        tree, reason = cls._from_csv_on_device(path, n_currencies)
+        it was, `csv_fallback_reason` why the host's.  After the device's `entries` is made on first use, from the file.
+        name_index: also sort the names on the device beside the leaves, which stay in file order (ss_mst_csv_name_index_dev),
+        and keep the text and the index in HBM -- the file's size plus 20 bytes a row -- so that the tree answers by name and
+        reports repeated names without parsing the file.  `has_name_index` says whether it does, `name_index_reason` why not:
+        a name of more than 64 bytes (the tree is device-read all the same), or the host's reason for reading the file."""
+        tree, reason = cls._from_csv_on_device(path, n_currencies, name_index=name_index)
         if tree is None:
             tree = super().from_csv(path, n_currencies, n_bytes)
             tree.csv_ingest, tree.csv_fallback_reason = "host", reason
+            if name_index:
+                tree.name_index_reason = reason
         return tree
 
     @classmethod
@@ -645,9 +731,9 @@ class DeviceMerkleSumTree(_Tree):
         return tree
 
     @classmethod
-    def _from_csv_on_device(cls, path: str, n_currencies: int, sorted_leaves: bool = False):
+    def _from_csv_on_device(cls, path: str, n_currencies: int, sorted_leaves: bool = False, name_index: bool = False):
         """-> (tree, None), or (None, why the device does not take this file); sorted_leaves: the leaves in the order of the
-        names' bytes"""
+        names' bytes; name_index: the leaves in file order and the names' sorted order beside them"""
         import torch
         if not 1 <= n_currencies <= 64:
             return None, "n_currencies outside 1..64"
@@ -703,12 +789,33 @@ class DeviceMerkleSumTree(_Tree):
                                                       ffi.dev_ptr(d_name_spans), ffi.dev_ptr(d_users), ffi.dev_ptr(d_bals),
                                                       C.byref(problem), stream))
         else:
-            d_spans = torch.empty(n + 2 + 2 * n * (1 + n_currencies), dtype=torch.int64, device="cuda")
+            # with the index the two blocks of the sorted call: the entries call uses the first, the index call both
+            span_words = 2 * (n + 1 + 2 * n * (1 + n_currencies)) if name_index else n + 2 + 2 * n * (1 + n_currencies)
+            d_spans = torch.empty(span_words, dtype=torch.int64, device="cuda")
             ffi.check(L.sg_mst_csv_entries_dev(ffi.dev_ptr(d_text), size, body_off, ffi.dev_ptr(d_tiles), ord(delim), n_currencies, n, rows,
                                                ffi.dev_ptr(d_spans), ffi.dev_ptr(d_users), ffi.dev_ptr(d_bals), C.byref(problem), stream))
         if problem.value:
             return None, f"row {problem.value >> 8}: {_CSV_ROW_PROBLEMS.get(problem.value & 0xff, 'outside the subset')}"
+        index, index_reason = None, None
+        if name_index and not sorted_leaves:
+            S = ffi.snapshot_lib()
+            sort_bytes = C.c_uint64(0)
+            ffi.check(S.ss_mst_sort_scratch(n, C.byref(sort_bytes)))
+            d_sort = torch.empty(sort_bytes.value, dtype=torch.uint8, device="cuda")
+            d_order = torch.empty(n, dtype=torch.int32, device="cuda")
+            d_name_spans = torch.empty(2 * n, dtype=torch.int32, device="cuda")
+            d_leaf_name_spans = torch.empty(2 * n, dtype=torch.int32, device="cuda")
+            ffi.check(S.ss_mst_csv_name_index_dev(ffi.dev_ptr(d_text), size, body_off, ffi.dev_ptr(d_tiles), ord(delim), n_currencies, n,
+                                                  ffi.dev_ptr(d_spans), ffi.dev_ptr(d_sort), ffi.dev_ptr(d_order), ffi.dev_ptr(d_name_spans),
+                                                  ffi.dev_ptr(d_leaf_name_spans), C.byref(problem), stream))
+            if problem.value:                                 # in practice a name over 64 bytes: the tree is device-read all the same
+                index_reason = f"row {problem.value >> 8}: {_CSV_ROW_PROBLEMS.get(problem.value & 0xff, 'outside the subset')}"
+            else:
+                index = {"text": d_text, "size": size, "body_off": body_off, "delim": delim, "n": n, "d_order": d_order,
+                         "d_name_spans": d_name_spans, "d_leaf_name_spans": d_leaf_name_spans}
         tree = cls(d_users, d_bals, depth, n_currencies)       # same stream; synchronized when it returns
+        if name_index and not sorted_leaves:
+            tree._index_dev, tree.name_index_reason = index, index_reason
         if sorted_leaves:
             tree.is_sorted = True
             tree._sorted_dev = {"text": d_text, "size": size, "body_off": body_off, "delim": delim, "n": n, "d_order": d_order,
@@ -719,18 +826,21 @@ class DeviceMerkleSumTree(_Tree):
         return tree, None
 
     def _finds_on_device(self) -> bool:
-        """a device-sorted tree whose entries are still unparsed: names are looked up in the text in HBM"""
-        return self._entries is None and self._csv_lazy is not None and self._sorted_dev is not None
+        """a device-read tree that holds the names' sorted order and whose entries are still unparsed: names are looked up in the
+        text in HBM"""
+        return self._entries is None and self._csv_lazy is not None and self._names_dev() is not None
 
     def index_of_username(self, username: str) -> int:
-        """mst.rs:207-223; on a device-sorted tree whose entries are unparsed a binary search on the device, no parse"""
+        """mst.rs:207-223; on a tree with the names' order in HBM whose entries are unparsed a binary search on the device, no
+        parse"""
         if self._finds_on_device():
             return self.indices_of_usernames([username])[0]
         return super().index_of_username(username)
 
     def indices_of_usernames(self, usernames):
-        """`index_of_username` of every name, a repeated name's first leaf: one device call (ss_mst_find_names) on a
-        device-sorted tree whose entries are unparsed.  KeyError("Username not found") if any name is missing."""
+        """`index_of_username` of every name, a repeated name's first leaf: one device call on a tree with the names' order in HBM
+        whose entries are unparsed (ss_mst_find_names on a device-sorted tree; ss_mst_find_leaves, which answers through `d_order`,
+        on one in file order).  KeyError("Username not found") if any name is missing."""
         usernames = list(usernames)
         if not self._finds_on_device():
             return [self.index_of_username(name) for name in usernames]
@@ -741,20 +851,27 @@ class DeviceMerkleSumTree(_Tree):
         np.cumsum(np.fromiter(map(len, names), dtype=np.uint64, count=len(names)), out=name_off[1:])
         name_bytes = np.frombuffer(b"".join(names) or b"\0", dtype=np.uint8)       # only empty names: a buffer to point at all the same
         found = np.zeros(len(names), dtype=np.uint32)
-        d = self._sorted_dev
-        ffi.check(ffi.snapshot_lib().ss_mst_find_names(ffi.dev_ptr(d["text"]), d["size"], d["body_off"], ffi.dev_ptr(d["d_name_spans"]),
-                                                       d["n"], ffi.ptr(name_bytes), ffi.ptr(name_off), len(names), ffi.ptr(found),
-                                                       ffi.current_stream_ptr()))
+        d = self._names_dev()
+        if self._sorted_dev is not None:
+            ffi.check(ffi.snapshot_lib().ss_mst_find_names(ffi.dev_ptr(d["text"]), d["size"], d["body_off"], ffi.dev_ptr(d["d_name_spans"]),
+                                                           d["n"], ffi.ptr(name_bytes), ffi.ptr(name_off), len(names), ffi.ptr(found),
+                                                           ffi.current_stream_ptr()))
+        else:
+            ffi.check(ffi.snapshot_lib().ss_mst_find_leaves(ffi.dev_ptr(d["text"]), d["size"], d["body_off"], ffi.dev_ptr(d["d_name_spans"]),
+                                                            ffi.dev_ptr(d["d_order"]), d["n"], ffi.ptr(name_bytes), ffi.ptr(name_off),
+                                                            len(names), ffi.ptr(found), ffi.current_stream_ptr()))
         if (found == _ABSENT).any():
             raise KeyError("Username not found")
         return [int(i) for i in found]
 
     def _entry_from_text(self, index: int):
-        """entry `index` of a device-sorted tree whose entries are unparsed, from the row's text in HBM: two small copies"""
-        nc, d = self.n_currencies, self._sorted_dev
+        """entry `index` of a tree with the names' order in HBM whose entries are unparsed, from the row's text there: two small
+        copies.  The leaf's name span is the sorted one on a device-sorted tree, `d_leaf_name_spans` on one in file order."""
+        nc, d = self.n_currencies, self._names_dev()
         if index >= d["n"]:
             return (None, [0] * nc)
-        begin, end = (int(x) & 0xFFFFFFFF for x in d["d_name_spans"][2 * index:2 * index + 2].cpu().tolist())
+        leaf_spans = d.get("d_leaf_name_spans", d["d_name_spans"])
+        begin, end = (int(x) & 0xFFFFFFFF for x in leaf_spans[2 * index:2 * index + 2].cpu().tolist())
         lo, text = d["body_off"] + begin, b""
         want = end - begin + 1 + 24 * nc
         while b"\n" not in text[end - begin:] and lo + len(text) < d["size"]:       # the row ends at its line end or the file's
@@ -850,6 +967,37 @@ class DeviceMerkleSumTree(_Tree):
         listed = int(summary[2])
         bad = d_bad[:listed].cpu().numpy().view(np.uint32) if listed else np.zeros(0, dtype=np.uint32)
         return RangeAudit(n_bytes, summary[0], summary[1], bad, int(summary[3]), d_flags, d_reasons)
+
+    def duplicate_names(self, cap=None) -> DuplicateNames:
+        """The usernames that occur more than once.  A tree with the names' order in HBM (`has_name_index`) answers from there in
+        one device call (ss_mst_duplicate_names_dev) on the current stream, one small copy for the summary and one for each list,
+        and parses nothing; any other tree answers from `entries` on the host.  cap: list at most that many shadowed leaves
+        (None: all).  Updates never change names, so the report holds for the life of the tree."""
+        import torch
+        d = self._names_dev()
+        if d is None:
+            return super().duplicate_names(cap)
+        if cap is not None and cap < 0:
+            raise ValueError("cap below 0")
+        S = ffi.snapshot_lib()
+        n = d["n"]
+        list_cap = n if cap is None else min(int(cap), n)
+        scratch_bytes = C.c_uint64(0)
+        ffi.check(S.ss_mst_duplicate_names_scratch(n, C.byref(scratch_bytes)))
+        d_scratch = torch.empty(scratch_bytes.value // 4, dtype=torch.int32, device="cuda")
+        d_shadowed = torch.empty(list_cap, dtype=torch.int32, device="cuda") if list_cap else None
+        d_first = torch.empty(list_cap, dtype=torch.int32, device="cuda") if list_cap else None
+        summary = (C.c_uint64 * 3)()
+        ffi.check(S.ss_mst_duplicate_names_dev(ffi.dev_ptr(d["text"]), d["size"], d["body_off"], ffi.dev_ptr(d["d_name_spans"]),
+                                               None if self._sorted_dev is not None else ffi.dev_ptr(d["d_order"]), n,
+                                               ffi.dev_ptr(d_shadowed) if list_cap else None, ffi.dev_ptr(d_first) if list_cap else None,
+                                               list_cap, ffi.dev_ptr(d_scratch), summary, ffi.current_stream_ptr()))
+        listed = int(summary[2])
+        take = lambda t: t[:listed].cpu().numpy().view(np.uint32) if listed else np.zeros(0, dtype=np.uint32)
+        return DuplicateNames(summary[0], summary[1], take(d_shadowed), take(d_first))
+
+    def _name_of_leaf(self, index: int):
+        return self._entry_from_text(index)[0] if self._finds_on_device() else self.entries[index][0]
 
     def explain_unprovable(self, audit: RangeAudit, index: int):
         """What is wrong with user `index`: [(what, level, node, currency, value)] for every balance >= 2^(8 audit.n_bytes) that the
