@@ -228,6 +228,29 @@ def snapshot_lib():
     return L
 
 
+# C ABI of one round's snapshot against the next: the diff of a new file with a tree in HBM and the apply of its changed balances
+# (include/summa_rounds.h), exported by the same library; errors go through sg_last_error
+ROUNDS_EXPORTS = ["sr_mst_diff_scratch", "sr_mst_csv_diff_dev", "sr_mst_apply_diff_dev"]
+ROUNDS_ARGTYPES = {
+    "sr_mst_diff_scratch": [C.c_uint64, C.c_uint32, C.c_void_p],
+    "sr_mst_csv_diff_dev": [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p,
+                            C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
+                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                            C.c_void_p, C.c_void_p, C.c_void_p],
+    "sr_mst_apply_diff_dev": [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
+                              C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+}
+
+
+def rounds_lib():
+    L = lib()
+    if not getattr(L, "_sr_ready", False):
+        for name in ROUNDS_EXPORTS:
+            getattr(L, name).argtypes = ROUNDS_ARGTYPES[name]
+        L._sr_ready = True
+    return L
+
+
 def check_prover(rc: int):
     if rc != SG_OK:
         raise SummaGpuError(rc, prover_lib().sp_last_error().decode())

@@ -203,6 +203,63 @@ class DuplicateNames:
         return out
 
 
+class SnapshotDiff:
+    """What `diff_csv` / `diff_entries` found: the next round's file B joined by username with the tree T as it was
+    (include/summa_rounds.h has the rules).  A row of B is looked up as `index_of_username` looks a name up, so it finds the first
+    leaf of its name; of several rows that find one leaf the first in file order owns it.  Balances compare as field elements: 007
+    equals 7, and an integer >= r equals its residue.
+      n_new, n_shadowed_rows, n_changed, n_same   the rows of B: not found in T; behind another row of the same name; the owner of a
+                         leaf with a balance that differs; the owner of a leaf with none
+      n_gone             named leaves of T that no row of B found
+      n_unreachable      leaves of T behind another of the same name (`duplicate_names`): no row can own them, they are neither
+                         changed nor gone
+      changed            numpy.uint32: the changed leaves in increasing order, all of them
+      new_rows, gone     numpy.uint32: the new rows of B and the gone leaves of T in increasing order (with a `cap`, the first `cap`)
+      ok                 nobody changed, nobody is new, nobody is gone
+      ingest, fallback_reason   "device" (both texts were joined in HBM, sr_mst_csv_diff_dev) or "host" (from `entries`), and why
+      row_leaf(), row_state(), leaf_state(), owner()   the arrays as numpy (on the device way they stay in HBM until asked for): per
+                         row its leaf or 0xFFFFFFFF and its state (ROW_*), per leaf of all 2^depth its state (LEAF_*) and owner row
+    A diff is of the tree as it was: `apply_diff` refuses it after another update.  New users are not inserted and gone users are
+    not zeroed by an apply -- a leaf's username is fixed in a built tree --, so n_new or n_gone above 0 says that a rebuild is due."""
+
+    LEAF_PADDING, LEAF_SAME, LEAF_CHANGED, LEAF_GONE, LEAF_UNREACHABLE = 0, 1, 2, 3, 4
+    ROW_SAME, ROW_CHANGED, ROW_NEW, ROW_SHADOWED = 1, 2, 3, 4
+    ABSENT = 0xFFFFFFFF
+
+    def __init__(self, counts, changed, new_rows, gone, arrays, ingest, fallback_reason=None, new_balances=None, dev=None):
+        (self.n_new, self.n_shadowed_rows, self.n_changed, self.n_same, self.n_gone, self.n_unreachable) = (int(x) for x in counts)
+        self.changed, self.new_rows, self.gone = (np.asarray(a, dtype=np.uint32) for a in (changed, new_rows, gone))
+        self._arrays = arrays                  # {"row_leaf", "row_state", "leaf_state", "owner"}: numpy arrays or device tensors
+        self.ingest, self.fallback_reason = ingest, fallback_reason
+        self.new_balances = new_balances       # the host way: the owner row's balances for every changed leaf, in the list's order
+        self._dev = dev                        # the device way: what sr_mst_apply_diff_dev takes
+        self._tree, self._epoch = None, None
+
+    @property
+    def ok(self) -> bool:
+        return self.n_new == self.n_changed == self.n_gone == 0
+
+    def summary(self):
+        return {"new": self.n_new, "shadowed": self.n_shadowed_rows, "changed": self.n_changed, "same": self.n_same, "gone": self.n_gone,
+                "unreachable": self.n_unreachable, "new_listed": len(self.new_rows), "gone_listed": len(self.gone)}
+
+    def _array(self, key, dtype):
+        a = self._arrays[key]
+        return (a if isinstance(a, np.ndarray) else a.cpu().numpy()).view(dtype)
+
+    def row_leaf(self) -> np.ndarray:
+        return self._array("row_leaf", np.uint32)
+
+    def row_state(self) -> np.ndarray:
+        return self._array("row_state", np.uint8)
+
+    def leaf_state(self) -> np.ndarray:
+        return self._array("leaf_state", np.uint8)
+
+    def owner(self) -> np.ndarray:
+        return self._array("owner", np.uint32)
+
+
 class _Tree:
     """What MerkleSumTree and DeviceMerkleSumTree share: everything that needs only `depth`, `n_currencies`, `entries` (None
     where a tree holds none), `is_sorted` and the class's `from_entries`."""
@@ -279,6 +336,60 @@ class _Tree:
             first.append(head)
         listed = len(shadowed) if cap is None else min(int(cap), len(shadowed))
         return DuplicateNames(repeated, len(shadowed), shadowed[:listed], first[:listed])
+
+    _updates = 0              # how many times the balances changed: a diff is of the tree as it was
+
+    def diff_entries(self, entries, cap=None) -> SnapshotDiff:
+        """The next round's entries [(username, [balances])] against this tree, from `entries` on the host (SnapshotDiff has the
+        rules).  cap: list at most that many new rows and gone leaves (None: all)."""
+        if cap is not None and cap < 0:
+            raise ValueError("cap below 0")
+        if self.entries is None:
+            raise ValueError("a tree built from field elements holds no entries")
+        entries = list(entries)
+        _check_balance_rows([bal for _, bal in entries], self.n_currencies, "wrong number of balances")
+        D = SnapshotDiff
+        first = {}
+        for leaf, (name, _) in enumerate(self.entries):
+            if isinstance(name, str):
+                first.setdefault(name, leaf)
+        leaves = 1 << self.depth
+        row_leaf = np.array([first.get(name, D.ABSENT) for name, _ in entries], dtype=np.uint32)
+        owner = np.full(leaves, D.ABSENT, dtype=np.uint32)
+        for row in range(len(entries) - 1, -1, -1):           # the lowest row is written last
+            if row_leaf[row] != D.ABSENT:
+                owner[row_leaf[row]] = row
+        row_state = np.full(len(entries), D.ROW_NEW, dtype=np.uint8)
+        leaf_state = np.full(leaves, D.LEAF_PADDING, dtype=np.uint8)
+        for row, leaf in enumerate(row_leaf.tolist()):
+            if leaf == D.ABSENT:
+                continue
+            if owner[leaf] != row:
+                row_state[row] = D.ROW_SHADOWED
+                continue
+            same = [v % R_MODULUS for v in entries[row][1]] == [v % R_MODULUS for v in self.entries[leaf][1]]
+            row_state[row], leaf_state[leaf] = (D.ROW_SAME, D.LEAF_SAME) if same else (D.ROW_CHANGED, D.LEAF_CHANGED)
+        for leaf, (name, _) in enumerate(self.entries):
+            if isinstance(name, str):
+                if first[name] != leaf:
+                    leaf_state[leaf] = D.LEAF_UNREACHABLE
+                elif owner[leaf] == D.ABSENT:
+                    leaf_state[leaf] = D.LEAF_GONE
+        changed, gone = np.flatnonzero(leaf_state == D.LEAF_CHANGED), np.flatnonzero(leaf_state == D.LEAF_GONE)
+        new_rows = np.flatnonzero(row_state == D.ROW_NEW)
+        counts = [new_rows.size, int((row_state == D.ROW_SHADOWED).sum()), changed.size, int((row_state == D.ROW_SAME).sum()), gone.size,
+                  int((leaf_state == D.LEAF_UNREACHABLE).sum())]
+        listed = None if cap is None else int(cap)
+        diff = SnapshotDiff(counts, changed, new_rows[:listed], gone[:listed],
+                            {"row_leaf": row_leaf, "row_state": row_state, "leaf_state": leaf_state, "owner": owner}, "host",
+                            new_balances=[list(entries[owner[leaf]][1]) for leaf in changed.tolist()])
+        diff._tree, diff._epoch = self, self._updates
+        return diff
+
+    def diff_csv(self, path: str, cap=None) -> SnapshotDiff:
+        """`diff_entries` of the next round's CSV, parsed on the host"""
+        entries, _ = parse_csv_to_entries(path, self.n_currencies)
+        return self.diff_entries(entries, cap)
 
     def _name_of_leaf(self, index: int):
         return self.entries[index][0]
@@ -424,6 +535,7 @@ class MerkleSumTree(_Tree):
         _check_balance_rows([new_balances], nc, "wrong number of balances")
         index = self.index_of_username(username)
         self.entries[index] = (username, list(new_balances))
+        self._updates += 1
         u, b = self._entry_fields(username, new_balances)
         ub, bb = np.frombuffer(u, dtype=np.uint8), np.frombuffer(b, dtype=np.uint8)
         self._set_node(0, index, _hash_batch("leaf", ub, bb, n=1, nc=nc), bb)
@@ -616,6 +728,11 @@ class DeviceMerkleSumTree(_Tree):
     above them are re-hashed on the device, in the arrays the tree was built from (`d_balances` of the plain constructor is
     written too), and nothing comes back but the root when it is next asked for.
 
+    `diff_csv` joins the NEXT round's CSV with the tree by username -- who changed, who is new, who is gone (SnapshotDiff) --, where
+    both texts lie when the tree holds the names' order (sr_mst_csv_diff_dev), else from `entries`; `apply_diff` writes the changed
+    balances in place without moving a leaf (sr_mst_apply_diff_dev: the balances are folded from the file's text in HBM and never
+    visit the host), `apply_csv` does both.  The tree counts its updates, and a diff taken before another update is refused.
+
     `range_audit` says which users of the snapshot can receive a valid inclusion proof at all -- whose circuit would fail a range
     check, and at which one -- from the node balances in HBM (ss_mst_range_audit_dev); `explain_unprovable` names the balances."""
 
@@ -627,6 +744,7 @@ class DeviceMerkleSumTree(_Tree):
     csv_fallback_reason = None    # ... and why the host read it
     _csv_lazy = None          # a device-read tree whose entries nobody has asked for: (path, {leaf index: balances set since})
     _sorted_dev = None        # a device-sorted tree: {"text", "size", "body_off", "delim", "n", "d_order", "d_name_spans"}
+    _applied = ()             # the changed leaves of every device diff applied while the entries were unparsed
     _index_dev = None         # from_csv(name_index=True): the same record beside leaves in file order, plus "d_leaf_name_spans"
     name_index_reason = None  # from_csv(name_index=True) without an index: why
 
@@ -640,6 +758,11 @@ class DeviceMerkleSumTree(_Tree):
             if self._sorted_dev is not None:                  # the device's order: one copy and no host sort
                 parsed = [parsed[i] for i in self._sorted_dev["d_order"].cpu().tolist()]
             parsed += [(None, [0] * self.n_currencies)] * ((1 << self.depth) - len(parsed))
+            if self._applied:                                 # leaves an applied diff changed: their balances are d_bals'
+                leaves = np.unique(np.concatenate(self._applied))
+                for i, bal in zip(leaves.tolist(), self._balances_of_leaves(leaves)):
+                    parsed[i] = (parsed[i][0], bal)
+                self._applied = ()
             for i, bal in changed.items():
                 parsed[i] = (parsed[i][0], bal)
             self._entries, self._csv_lazy = parsed, None
@@ -735,42 +858,12 @@ class DeviceMerkleSumTree(_Tree):
         """-> (tree, None), or (None, why the device does not take this file); sorted_leaves: the leaves in the order of the
         names' bytes; name_index: the leaves in file order and the names' sorted order beside them"""
         import torch
-        if not 1 <= n_currencies <= 64:
-            return None, "n_currencies outside 1..64"
-        data = np.fromfile(path, dtype=np.uint8)
-        line, eol, _ = data[:1 << 16].tobytes().partition(b"\n")
-        if not eol:
-            return None, "no line end in the first 64 KiB"
-        body_off, size = len(line) + 1, int(data.size)
-        line = line[:-1] if line.endswith(b"\r") else line
-        if not line.isascii() or any(c in line for c in b'"\r\0'):
-            return None, "header line: a quote, carriage return, NUL or non-ASCII byte"
-        delim = ";" if b";" in line else ","
-        header = line.decode().split(delim)
-        crypto = [tuple(h.split("_")[1:]) for h in header[1:]]
-        if (len(header) - 1 != n_currencies or header[0] != "username"
-                or any(len(h.split("_")) != 3 or h.split("_")[0] != "balance" for h in header[1:])):
-            return None, "header line: not username and n_currencies balance_<name>_<chain> columns"
-        if body_off == size:
-            return None, "no rows"
-        if size - body_off >= 1 << 32:
-            return None, "a body of 4 GiB or more"
+        scanned, reason = cls._csv_text_on_device(path, n_currencies)
+        if scanned is None:
+            return None, reason
+        d_text, size, body_off, delim, crypto, d_tiles, n = scanned
         L = ffi.lib()
-        tile, cap = C.c_uint32(0), C.c_uint32(0)
-        L.sg_mst_csv_geometry(C.byref(tile), C.byref(cap))
-        pad = -body_off % 16                                  # the body on a 16-byte boundary: the kernels' wide loads
-        d_file = torch.empty(pad + size, dtype=torch.uint8, device="cuda")
-        d_file[pad:].copy_(torch.from_numpy(data))
-        d_text = d_file[pad:]
-        d_tiles = torch.empty(-(-(size - body_off) // tile.value) + 2, dtype=torch.int32, device="cuda")
-        n_rows, flags = C.c_uint64(0), C.c_uint32(0)
         stream = ffi.current_stream_ptr()
-        ffi.check(L.sg_mst_csv_scan_dev(ffi.dev_ptr(d_text), size, body_off, ffi.dev_ptr(d_tiles), C.byref(n_rows), C.byref(flags), stream))
-        if flags.value:
-            return None, " and ".join(text for bit, text in _CSV_FLAGS if flags.value & bit)
-        n = n_rows.value
-        if n == 0:
-            return None, "no rows"
         depth = max(0, (n - 1).bit_length())
         rows = 1 << depth
         d_users = torch.empty(32 * rows, dtype=torch.uint8, device="cuda")
@@ -825,6 +918,50 @@ class DeviceMerkleSumTree(_Tree):
         tree.csv_ingest = "device"
         return tree, None
 
+    @staticmethod
+    def _csv_text_on_device(path: str, n_currencies: int):
+        """The text of a snapshot CSV in HBM behind its header line, which the host parses, and the reader's scan of it
+        (sg_mst_csv_scan_dev): -> ((d_text, size, body_off, delim, cryptocurrencies, d_tiles, n_rows), None), or (None, why the
+        device does not take this file)"""
+        import torch
+        if not 1 <= n_currencies <= 64:
+            return None, "n_currencies outside 1..64"
+        data = np.fromfile(path, dtype=np.uint8)
+        line, eol, _ = data[:1 << 16].tobytes().partition(b"\n")
+        if not eol:
+            return None, "no line end in the first 64 KiB"
+        body_off, size = len(line) + 1, int(data.size)
+        line = line[:-1] if line.endswith(b"\r") else line
+        if not line.isascii() or any(c in line for c in b'"\r\0'):
+            return None, "header line: a quote, carriage return, NUL or non-ASCII byte"
+        delim = ";" if b";" in line else ","
+        header = line.decode().split(delim)
+        crypto = [tuple(h.split("_")[1:]) for h in header[1:]]
+        if (len(header) - 1 != n_currencies or header[0] != "username"
+                or any(len(h.split("_")) != 3 or h.split("_")[0] != "balance" for h in header[1:])):
+            return None, "header line: not username and n_currencies balance_<name>_<chain> columns"
+        if body_off == size:
+            return None, "no rows"
+        if size - body_off >= 1 << 32:
+            return None, "a body of 4 GiB or more"
+        L = ffi.lib()
+        tile, cap = C.c_uint32(0), C.c_uint32(0)
+        L.sg_mst_csv_geometry(C.byref(tile), C.byref(cap))
+        pad = -body_off % 16                                  # the body on a 16-byte boundary: the kernels' wide loads
+        d_file = torch.empty(pad + size, dtype=torch.uint8, device="cuda")
+        d_file[pad:].copy_(torch.from_numpy(data))
+        d_text = d_file[pad:]
+        d_tiles = torch.empty(-(-(size - body_off) // tile.value) + 2, dtype=torch.int32, device="cuda")
+        n_rows, flags = C.c_uint64(0), C.c_uint32(0)
+        stream = ffi.current_stream_ptr()
+        ffi.check(L.sg_mst_csv_scan_dev(ffi.dev_ptr(d_text), size, body_off, ffi.dev_ptr(d_tiles), C.byref(n_rows), C.byref(flags), stream))
+        if flags.value:
+            return None, " and ".join(text for bit, text in _CSV_FLAGS if flags.value & bit)
+        n = n_rows.value
+        if n == 0:
+            return None, "no rows"
+        return (d_text, size, body_off, delim, crypto, d_tiles, n), None
+
     def _finds_on_device(self) -> bool:
         """a device-read tree that holds the names' sorted order and whose entries are still unparsed: names are looked up in the
         text in HBM"""
@@ -878,8 +1015,19 @@ class DeviceMerkleSumTree(_Tree):
             text = bytes(d["text"][lo:min(d["size"], lo + want)].cpu().numpy())
             want *= 4
         row = text[end - begin + 1:].split(b"\n")[0].rstrip(b"\r")
-        balances = [int(x) for x in row.split(d["delim"].encode())]
-        return (text[:end - begin].decode(), self._csv_lazy[1].get(index, balances))
+        if index in self._csv_lazy[1]:
+            balances = self._csv_lazy[1][index]
+        elif any(a[min(int(np.searchsorted(a, index)), a.size - 1)] == index for a in self._applied):
+            balances = self._balances_of_leaves([index])[0]   # an applied diff changed it: the leaf's own row of d_bals says what it holds
+        else:
+            balances = [int(x) for x in row.split(d["delim"].encode())]
+        return (text[:end - begin].decode(), balances)
+
+    def get_entry(self, index: int):
+        """tree.rs's get_entry; on a tree with the names' order in HBM whose entries are unparsed from the row's text there, no parse"""
+        if self._finds_on_device() and 0 <= index < (1 << self.depth):
+            return self._entry_from_text(index)
+        return super().get_entry(index)
 
     def update_leaf(self, username: str, new_balances):
         """mst.rs:169-204: new balances for one user; the leaf and its `depth` ancestors are re-hashed in place on the device.
@@ -940,6 +1088,109 @@ class DeviceMerkleSumTree(_Tree):
                                               self.n_currencies, ffi.dev_ptr(self.d_users), ffi.dev_ptr(self.d_bals),
                                               ffi.dev_ptr(self.d_h), ffi.dev_ptr(self.d_b), ffi.current_stream_ptr()))
         torch.cuda.current_stream().synchronize()
+        self._updates += 1
+
+    def diff_csv(self, path: str, cap=None) -> SnapshotDiff:
+        """The next round's CSV against this tree (SnapshotDiff has the rules).  A tree with the names' order in HBM
+        (`has_name_index`) joins the two texts where they lie, in one device call on the current stream (sr_mst_csv_diff_dev), when
+        the file is inside the device reader's subset: neither file is parsed on the host, and the lists and the summary are all
+        that comes back.  Any other tree or file goes the host's way, `diff_entries` of the parsed file, and the diff says why
+        (`ingest`, `fallback_reason`).  cap: list at most that many new rows and gone leaves (None: all)."""
+        if cap is not None and cap < 0:
+            raise ValueError("cap below 0")
+        diff, reason = self._diff_csv_on_device(path, cap)
+        if diff is None:
+            diff = super().diff_csv(path, cap)
+            diff.fallback_reason = reason
+        return diff
+
+    def _diff_csv_on_device(self, path: str, cap):
+        """-> (diff, None), or (None, why the device does not take this tree or this file)"""
+        import torch
+        t = self._names_dev()
+        if t is None:
+            return None, "the tree holds no name index"
+        nc, depth = self.n_currencies, self.depth
+        scanned, reason = self._csv_text_on_device(path, nc)
+        if scanned is None:
+            return None, reason
+        d_text, size, body_off, delim, _, d_tiles, n = scanned
+        R = ffi.rounds_lib()
+        leaves = 1 << depth
+        list_cap = max(n, leaves) if cap is None else min(int(cap), max(n, leaves))
+        scratch_bytes = C.c_uint64(0)
+        ffi.check(R.sr_mst_diff_scratch(n, depth, C.byref(scratch_bytes)))
+        i32 = lambda count: torch.empty(count, dtype=torch.int32, device="cuda")
+        d_spans = torch.empty(n + 2 + 2 * n * (1 + nc), dtype=torch.int64, device="cuda")
+        d_row_leaf, d_owner, d_changed = i32(n), i32(leaves), i32(min(n, leaves))
+        d_row_state = torch.empty(n, dtype=torch.uint8, device="cuda")
+        d_leaf_state = torch.empty(leaves, dtype=torch.uint8, device="cuda")
+        d_new, d_gone = (i32(list_cap), i32(list_cap)) if list_cap else (None, None)
+        d_scratch = i32(scratch_bytes.value // 4)
+        problem, summary = C.c_uint64(0), (C.c_uint64 * 8)()
+        ffi.check(R.sr_mst_csv_diff_dev(ffi.dev_ptr(d_text), size, body_off, ffi.dev_ptr(d_tiles), ord(delim), nc, n, ffi.dev_ptr(d_spans),
+                                        ffi.dev_ptr(t["text"]), t["size"], t["body_off"], ffi.dev_ptr(t["d_name_spans"]),
+                                        None if self._sorted_dev is not None else ffi.dev_ptr(t["d_order"]), t["n"], depth,
+                                        ffi.dev_ptr(self.d_bals), ffi.dev_ptr(d_row_leaf), ffi.dev_ptr(d_row_state), ffi.dev_ptr(d_leaf_state),
+                                        ffi.dev_ptr(d_owner), ffi.dev_ptr(d_changed), ffi.dev_ptr(d_new) if list_cap else None,
+                                        ffi.dev_ptr(d_gone) if list_cap else None, list_cap, ffi.dev_ptr(d_scratch), C.byref(problem), summary,
+                                        ffi.current_stream_ptr()))
+        if problem.value:
+            return None, f"row {problem.value >> 8}: {_CSV_ROW_PROBLEMS.get(problem.value & 0xff, 'outside the subset')}"
+        take = lambda d, count: d[:count].cpu().numpy().view(np.uint32) if count else np.zeros(0, dtype=np.uint32)
+        diff = SnapshotDiff(list(summary)[:6], take(d_changed, int(summary[2])), take(d_new, int(summary[6])), take(d_gone, int(summary[7])),
+                            {"row_leaf": d_row_leaf, "row_state": d_row_state, "leaf_state": d_leaf_state, "owner": d_owner}, "device",
+                            dev={"text": d_text, "size": size, "body_off": body_off, "n": n, "d_spans": d_spans, "d_owner": d_owner,
+                                 "d_changed": d_changed})
+        diff._tree, diff._epoch = self, self._updates
+        return diff, None
+
+    def apply_diff(self, diff: SnapshotDiff):
+        """Write the changed balances of `diff` into the tree in place and return the new root.  A device diff's balances are folded
+        once more where the file's text lies and go through the update's kernels (sr_mst_apply_diff_dev): they never visit the
+        host; only the list of changed leaves does, for the plan of the levels.  A host diff goes through `update_leaves_at`.
+        New users are not inserted and gone users are not zeroed.  ValueError for a diff taken of another tree, or of this tree
+        before another update: the tree is untouched."""
+        import torch
+        if diff._tree is not self:
+            raise ValueError("a diff of another tree")
+        if diff._epoch != self._updates:
+            raise ValueError("a diff taken before another update of the tree")
+        if diff.n_changed == 0:
+            return self.root()
+        if diff.ingest != "device":
+            return self.update_leaves_at(diff.changed.tolist(), diff.new_balances)
+        d = diff._dev
+        ffi.check(ffi.rounds_lib().sr_mst_apply_diff_dev(ffi.dev_ptr(d["text"]), d["size"], d["body_off"], ffi.dev_ptr(d["d_spans"]), d["n"],
+                                                         ffi.dev_ptr(d["d_owner"]), ffi.dev_ptr(d["d_changed"]), diff.n_changed, self.depth,
+                                                         self.n_currencies, ffi.dev_ptr(self.d_users), ffi.dev_ptr(self.d_bals),
+                                                         ffi.dev_ptr(self.d_h), ffi.dev_ptr(self.d_b), ffi.current_stream_ptr()))
+        torch.cuda.current_stream().synchronize()             # for the constructor's reason, as _update_dev
+        self._updates += 1
+        self._root = None
+        if self._csv_lazy is not None:                        # entries nobody has read yet: these leaves' balances are d_bals' now
+            self._applied = tuple(self._applied) + (diff.changed,)
+            if self._csv_lazy[1]:
+                for i in diff.changed.tolist():
+                    self._csv_lazy[1].pop(i, None)
+        elif self._entries is not None:
+            for i, bal in zip(diff.changed.tolist(), self._balances_of_leaves(diff.changed)):
+                self._entries[i] = (self._entries[i][0], bal)
+        return self.root()
+
+    def apply_csv(self, path: str, cap=None) -> SnapshotDiff:
+        """`diff_csv` followed by `apply_diff`; returns the diff"""
+        diff = self.diff_csv(path, cap)
+        self.apply_diff(diff)
+        return diff
+
+    def _balances_of_leaves(self, leaves):
+        """the balances of some leaves as integers from their rows of `d_bals`: one gather and one copy"""
+        import torch
+        nc = self.n_currencies
+        at = torch.as_tensor(np.asarray(leaves, dtype=np.int64), device="cuda")
+        rows = self.d_bals.view(-1, 32 * nc)[at].cpu().numpy()
+        return [[_mont_to_int(row[32 * c:32 * c + 32]) for c in range(nc)] for row in rows]
 
     def range_audit(self, n_bytes: int = 8, cap=None) -> RangeAudit:
         """Which users of this snapshot can receive a valid inclusion proof from a circuit of `n_bytes`: one device call
