@@ -12,6 +12,8 @@ totals (MST_DIFF_TILE, MST_DIFF_GROUP and MST_DIFF_THREADS of csrc/mst_diff.h, r
 edges are 64, 256 and 16384, and 16386 is the smallest size with leaf positions 16383, 16384 and 16385."""
 import random
 
+import numpy as np
+
 from mst_csv_cases import header, write_case  # noqa: F401  (write_case: for the tests that import this module)
 from mst_names_cases import caps_for  # noqa: F401
 
@@ -171,3 +173,114 @@ def model(a, b, nc: int, sorted_tree: bool, cap=None):
 def caps_of(m):
     """the caps a case is asked with: caps_for of its new rows and of its gone leaves"""
     return sorted(set(caps_for(m["summary"][0])) | set(caps_for(m["summary"][4])))
+
+
+# ----------------------------------------------------------------------------- past 64 groups: numpy only
+# Every list's scatter sums the totals of the groups before an item's own by a wave: LANES = 64 totals a trip of its loop, then six
+# shuffle steps.  An item's place takes a second trip only from group 65 on, item 65 * GROUP_ROWS; one of group 64 still sums
+# exactly 64 groups in one trip.  BIG is the smallest size with items 65 * GROUP_ROWS - 1 (the last place of one full trip) and
+# the first two that need a second: the tree of BIG rows has depth 21, 128 groups of leaves, and a file of BIG rows 66 of rows.
+LANES = 64
+TRIP_ROWS = LANES * GROUP_ROWS
+BIG = 65 * GROUP_ROWS + 2
+BIG_WIDTH = 7                                               # digits a name above a million names: byte order is numeric order
+BIG_EDGES = (GROUP_ROWS, TRIP_ROWS, 65 * GROUP_ROWS)
+BIG_NC = 2
+
+
+def pattern(n: int, offsets, start: int = 0):
+    """items e + d for every edge e of BIG_EDGES and d of offsets, and 1 + g % 5 items from `start` on in every group g: every
+    group's total is non-zero and neighbours' differ"""
+    out = {e + d for e in BIG_EDGES for d in offsets}
+    for g in range(-(-n // GROUP_ROWS)):
+        out |= {g * GROUP_ROWS + start + j for j in range(1 + g % 5)}
+    return np.array(sorted(p for p in out if 0 <= p < n), dtype=np.int64)
+
+
+def big_case(sorted_tree: bool, n: int = BIG):
+    """A, B1 (the report case) and B2 (the apply case) as numbers: {"a": (keys, balances [n, 2]), "b1": (..), "b2": (..),
+    "changed", "gone": the chosen leaves, "new": the renamed rows, "shadowed": the rows repeated at the end}.
+    A is n distinct names in a seeded permutation.  The chosen leaves are leaves of the tree's kind.  Group 65 has two items,
+    which the lists share: the gone leaves are e - 2 and e + 1 of every edge e and 1 + g % 5 leaves from the ninth on in every
+    group, the changed leaves e - 1 and e and the first 1 + g % 5 of every group, less the gone ones.  B1 has A's rows in A's
+    order, the changed leaves' first balance or second bumped, the gone leaves' rows under fresh names -- in a sorted tree also
+    the rows e - 1, e, e + 1 and the first 1 + g % 5 of every group of rows, whose leaves lie anywhere: there the new rows' list
+    has both rows of group 65 --, and three rows once more at the end.  B2 has A's names in A's order and the same bumps."""
+    seed = int.from_bytes(f"mst_diff_cases.big.{n}".encode(), "little") % (1 << 63)
+    keys = np.random.default_rng(seed).permutation(n).astype(np.int64)
+    rows = np.arange(n, dtype=np.int64)
+    bal = np.stack([10_000_000 + 2 * rows, 20_000_000 + 2 * rows + 1], axis=1)
+    order = np.argsort(keys, kind="stable") if sorted_tree else rows           # the file row of A at every leaf
+    leaf_of_row = np.empty(n, dtype=np.int64)
+    leaf_of_row[order] = rows
+    new_rows = order[pattern(n, (-2, 1), 8)]
+    if sorted_tree:
+        new_rows = np.union1d(new_rows, pattern(n, (-1, 0, 1)))
+    new_rows = np.sort(new_rows)
+    gone = np.sort(leaf_of_row[new_rows])
+    changed = np.setdiff1d(pattern(n, (-1, 0)), gone)
+    bumped = bal.copy()
+    at = order[changed]
+    bumped[at, changed % 2] += 1
+    b1_keys, b1_bal = keys.copy(), bumped.copy()
+    b1_keys[new_rows] = n + np.arange(new_rows.size)
+    again = np.setdiff1d(rows, new_rows)[[0, 5, -1]]         # (of rows that keep their names: the later row is shadowed)
+    b1_keys, b1_bal = np.concatenate([b1_keys, b1_keys[again]]), np.concatenate([b1_bal, b1_bal[again] + 5])
+    return {"a": (keys, bal), "b1": (b1_keys, b1_bal), "b2": (keys, bumped), "changed": changed, "gone": gone, "new": new_rows,
+            "shadowed": n + np.arange(3)}
+
+
+def write_big(path, keys, bal):
+    """a file of 7-digit names and two balances of 8 digits a row, without a per-row step"""
+    from mst_names_cases import fixed_rows, write_fixed
+    return write_fixed(path, bal.shape[1], fixed_rows(keys, BIG_WIDTH, list(bal.T)))
+
+
+def fixed_width(rows):
+    """are these rows' names digits of one width (model_np's)?"""
+    return bool(rows) and all(nm.isdigit() and len(nm) == len(rows[0][0]) for nm, _ in rows)
+
+
+def as_numbers(rows):
+    """rows [(name bytes, [balance texts])] with fixed-width names -> (keys, balances [n, nc]); the balances are below 2^62"""
+    return np.array([int(nm) for nm, _ in rows], dtype=np.int64), np.array([[int(x) for x in bal] for _, bal in rows], dtype=np.int64)
+
+
+def model_np(a, b, sorted_tree: bool, cap=None):
+    """model() for names of fixed-width digits, a and b as (keys, balances [n, nc]) of integers below r: the same keys, arrays for
+    lists ("balances": [changed, nc], the owner rows')"""
+    (a_keys, a_bal), (b_keys, b_bal) = a, b
+    n_tree, n = a_keys.size, b_keys.size
+    depth = max(0, (n_tree - 1).bit_length())
+    leaves = 1 << depth
+    order = np.argsort(a_keys, kind="stable") if sorted_tree else np.arange(n_tree, dtype=np.int64)
+    by_leaf = a_keys[order]
+    by_name = np.argsort(by_leaf, kind="stable")             # the leaves by name, equal names by leaf: a run's first is found
+    s = by_leaf[by_name]
+    heads = np.ones(n_tree, dtype=bool)
+    heads[1:] = s[1:] != s[:-1]
+    names, first_leaf = s[heads], by_name[heads]
+    at = np.minimum(np.searchsorted(names, b_keys), names.size - 1)
+    found = names[at] == b_keys
+    rows = np.arange(n, dtype=np.int64)
+    row_leaf = np.where(found, first_leaf[at], ABSENT)
+    owner = np.full(leaves, ABSENT, dtype=np.int64)
+    owned, at_first = np.unique(row_leaf[found], return_index=True)           # the first occurrence: the lowest row
+    owner[owned] = rows[found][at_first]
+    owns = found.copy()
+    owns[found] = owner[row_leaf[found]] == rows[found]
+    same = np.zeros(n, dtype=bool)
+    same[owns] = (b_bal[owns] == a_bal[order[row_leaf[owns]]]).all(axis=1)
+    row_state = np.where(~found, ROW_NEW, np.where(~owns, ROW_SHADOWED, np.where(same, ROW_SAME, ROW_CHANGED))).astype(np.uint8)
+    leaf_state = np.full(leaves, LEAF_PADDING, dtype=np.uint8)
+    leaf_state[:n_tree] = LEAF_GONE
+    leaf_state[row_leaf[owns]] = np.where(same[owns], LEAF_SAME, LEAF_CHANGED)
+    leaf_state[by_name[~heads]] = LEAF_UNREACHABLE
+    changed, new, gone = (np.flatnonzero(x).astype(np.uint32) for x in (leaf_state == LEAF_CHANGED, row_state == ROW_NEW, leaf_state == LEAF_GONE))
+    new_listed, gone_listed = (x.size if cap is None else min(cap, x.size) for x in (new, gone))
+    count = lambda states, code: int(np.count_nonzero(states == code))
+    summary = [int(new.size), count(row_state, ROW_SHADOWED), count(row_state, ROW_CHANGED), count(row_state, ROW_SAME), int(gone.size),
+               count(leaf_state, LEAF_UNREACHABLE), new_listed, gone_listed]
+    return {"n_tree": n_tree, "depth": depth, "row_leaf": row_leaf.astype(np.uint32), "row_state": row_state, "leaf_state": leaf_state,
+            "owner": owner.astype(np.uint32), "changed": changed, "new": new[:new_listed], "gone": gone[:gone_listed], "summary": summary,
+            "balances": b_bal[owner[changed]], "leaf_rows": order}

@@ -9,6 +9,8 @@ multiset M has M[p] = M[p - 1] for every p of a set of edges and a fresh name ot
 balances are distinct per row, so that file order shows in the leaves."""
 import random
 
+import numpy as np
+
 import mst_sort_cases as sort_cases
 from mst_csv_cases import GOLDENS, header, write_case  # noqa: F401  (write_case: for the tests that import this module)
 
@@ -30,21 +32,21 @@ EDGE_SETS = {
 }
 
 
-def multiset(n: int, edges):
+def multiset(n: int, edges, width: int = 6):
     """the sorted names: M[p] = M[p - 1] for p in edges, else the next fresh name"""
     edges, out, k = set(edges), [], 0
     for p in range(n):
         if p and p in edges:
             out.append(out[-1])
         else:
-            out.append(f"{k:06d}")
+            out.append(f"{k:0{width}d}")
             k += 1
     return out
 
 
-def generated(n: int, edge_set: str):
+def generated(n: int, edge_set: str, width: int = 6):
     """the names of the rows in file order: the multiset in a seeded shuffle"""
-    names = multiset(n, EDGE_SETS[edge_set])
+    names = multiset(n, EDGE_SETS[edge_set], width)
     random.Random(f"mst_names_cases.{edge_set}.{n}").shuffle(names)
     return names
 
@@ -109,3 +111,89 @@ def first_rows(names):
     for row, name in enumerate(names):
         out.setdefault(name, row)
     return out
+
+
+# ----------------------------------------------------------------------------- past 64 groups: numpy only
+# The scatter sums the totals of the groups before a position's own by a wave: LANES = 64 totals a trip of its loop, then six
+# shuffle steps.  A position's place takes a second trip only from group 65 on, position 65 * GROUP_ROWS; one of group 64 still
+# sums exactly 64 groups in one trip.  BIG is the smallest size with positions 65 * GROUP_ROWS - 1 (the last place of one full
+# trip) and the first two that need a second.  Above a million names the width is 7 digits: byte order is numeric order.
+LANES = 64
+TRIP_ROWS = LANES * GROUP_ROWS
+BIG = 65 * GROUP_ROWS + 2
+BIG_WIDTH = 7
+BIG_EDGES = (GROUP_ROWS, TRIP_ROWS, 65 * GROUP_ROWS)
+
+
+def big_edges(n: int = BIG, edges=BIG_EDGES):
+    """the positions p with M[p] = M[p - 1]: both sides of the group edge, of the end of a trip and of the start of group 65,
+    and 1 + g % 5 positions at the start of every group g, so that every group's total is non-zero and neighbours' differ"""
+    out = {e + d for e in edges for d in (-1, 0, 1)}
+    for g in range(-(-n // GROUP_ROWS)):
+        out |= {g * GROUP_ROWS + j for j in range(1 + g % 5)}
+    return np.array(sorted(p for p in out if 0 < p < n), dtype=np.int64)
+
+
+def big_keys(n: int = BIG, tag: str = "names"):
+    """the big case's names as numbers, in file order: multiset(n, big_edges(n)) in a seeded permutation"""
+    fresh = np.ones(n, dtype=bool)
+    fresh[big_edges(n)] = False
+    m = np.cumsum(fresh) - 1
+    seed = int.from_bytes(f"mst_names_cases.big.{tag}.{n}".encode(), "little") % (1 << 63)
+    return m[np.random.default_rng(seed).permutation(n)]
+
+
+def digits(values, width: int):
+    """integers -> their decimal digits, zero-padded: uint8 [len, width]"""
+    values = np.asarray(values, dtype=np.int64)
+    assert values.size == 0 or (values.min() >= 0 and values.max() < 10 ** width)
+    return (values[:, None] // 10 ** np.arange(width - 1, -1, -1, dtype=np.int64) % 10 + ord("0")).astype(np.uint8)
+
+
+def fixed_rows(keys, width: int, balances, balance_width: int = 8, delim: str = ","):
+    """the body of a CSV whose rows have one width: the name's `width` digits and every column of `balances` in `balance_width`
+    digits -> uint8, one allocation and no per-row Python"""
+    cols = []
+    for column in [digits(keys, width)] + [digits(b, balance_width) for b in balances]:
+        cols += [column, np.full((len(keys), 1), ord(delim), dtype=np.uint8)]
+    cols[-1] = np.full((len(keys), 1), ord("\n"), dtype=np.uint8)
+    return np.concatenate(cols, axis=1).reshape(-1)
+
+
+def write_fixed(path, nc: int, body):
+    """header(nc) and a body of fixed_rows -> path"""
+    with open(path, "wb") as f:
+        f.write(header(nc).encode())
+        body.tofile(f)
+    return str(path)
+
+
+def keys_of(names):
+    """names (bytes, file order) -> integers that order as the names' bytes do: the numbers of fixed-width digits, else ranks"""
+    if names and all(nm.isdigit() and len(nm) == len(names[0]) for nm in names):
+        return np.array([int(nm) for nm in names], dtype=np.int64)
+    rank = {nm: k for k, nm in enumerate(sorted(set(names)))}
+    return np.array([rank[nm] for nm in names], dtype=np.int64)
+
+
+def shadowed_positions(keys):
+    """(the stable order, which sorted positions are shadowed: bool per position)"""
+    keys = np.asarray(keys)
+    order = np.argsort(keys, kind="stable")
+    s = keys[order]
+    same = np.zeros(keys.size, dtype=bool)
+    same[1:] = s[1:] == s[:-1]
+    return order, same
+
+
+def model_np(keys, cap=None, in_file_order: bool = True):
+    """model() over integer keys, in numpy: the lists are uint32 arrays"""
+    order, same = shadowed_positions(keys)
+    pos = np.arange(order.size, dtype=np.int64)
+    head = np.maximum.accumulate(np.where(same, 0, pos))      # the start of every position's run
+    at = np.flatnonzero(same)
+    leaf = order if in_file_order else pos
+    listed = at.size if cap is None else min(cap, at.size)
+    repeated = int(np.count_nonzero(same[1:] & ~same[:-1]))
+    return {"summary": [repeated, int(at.size), listed], "shadowed": leaf[at[:listed]].astype(np.uint32),
+            "first": leaf[head[at[:listed]]].astype(np.uint32)}

@@ -3,7 +3,10 @@ explain_unprovable and prove_batch(audit=...)) against the integer model of mst_
 and all four summary words, compared exactly.  The synthetic cases upload level-major sums mod r in Montgomery form -- the audit
 reads balances only, so no hash is needed -- at the depths of mst_audit_cases.DEPTHS (block edges), at depth 11 (several tiles of
 the list's scan) and at GROUPS_DEPTH = 15: 2^15 leaves are 512 tiles of 64, more than the 256 tile counts one workgroup of the
-groups step scans, so the second group's places depend on the first group's total."""
+groups step scans, so the second group's places depend on the first group's total.  Sparse trees at depths 16, 20 and 21, against
+the numpy model over their non-zero nodes, have 4, 64 and 128 such groups: the scatter's wave sums 64 group totals a trip of its
+loop, so every lane and shuffle step carries data at 64 and the second trip runs at 128.  And 5, 33, 63 and 64 currencies put a
+node's bits of the flags kernel's bit string across a word's edge, or exactly on it."""
 import ctypes as C
 import os
 
@@ -83,6 +86,61 @@ def test_the_tile_counts_span_two_groups_of_the_prefix_step(gpu, nc, n_bytes):
     for name, plant, caps in cases.plants(depth, nc, n_bytes):
         if name in ("edges", "every leaf", "last leaf"):
             check(gpu, cases.planted(depth, nc, n_bytes, plant), n_bytes, caps[:3], (name, depth, nc, n_bytes))
+
+
+@pytest.mark.parametrize("nc", cases.MANY_CURRENCIES)
+@pytest.mark.parametrize("depth", cases.MANY_DEPTHS)
+def test_the_bit_gather_at_many_currencies_agrees_with_the_model(gpu, depth, nc):
+    """a node's nc bits out of the workgroup's bit string: fields that straddle a word of it with up to 63 bits on either side
+    (nc = 5, 33, 63) and the aligned one that skips the mask (nc = 64), flags up to 64, a partial last block"""
+    for n_bytes in cases.MANY_N_BYTES:
+        for name, plant, caps in cases.plants(depth, nc, n_bytes) + cases.many_currency_plants(depth, nc, n_bytes):
+            check(gpu, cases.planted(depth, nc, n_bytes, plant), n_bytes, caps, (name, depth, nc, n_bytes))
+
+
+def run_abi_np(ffi, d_bal, depth, nc, n_bytes, cap):
+    """run_abi for the depths where lists of Python integers cost too much: the same call over the same pre-filled buffers, the
+    outputs as numpy arrays, the list whole -- the listed leaves and the two spare entries behind the cap"""
+    import torch
+    S = ffi.snapshot_lib()
+    leaves = 1 << depth
+    bad_cap = leaves if cap is None else cap
+    size = C.c_uint64(0)
+    ffi.check(S.ss_mst_range_audit_scratch(depth, C.byref(size)))
+    d_flags = torch.full((2 * leaves - 1,), 0xEE, dtype=torch.uint8, device="cuda")
+    d_masks = torch.full((leaves,), UNWRITTEN, dtype=torch.int32, device="cuda")
+    d_bad = torch.full((bad_cap + 2,), UNWRITTEN, dtype=torch.int32, device="cuda")
+    d_scratch = torch.full((size.value // 4,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
+    summary = (C.c_uint64 * 4)()
+    torch.cuda.current_stream().synchronize()
+    ffi.check(S.ss_mst_range_audit_dev(ffi.dev_ptr(d_bal), depth, nc, n_bytes, ffi.dev_ptr(d_flags), ffi.dev_ptr(d_masks),
+                                       ffi.dev_ptr(d_bad) if bad_cap else None, bad_cap, ffi.dev_ptr(d_scratch), summary,
+                                       ffi.current_stream_ptr()))
+    return {"flags": d_flags.cpu().numpy(), "masks": d_masks.cpu().numpy().view(np.uint32), "bad": d_bad.cpu().numpy().view(np.uint32),
+            "summary": list(summary)}
+
+
+@pytest.mark.parametrize("depth", sorted(cases.SPARSE_DEPTHS))
+def test_sparse_trees_past_64_groups_agree_with_the_numpy_model(gpu, depth):
+    """4, 64 and 128 groups of the list's compaction: at 64 every lane of the scatter's wave holds a group's total and all six
+    shuffle steps carry data, at 128 the loop over the totals takes its second trip"""
+    import torch
+    nc, n_bytes = cases.SPARSE_DEPTHS[depth], cases.SPARSE_N_BYTES
+    assert (1 << depth) // cases.GROUP_ROWS == {16: 4, 20: cases.LANES, 21: 2 * cases.LANES}[depth]
+    for name, plant, caps in cases.sparse_plants(depth, n_bytes):
+        nodes = cases.sparse_nodes(depth, nc, plant)
+        d_bal = torch.from_numpy(cases.sparse_bytes(depth, nc, nodes)).cuda()
+        full = cases.sparse_model(depth, n_bytes, nodes)
+        assert full["summary"][1] == caps[3] and len(caps) == 5 + (depth == 21) and all(1 < c < caps[3] for c in caps[5:])
+        for cap in caps:
+            want, got = cases.cut(full, cap), run_abi_np(gpu, d_bal, depth, nc, n_bytes, cap)
+            what = (name, depth, cap)
+            assert got["summary"] == want["summary"], what
+            listed = want["summary"][2]
+            wrong = np.flatnonzero(got["bad"][:listed] != want["bad"])
+            assert wrong.size == 0, (what, "the list", int(wrong[0]), int(got["bad"][wrong[0]]), int(want["bad"][wrong[0]]))
+            assert (got["bad"][listed:] == UNWRITTEN).all(), (what, "entries behind the listed leaves were written")
+            assert np.array_equal(got["masks"], want["masks"]) and np.array_equal(got["flags"], want["flags"]), what
 
 
 @pytest.mark.parametrize("kind", wc.TREE_KINDS)

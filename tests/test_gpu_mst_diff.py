@@ -3,7 +3,8 @@ against the model of mst_diff_cases.py on every case and cap, the tree after sr_
 leaves with the changed balances (bit for bit, the oracle's root at the small sizes, `from_csv` of the new file where the leaves
 line up), the Python surface -- `diff_csv`, `apply_diff`, `apply_csv` and what the tree says of its entries afterwards, with no
 host parse and no balance packed on the device way --, the host fallback, the stale diff, and the stream order of both entry
-points with the helpers of test_gpu_stream_order.py."""
+points with the helpers of test_gpu_stream_order.py.  The report and the apply once more at mst_diff_cases.BIG rows against the
+numpy model: past 64 groups of the lists' compaction, where the scatter's sum of the group totals takes a second trip."""
 import ctypes as C
 import functools
 
@@ -360,6 +361,107 @@ def test_the_apply_on_a_stream_of_the_callers(gpu, files):
     assert diff.n_changed == 16386 and diff.ingest == "device"
     for what in ("d_bals", "d_h", "d_b"):
         _same(getattr(tree, what).cpu().numpy(), want[what], f"{name}: {what}")
+
+
+# ============================================================================= past 64 groups of the lists' compaction
+@pytest.fixture(scope="module")
+def big(tmp_path_factory):
+    """{sorted_tree: the big case, with the paths of its files under "paths"}: A, B1 and, for the tree in file order, B2"""
+    d = tmp_path_factory.mktemp("mst_diff_big")
+    out = {}
+    for sorted_tree in (False, True):
+        case = cases.big_case(sorted_tree)
+        kind = "sorted" if sorted_tree else "file"
+        case["paths"] = {k: cases.write_big(d / f"{kind}.{k}.csv", *case[k]) for k in (("a", "b1") if sorted_tree else ("a", "b1", "b2"))}
+        out[sorted_tree] = case
+    return out
+
+
+def big_tree(case, sorted_tree):
+    from circuits_halo2_amd.merkle_sum_tree import DeviceMerkleSumTree
+    path = case["paths"]["a"]
+    tree = DeviceMerkleSumTree.from_csv_sorted(path, cases.BIG_NC) if sorted_tree else DeviceMerkleSumTree.from_csv(path, cases.BIG_NC, name_index=True)
+    assert tree.csv_ingest == "device" and tree.has_name_index and (tree.depth, tree._names_dev()["n"]) == (21, cases.BIG)
+    return tree
+
+
+def run_diff_np(tree, scanned, cap):
+    """run_diff over a file scanned once, for the sizes where lists of Python integers cost too much: the same call over buffers
+    pre-filled and guarded in the same way, every output whole as a numpy array"""
+    import torch
+    from circuits_halo2_amd import ffi
+    nc, depth = tree.n_currencies, tree.depth
+    text, size, body_off, delim, _, tiles, n = scanned
+    R = ffi.rounds_lib()
+    leaves = 1 << depth
+    scratch = C.c_uint64(0)
+    ffi.check(R.sr_mst_diff_scratch(n, depth, C.byref(scratch)))
+    sizes = {"spans": 8 * (n + 2 + 2 * n * (1 + nc)), "row_leaf": 4 * n, "row_state": n, "leaf_state": leaves, "owner": 4 * leaves,
+             "changed": 4 * min(n, leaves), "new": 4 * cap, "gone": 4 * cap, "scratch": scratch.value}
+    b = {k: _guarded(v) for k, v in sizes.items()}
+    t = tree._names_dev()
+    problem, summary = C.c_uint64(77), (C.c_uint64 * 8)()
+    ffi.check(R.sr_mst_csv_diff_dev(ffi.dev_ptr(text), size, body_off, ffi.dev_ptr(tiles), ord(delim), nc, n, ffi.dev_ptr(b["spans"]),
+                                    ffi.dev_ptr(t["text"]), t["size"], t["body_off"], ffi.dev_ptr(t["d_name_spans"]),
+                                    None if tree._sorted_dev is not None else ffi.dev_ptr(t["d_order"]), t["n"], depth, ffi.dev_ptr(tree.d_bals),
+                                    ffi.dev_ptr(b["row_leaf"]), ffi.dev_ptr(b["row_state"]), ffi.dev_ptr(b["leaf_state"]), ffi.dev_ptr(b["owner"]),
+                                    ffi.dev_ptr(b["changed"]), ffi.dev_ptr(b["new"]) if cap else None, ffi.dev_ptr(b["gone"]) if cap else None,
+                                    cap, ffi.dev_ptr(b["scratch"]), C.byref(problem), summary, ffi.current_stream_ptr()))
+    torch.cuda.current_stream().synchronize()
+    assert problem.value == 0
+    for k, used in sizes.items():
+        assert (b[k][used:] == GUARD).all(), f"the bytes behind {k} changed"
+    out = {k: b[k][:sizes[k]].cpu().numpy() for k in ("row_state", "leaf_state")}
+    out.update({k: b[k][:sizes[k]].cpu().numpy().view(np.uint32) for k in ("row_leaf", "owner", "changed", "new", "gone")})
+    return dict(out, summary=[int(x) for x in summary])
+
+
+def _same_array(got, want, what):
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    wrong = np.flatnonzero(got != want)
+    assert wrong.size == 0, (what, f"{wrong.size} entries differ, the first at", int(wrong[0]), int(got[wrong[0]]), int(want[wrong[0]]))
+
+
+@pytest.mark.parametrize("sorted_tree", [False, True], ids=["file", "sorted"])
+def test_every_output_of_the_diff_at_big_rows_equals_the_numpy_model(gpu, big, sorted_tree):
+    """a tree of depth 21 -- 128 groups of leaves, the chosen ones in groups 0 .. 65 -- and a file of 66 groups of rows: items of
+    group 64 sum 64 group totals in one full trip of the scatter's loop, all six shuffle steps carrying data, those of group 65
+    take the second trip"""
+    from circuits_halo2_amd.merkle_sum_tree import DeviceMerkleSumTree
+    case = big[sorted_tree]
+    tree = big_tree(case, sorted_tree)
+    full = cases.model_np(case["a"], case["b1"], sorted_tree)
+    scanned, reason = DeviceMerkleSumTree._csv_text_on_device(case["paths"]["b1"], cases.BIG_NC)
+    assert scanned is not None, reason
+    n_new, n_gone = full["summary"][0], full["summary"][4]
+    before_65 = int(np.count_nonzero(full["new"] < 65 * cases.GROUP_ROWS))
+    assert before_65 > 1 and n_new - before_65 == (2 if sorted_tree else 1)     # the new rows of group 65: see big_case
+    for cap in sorted({0, 1, max(n_new, n_gone), before_65, before_65 + 1}):
+        want = cases.model_np(case["a"], case["b1"], sorted_tree, cap)
+        got = run_diff_np(tree, scanned, cap)
+        assert got["summary"] == want["summary"], (cap, got["summary"])
+        for key in ("row_leaf", "row_state", "leaf_state", "owner"):
+            _same_array(got[key], want[key], (cap, key))
+        for key in ("changed", "new", "gone"):
+            listed = want[key].size
+            _same_array(got[key][:listed], want[key], (cap, key))
+            assert (got[key][listed:] == FILL32).all(), (cap, key, "an entry behind the listed ones was written")
+
+
+def test_the_apply_at_big_rows_leaves_the_new_files_own_tree(gpu, big):
+    """apply_csv of B2 on the tree in file order: the leaves line up with the new file's own tree, bit for bit in all four arrays"""
+    from circuits_halo2_amd.merkle_sum_tree import DeviceMerkleSumTree
+    case = big[False]
+    tree = big_tree(case, False)
+    diff = tree.apply_csv(case["paths"]["b2"])
+    assert diff.ingest == "device" and np.array_equal(diff.changed, case["changed"].astype(np.uint32))
+    changed = case["changed"].size
+    assert diff.summary() == dict(zip(cases.SUMMARY, [0, 0, changed, cases.BIG - changed, 0, 0, 0, 0]))
+    fresh = DeviceMerkleSumTree.from_csv(case["paths"]["b2"], cases.BIG_NC, name_index=True)
+    for what in ("d_users", "d_bals", "d_h", "d_b"):
+        _same(getattr(tree, what).cpu().numpy(), getattr(fresh, what).cpu().numpy(), f"big: {what}")
+    again = tree.diff_csv(case["paths"]["b2"])
+    assert again.n_changed == 0 and again.changed.size == 0 and again.n_same == cases.BIG and again.n_new == again.n_gone == 0
 
 
 # ============================================================================= stream order

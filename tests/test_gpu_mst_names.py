@@ -6,7 +6,8 @@ Through the ABI, per case: the three arrays of the index against Python's stable
 and two absent ones through ss_mst_find_leaves against list.index -- the reference's position() --; the report against the model,
 summary and both lists word for word, at every cap, with the order (leaves in file order) and without it (a sorted tree), and
 with what lies behind the listed entries untouched.  Through Python: `from_csv(name_index=True)` builds the tree `from_csv` builds
-and answers by name without a host parse.  Both new device calls are held to the stream-order contract with the sequence of
+and answers by name without a host parse.  The report once more at mst_names_cases.BIG rows, 66 groups of its compaction,
+against the numpy model: the scatter's wave sums 64 group totals a trip of its loop.  Both new device calls are held to the stream-order contract with the sequence of
 tests/test_gpu_mst_sort.py."""
 import ctypes as C
 import functools
@@ -279,6 +280,77 @@ def test_a_host_read_file_says_why_it_has_no_index(gpu, tmp_path):
     assert tree.csv_ingest == "host" and not tree.has_name_index and tree.name_index_reason == tree.csv_fallback_reason != None  # noqa: E711
     dups = tree.duplicate_names()
     assert (dups.n_repeated_names, dups.n_shadowed, dups.shadowed.tolist(), dups.first.tolist()) == (1, 1, [2], [0])
+
+
+# ============================================================================= the report past 64 groups of its compaction
+@pytest.fixture(scope="module")
+def big_file(tmp_path_factory):
+    """BIG rows of 7-digit names, repeated at both sides of the edges and at the start of every group: (path, keys in file order)"""
+    keys = cases.big_keys()
+    rows = np.arange(keys.size, dtype=np.int64)
+    path = tmp_path_factory.mktemp("mst_names_big") / "big.csv"
+    return cases.write_fixed(path, 2, cases.fixed_rows(keys, cases.BIG_WIDTH, [10_000_000 + 3 * rows, 20_000_000 + 7 * rows])), keys
+
+
+@pytest.fixture(scope="module")
+def big_trees(gpu, big_file):
+    """{ordered: the tree}: `from_csv(name_index=True)`, leaves in file order, and `from_csv_sorted`, of the one file"""
+    from circuits_halo2_amd import merkle_sum_tree as M
+    path, keys = big_file
+    trees = {True: M.DeviceMerkleSumTree.from_csv(path, 2, 8, name_index=True), False: M.DeviceMerkleSumTree.from_csv_sorted(path, 2, 8)}
+    for ordered, tree in trees.items():
+        assert tree.csv_ingest == "device" and tree.has_name_index and tree.is_sorted == (not ordered)
+        assert (tree.depth, tree._names_dev()["n"]) == (21, cases.BIG)
+    return trees
+
+
+def report_np(d, n, cap, ordered):
+    """report() over a tree's own index, the lists as numpy arrays: (summary, shadowed, first), each list with the 16 entries behind
+    the cap, pre-filled"""
+    import torch
+    from circuits_halo2_amd import ffi
+    S = ffi.snapshot_lib()
+    scratch_bytes = C.c_uint64(0)
+    ffi.check(S.ss_mst_duplicate_names_scratch(n, C.byref(scratch_bytes)))
+    scratch = _guarded(scratch_bytes.value)
+    lists = {k: _guarded(4 * cap) for k in ("shadowed", "first")}
+    summary = (C.c_uint64 * 3)(71, 72, 73)
+    ffi.check(S.ss_mst_duplicate_names_dev(ffi.dev_ptr(d["text"]), d["size"], d["body_off"], ffi.dev_ptr(d["d_name_spans"]),
+                                           ffi.dev_ptr(d["d_order"]) if ordered else None, n,
+                                           ffi.dev_ptr(lists["shadowed"]) if cap else None, ffi.dev_ptr(lists["first"]) if cap else None, cap,
+                                           ffi.dev_ptr(scratch), summary, ffi.current_stream_ptr()))
+    torch.cuda.current_stream().synchronize()
+    assert (scratch[scratch_bytes.value:] == GUARD).all(), "the bytes behind d_scratch changed"
+    return [int(x) for x in summary], lists["shadowed"].cpu().numpy().view(np.uint32), lists["first"].cpu().numpy().view(np.uint32)
+
+
+@pytest.mark.parametrize("ordered", [True, False], ids=["file_order", "sorted"])
+def test_the_report_at_big_rows_agrees_with_the_numpy_model(gpu, big_file, big_trees, ordered):
+    """66 groups of sorted positions: positions of group 64 sum 64 group totals in one full trip of the scatter's loop, all six
+    shuffle steps carrying data; the two positions of group 65 take the second trip"""
+    keys = big_file[1]
+    tree = big_trees[ordered]
+    d = tree._names_dev()
+    order, same = cases.shadowed_positions(keys)
+    assert np.array_equal(d["d_order"].cpu().numpy().view(np.uint32), order), "d_order is not numpy's stable order"
+    full = cases.model_np(keys, None, ordered)
+    count = full["summary"][1]
+    inside_65 = int(np.count_nonzero(same[:65 * cases.GROUP_ROWS])) + 1
+    assert same[cases.BIG - 2] and same[cases.BIG - 1] and inside_65 == count - 1
+    for cap in sorted({0, 1, count, count - 1, count + 5, inside_65}):
+        want = cases.model_np(keys, cap, ordered)
+        summary, shadowed, first = report_np(d, cases.BIG, cap, ordered)
+        assert summary == want["summary"], (cap, summary)
+        listed = want["summary"][2]
+        for what, got in (("shadowed", shadowed), ("first", first)):
+            wrong = np.flatnonzero(got[:listed] != want[what])
+            assert wrong.size == 0, (cap, what, "entry", int(wrong[0]), int(got[wrong[0]]), int(want[what][wrong[0]]))
+            assert (got[listed:] == GUARD * 0x01010101).all(), f"{what}: an entry behind the {listed} listed ones was written (cap {cap})"
+    dups = tree.duplicate_names()
+    assert [dups.n_repeated_names, dups.n_shadowed, len(dups.shadowed)] == full["summary"]
+    assert np.array_equal(dups.shadowed, full["shadowed"]) and np.array_equal(dups.first, full["first"])
+    capped = tree.duplicate_names(cap=inside_65)
+    assert np.array_equal(capped.shadowed, full["shadowed"][:inside_65]) and capped.n_shadowed == count
 
 
 # ============================================================================= stream order

@@ -160,6 +160,118 @@ def test_the_groups_depth_spans_two_groups(exe):
     assert audit(exe, levels, n_bytes, cap) == cases.model(levels, n_bytes, cap)
 
 
+def audits(exe, asked):
+    """audit() for [(levels, n_bytes, bad_cap)] in one run of the program"""
+    lines = []
+    for levels, n_bytes, bad_cap in asked:
+        values = " ".join(format(v, "x") for v in cases.level_major(levels))
+        lines.append(f"audit {len(levels) - 1} {len(levels[0][0])} {n_bytes} {bad_cap} {values}")
+    out = ask(exe, lines)
+    assert [w[0] for w in out] == ["flags", "masks", "bad", "summary"] * len(asked)
+    return [{w[0]: [int(x) for x in w[1:]] for w in out[4 * k:4 * k + 4]} for k in range(len(asked))]
+
+
+def test_the_geometry_past_64_groups():
+    """what the sparse depths and BIG are for: a wave sums LANES group totals a trip"""
+    assert (cases.LANES, cases.GROUP_ROWS, cases.TRIP_ROWS) == (64, cases.TILE * cases.GROUP, 64 * 16384) and cases.TRIP_ROWS == 1 << 20
+    assert cases.BIG == 65 * cases.GROUP_ROWS + 2 == 1_064_962
+    group = lambda item: item // cases.GROUP_ROWS           # the groups before an item's own are 0 .. group - 1
+    trips = lambda item: -(-group(item) // cases.LANES)
+    assert [trips(cases.BIG - 3), trips(cases.BIG - 2), trips(cases.BIG - 1)] == [1, 2, 2] and group(cases.BIG - 3) == cases.LANES
+    assert trips(cases.TRIP_ROWS - 1) == trips(cases.TRIP_ROWS) == 1 and group(cases.TRIP_ROWS) == cases.LANES
+    assert {d: (1 << d) // cases.GROUP_ROWS for d in cases.SPARSE_DEPTHS} == {16: 4, 20: 64, 21: 128}
+    assert trips((1 << 20) - 1) == 1 and trips((1 << 21) - 1) == 2
+    for depth in cases.SPARSE_DEPTHS:
+        spots, groups = cases.sparse_spots(depth), (1 << depth) // cases.GROUP_ROWS
+        per_group = [sum(1 for i in spots if group(i) == g) for g in range(groups)]
+        assert all(per_group) and all(x != y for x, y in zip(per_group, per_group[1:]))
+        for g in {0, 63, 64, 65, groups - 1} & set(range(groups)):
+            assert {g * cases.GROUP_ROWS, (g + 1) * cases.GROUP_ROWS - 1} <= set(spots), (depth, g)
+        assert len({i >> 1 for i in spots}) == len(spots)
+        caps = [c[2] for c in cases.sparse_plants(depth, 8)]
+        assert caps[0][3] == 2 * len(spots) and caps[1][3] == 1 << depth
+        if depth == 21:
+            assert caps[0][5] == 2 * sum(per_group[:65]) + 1 and caps[1][5] == 65 * cases.GROUP_ROWS + 1 == cases.BIG - 1
+
+
+def _same_as_model(sparse, want, what):
+    assert {k: (v if k == "summary" else v.tolist()) for k, v in sparse.items()} == want, what
+
+
+@pytest.mark.parametrize("depth", [0, 1, 6, 7, 8, 11])
+def test_the_sparse_model_is_the_model(depth):
+    """key for key on every plant and cap of the dense family (its trees given as their non-zero nodes), and on the sparse
+    plants at these depths, whose nodes sparse_nodes computes: the tree of zeros with the plant, built densely, has the same"""
+    for nc, n_bytes in ((1, 1), (2, 5), (3, 8), (4, 31)):
+        for name, plant, caps in cases.plants(depth, nc, n_bytes):
+            levels = cases.planted(depth, nc, n_bytes, plant)
+            for cap in caps:
+                _same_as_model(cases.sparse_model(depth, n_bytes, cases.nonzero_nodes(levels), cap),
+                               cases.model(levels, n_bytes, (1 << depth) if cap is None else cap), (name, nc, n_bytes, cap))
+        for name, plant, caps in cases.sparse_plants(depth, n_bytes) + cases.plants(depth, nc, n_bytes):
+            zeros = [[0] * nc for _ in range(1 << depth)]
+            for leaf, c, v in plant:
+                zeros[leaf][c] = v
+            levels = cases.levels_of(zeros)
+            nodes = cases.sparse_nodes(depth, nc, plant)
+            assert nodes == cases.nonzero_nodes(levels), (name, nc, n_bytes)
+            assert np.array_equal(cases.sparse_bytes(depth, nc, nodes), cases.mont_bytes(cases.level_major(levels))), (name, nc)
+            full = cases.sparse_model(depth, n_bytes, nodes)
+            for cap in caps:
+                want = cases.model(levels, n_bytes, (1 << depth) if cap is None else cap)
+                _same_as_model(cases.sparse_model(depth, n_bytes, nodes, cap), want, (name, nc, n_bytes, cap))
+                _same_as_model(cases.cut(full, cap), want, (name, nc, n_bytes, cap))
+
+
+def test_the_mirror_agrees_with_the_sparse_model_at_four_groups(exe):
+    """depth 16, the sparse plants written out densely for the check program"""
+    depth, nc, n_bytes = 16, 1, cases.SPARSE_N_BYTES
+    for name, plant, caps in cases.sparse_plants(depth, n_bytes):
+        nodes = cases.sparse_nodes(depth, nc, plant)
+        values = [["0"] * (1 << (depth - level)) for level in range(depth + 1)]
+        for level, some in enumerate(nodes):
+            for i, b in some.items():
+                values[level][i] = format(b[0], "x")
+        text = " ".join(v for level in values for v in level)
+        full = cases.sparse_model(depth, n_bytes, nodes)
+        assert full["summary"][1] == caps[3] > 1
+        for cap in (1 << depth, caps[4]):
+            out = ask(exe, [f"audit {depth} {nc} {n_bytes} {cap} {text}"])
+            got = {w[0]: np.array([int(x) for x in w[1:]], dtype=np.uint64) for w in out}
+            want = cases.cut(full, cap)
+            assert got["summary"].tolist() == want["summary"], (name, cap)
+            for key in ("flags", "masks", "bad"):
+                assert np.array_equal(got[key], want[key]), (name, cap, key)
+
+
+@pytest.mark.parametrize("nc", cases.MANY_CURRENCIES)
+def test_many_currencies_agree_with_the_model_and_straddle_the_words(exe, nc):
+    """the plants that test_gpu_mst_audit.py adds for the flags kernel's bit gather, through the serial steps; and where they
+    put their bits in the workgroup's bit string: thread t of a workgroup is node t, its field bits t * nc .. t * nc + nc - 1"""
+    asked, wants, flags_seen, straddling = [], [], set(), set()
+    for depth in cases.MANY_DEPTHS:
+        for n_bytes in cases.MANY_N_BYTES:
+            for name, plant, caps in cases.many_currency_plants(depth, nc, n_bytes):
+                levels = cases.planted(depth, nc, n_bytes, plant)
+                for cap in caps:
+                    cap = (1 << depth) if cap is None else cap
+                    asked.append((levels, n_bytes, cap))
+                    wants.append(cases.model(levels, n_bytes, cap))
+                flags = wants[-1]["flags"]
+                flags_seen |= set(flags)
+                top = cases.top_of(n_bytes)
+                for node, balances in enumerate(b for level in levels for b in level):
+                    sh = (node % cases.THREADS) * nc % 64
+                    straddling |= {(c < 64 - sh) for c, v in enumerate(balances) if v >= top and sh + nc > 64}
+                if name == "every currency at every leaf":
+                    assert all(v >= top for b in levels[0] for v in b) and set(flags[:1 << depth]) == {1}
+    assert audits(exe, asked) == wants
+    assert flags_seen >= {0, 1, nc - 1, nc} | ({32, 33} & set(range(nc + 1)))
+    # out-of-range bits on both sides of a word's edge within one node's field -- or no field that crosses an edge at all
+    assert straddling == (set() if nc == 64 else {True, False})
+    assert [cases.straddling_leaf(256, n, n - 1) for n in cases.MANY_CURRENCIES] == [12, 1, 1, 256 // 3]
+
+
 # ============================================================================= the entry points: exports, scratch, refusals
 def test_exports_are_the_headers_prototypes():
     text = open(os.path.join(ROOT, "include", "summa_snapshot.h")).read()

@@ -142,6 +142,68 @@ def test_known_reports(models):
     assert models["empty_name_in_tree_file"]["row_leaf"] == [5, 1] and models["empty_name_in_tree_file"]["changed"] == [5]
 
 
+def test_the_numpy_model_is_the_model_on_every_case_of_fixed_width_names(models):
+    fixed = [c for c in CASES if cases.fixed_width(c[1]) and cases.fixed_width(c[2]) and len(c[1][0][0]) == len(c[2][0][0])]
+    assert {c[0].rsplit("_", 2)[0] for c in fixed} >= {"equal", "every_row_changed_shuffled", "edges_changed_shuffled", "edges_gone_shuffled",
+                                                        "twice_in_b", "twice_in_b_first_changed", "twice_in_a", "twice_in_a_gone"}
+    assert {"edges_gone_16386_sorted", "twice_in_a_257_file", "one_currency_65_sorted"} <= {c[0] for c in fixed}
+    for name, a, b, nc, sorted_tree in fixed:
+        want = models[name]
+        for cap in [None] + (cases.caps_of(want) if len(a) <= 257 else [1]):
+            want = models[name] if cap is None else cases.model(a, b, nc, sorted_tree, cap)
+            got = cases.model_np(cases.as_numbers(a), cases.as_numbers(b), sorted_tree, cap)
+            assert sorted(got) == sorted(want)
+            for key in want:
+                assert (got[key] if key in ("n_tree", "depth", "summary") else got[key].tolist()) == want[key], (name, cap, key)
+
+
+def test_the_big_case_is_built_from_the_edges_past_64_groups():
+    """what BIG is for -- a wave sums LANES group totals a trip -- and what the big case puts where, in both kinds of tree"""
+    assert (cases.LANES, cases.TRIP_ROWS, cases.BIG) == (64, 64 * cases.GROUP_ROWS, 65 * cases.GROUP_ROWS + 2) and cases.BIG == 1_064_962
+    group = lambda item: item // cases.GROUP_ROWS             # the groups before an item's own are 0 .. group - 1
+    trips = lambda item: -(-group(item) // cases.LANES)
+    assert [trips(cases.BIG - 3), trips(cases.BIG - 2), trips(cases.BIG - 1)] == [1, 2, 2] and group(cases.BIG - 3) == cases.LANES
+    assert trips(cases.TRIP_ROWS) == 1 and group(cases.TRIP_ROWS - 1) == cases.LANES - 1
+    assert (cases.BIG - 1).bit_length() == 21 and (1 << 21) // cases.GROUP_ROWS == 2 * cases.LANES and 10 ** (cases.BIG_WIDTH - 1) < cases.BIG
+    edge = 65 * cases.GROUP_ROWS
+    for sorted_tree in (False, True):
+        big = cases.big_case(sorted_tree)
+        a_keys, b1_keys = big["a"][0], big["b1"][0]
+        assert sorted(a_keys.tolist()) == list(range(cases.BIG)) and b1_keys.size == cases.BIG + 3 and big["b2"][0] is a_keys
+        m = cases.model_np(big["a"], big["b1"], sorted_tree)
+        for key, listed in (("changed", "changed"), ("gone", "gone"), ("new", "new")):
+            assert np.array_equal(m[listed], big[key]), (sorted_tree, key)
+        assert np.array_equal(np.flatnonzero(m["row_state"] == cases.ROW_SHADOWED), big["shadowed"])
+        assert m["summary"][:6] == [big["new"].size, 3, big["changed"].size, cases.BIG - big["new"].size - big["changed"].size,
+                                    big["gone"].size, 0]
+        # every list has items in every group up to 65, the groups' totals differ, and the places around the second trip are taken
+        for key, n_groups in (("changed", 66), ("gone", 66), ("new", 66)):
+            per_group = np.bincount(big[key] // cases.GROUP_ROWS, minlength=n_groups)
+            assert per_group.size == n_groups and per_group[:65].min() >= 1 and len(set(per_group.tolist())) >= 4, (sorted_tree, key)
+        assert {edge - 1, edge} <= set(big["changed"].tolist()) and {edge - 2, edge + 1} <= set(big["gone"].tolist())
+        assert {cases.GROUP_ROWS - 1, cases.GROUP_ROWS, cases.TRIP_ROWS - 1, cases.TRIP_ROWS} <= set(big["changed"].tolist())
+        if sorted_tree:
+            assert {edge - 1, edge, edge + 1} <= set(big["new"].tolist())
+        else:
+            assert np.array_equal(big["new"], big["gone"])
+        # the apply case: the same leaves change, every row is found, nothing else differs
+        m2 = cases.model_np(big["a"], big["b2"], sorted_tree)
+        assert np.array_equal(m2["changed"], big["changed"]) and m2["summary"] == [0, 0, big["changed"].size, cases.BIG - big["changed"].size, 0, 0, 0, 0]
+        assert cases.model_np(big["b2"], big["b2"], sorted_tree)["summary"][2:4] == [0, cases.BIG]
+
+
+def test_the_fixed_width_writer_writes_the_cases_text(tmp_path):
+    big = cases.big_case(False, 300)
+    keys, bal = big["b1"]
+    path = cases.write_big(tmp_path / "b1.csv", keys, bal)
+    rows = [(f"{k:07d}".encode(), [f"{v:08d}" for v in row]) for k, row in zip(keys.tolist(), bal.tolist())]
+    assert open(path).read() == cases.text_of(rows, 2)
+    m = cases.model_np(big["a"], big["b1"], False)
+    a_rows = [(f"{k:07d}".encode(), [str(v) for v in row]) for k, row in zip(big["a"][0].tolist(), big["a"][1].tolist())]
+    want = cases.model(a_rows, rows, 2, False)
+    assert all((m[key] if key in ("n_tree", "depth", "summary") else m[key].tolist()) == want[key] for key in want)
+
+
 # ============================================================================= the entry points: exports and refusals
 def test_exports_are_the_headers_prototypes_and_stay_out_of_the_other_headers():
     text = open(os.path.join(ROOT, "include", "summa_rounds.h")).read()

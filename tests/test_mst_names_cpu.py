@@ -165,6 +165,54 @@ def test_the_pool_reaches_a_third_group_with_almost_every_row_shadowed(exe, tmp_
     assert a["dups"][(count, True)]["summary"] == [300, count, count]
 
 
+def _same_as_model(got, want, what):
+    assert {k: (v if k == "summary" else v.tolist()) for k, v in got.items()} == want, what
+
+
+def test_the_numpy_model_is_the_model_on_every_case_and_the_pool():
+    text, _ = sort_cases.large(cases.LARGE, SORT_TILE)
+    generated = [c for c in ACCEPTED if c[0].rsplit("_", 1)[0] in cases.EDGE_SETS]
+    assert {c[0] for c in generated} >= {f"edges_{n}" for n in (65, 257, 16386)} | {f"none_{n}" for n in cases.SIZES}
+    for name, content in [(c[0], c[1]) for c in ACCEPTED] + [(cases.LARGE, text)]:
+        names = cases.names_of(content)
+        keys = cases.keys_of(names)
+        assert np.argsort(keys, kind="stable").tolist() == sort_cases.stable_order(names), name
+        count = cases.model(names)["summary"][1]
+        for cap in [None] + cases.caps_for(count):
+            for ordered in (True, False):
+                _same_as_model(cases.model_np(keys, cap, ordered), cases.model(names, cap, ordered), (name, cap, ordered))
+    # a name width: the family at 7 digits is the family, and the fixed-width writer writes what rows_text does
+    seven = cases.generated(257, "edges", 7)
+    assert [int(nm) for nm in seven] == [int(nm) for nm in cases.generated(257, "edges")] and {len(nm) for nm in seven} == {7}
+    keys = cases.keys_of([nm.encode() for nm in seven])
+    rows = np.arange(257)
+    body = cases.fixed_rows(keys, 7, [1000 * rows + 1, 1000 * rows + 2], 6).tobytes().decode()
+    assert body == "".join(f"{nm},{1000 * i + 1:06d},{1000 * i + 2:06d}\n" for i, nm in enumerate(seven))
+
+
+def test_the_big_case_is_built_from_the_edges_past_64_groups():
+    """what BIG is for -- a wave sums LANES group totals a trip -- and where the big case puts its shadowed positions"""
+    assert (cases.LANES, cases.TRIP_ROWS, cases.BIG) == (64, 64 * cases.GROUP_ROWS, 65 * cases.GROUP_ROWS + 2) and cases.BIG == 1_064_962
+    group = lambda item: item // cases.GROUP_ROWS             # the groups before an item's own are 0 .. group - 1
+    trips = lambda item: -(-group(item) // cases.LANES)
+    assert [trips(cases.BIG - 3), trips(cases.BIG - 2), trips(cases.BIG - 1)] == [1, 2, 2] and group(cases.BIG - 3) == cases.LANES
+    assert trips(cases.TRIP_ROWS) == 1 and group(cases.TRIP_ROWS - 1) == cases.LANES - 1 and 10 ** (cases.BIG_WIDTH - 1) < cases.BIG
+    edges = cases.big_edges()
+    assert {e + d for e in (cases.GROUP_ROWS, cases.TRIP_ROWS, 65 * cases.GROUP_ROWS) for d in (-1, 0, 1)} <= set(edges.tolist())
+    per_group = np.bincount(edges // cases.GROUP_ROWS, minlength=66)
+    assert per_group.size == 66 and per_group.min() >= 1 and (per_group[1:] != per_group[:-1]).all() and per_group[65] == 2
+    # the generator at a size Python affords is multiset's, and at BIG its sorted names repeat exactly at the edges
+    small = cases.big_keys(3 * cases.GROUP_ROWS + 2, "small")
+    assert sorted(f"{k:07d}" for k in small.tolist()) == cases.multiset(small.size, cases.big_edges(small.size).tolist(), 7)
+    keys = cases.big_keys()
+    order, same = cases.shadowed_positions(keys)
+    assert keys.size == cases.BIG and np.array_equal(np.flatnonzero(same), edges) and keys.max() == cases.BIG - 1 - edges.size
+    assert not np.array_equal(order, np.arange(cases.BIG))
+    m = cases.model_np(keys)
+    assert m["summary"][1:] == [edges.size, edges.size] and (m["shadowed"] > m["first"]).all()
+    assert np.array_equal(keys[m["shadowed"]], keys[m["first"]])
+
+
 @pytest.mark.parametrize("case", REFUSED, ids=[c[0] for c in REFUSED])
 def test_a_name_over_the_cap_is_reported(answers, case):
     a = answers[case[0]]
