@@ -251,6 +251,27 @@ def rounds_lib():
     return L
 
 
+# C ABI of a tree in HBM written back out as its snapshot CSV: the rows' lengths and positions, then the bytes
+# (include/summa_export.h), exported by the same library; errors go through sg_last_error
+EXPORT_EXPORTS = ["sx_mst_csv_scratch", "sx_mst_csv_measure_dev", "sx_mst_csv_write_dev"]
+EXPORT_ARGTYPES = {
+    "sx_mst_csv_scratch": [C.c_uint64, C.c_void_p],
+    "sx_mst_csv_measure_dev": [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_void_p],
+    "sx_mst_csv_write_dev": [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
+                             C.c_uint64, C.c_void_p, C.c_void_p],
+}
+
+
+def export_lib():
+    L = lib()
+    if not getattr(L, "_sx_ready", False):
+        for name in EXPORT_EXPORTS:
+            getattr(L, name).argtypes = EXPORT_ARGTYPES[name]
+        L._sx_ready = True
+    return L
+
+
 def check_prover(rc: int):
     if rc != SG_OK:
         raise SummaGpuError(rc, prover_lib().sp_last_error().decode())

@@ -260,9 +260,65 @@ class SnapshotDiff:
         return self._array("owner", np.uint32)
 
 
+class CsvExport:
+    """What `to_csv` wrote: `n_rows` rows and `size` bytes, the header line included; `ingest` says which way the text was made,
+    "device" (sx_mst_csv_measure_dev / sx_mst_csv_write_dev over the tree's text and balances in HBM) or "host" (from `entries`),
+    and `fallback_reason` why the host's."""
+
+    def __init__(self, n_rows, size, ingest, fallback_reason=None):
+        self.n_rows, self.size, self.ingest, self.fallback_reason = int(n_rows), int(size), ingest, fallback_reason
+
+    def __repr__(self):
+        return f"CsvExport(n_rows={self.n_rows}, size={self.size}, ingest={self.ingest!r}, fallback_reason={self.fallback_reason!r})"
+
+
+def _csv_delimiter(delimiter) -> str:
+    """one byte the reader takes as a delimiter (mst_diff_problem's rule): ASCII, no digit, quote, line end or NUL"""
+    if not isinstance(delimiter, str) or len(delimiter) != 1 or not delimiter.isascii() or delimiter in '"\r\n\0' or delimiter.isdigit():
+        raise ValueError("a delimiter the reader does not take")
+    return delimiter
+
+
+def _csv_header(cryptocurrencies, n_currencies: int, delimiter: str) -> str:
+    """`username`, then for every (name, chain) the delimiter and balance_<name>_<chain>, then the line end"""
+    crypto = [tuple(c) for c in cryptocurrencies or ()]
+    if not crypto:
+        raise ValueError("the tree has no cryptocurrency names and none are given")
+    if len(crypto) != n_currencies or any(len(c) != 2 for c in crypto):
+        raise ValueError("n_currencies (name, chain) pairs expected")
+    return delimiter.join(["username"] + [f"balance_{name}_{chain}" for name, chain in crypto]) + "\n"
+
+
 class _Tree:
     """What MerkleSumTree and DeviceMerkleSumTree share: everything that needs only `depth`, `n_currencies`, `entries` (None
     where a tree holds none), `is_sorted` and the class's `from_entries`."""
+
+    def to_csv(self, path: str, cryptocurrencies=None, delimiter=None) -> CsvExport:
+        """The snapshot CSV this tree commits to, from `entries` on the host, in the device reader's subset of CSV text: the header
+        line `username,balance_<name>_<chain>,..` of `cryptocurrencies` (default: the tree's own), then one row per named entry in
+        leaf order -- the name, then for each currency the delimiter (default ",") and the balance, then "\\n".  A balance is the
+        canonical integer in [0, r) of the leaf's field element in decimal: 007 comes out as 7, an integer >= r as its residue.
+        Padding entries (no name) are not written; duplicate names are written as they stand.  `from_csv` of the file has this
+        tree's root, and `from_csv_sorted` that of a sorted tree -- unless a padding leaf was given non-zero balances by
+        `update_leaves_at`: such a leaf has no name and is not written.
+        ValueError: a tree without cryptocurrency names when none are given; a tree that holds no entries (built from field
+        elements); a name with the delimiter, a quote, a line end, NUL or a non-ASCII byte in it, which would not read back as
+        the same snapshot."""
+        delim = _csv_delimiter("," if delimiter is None else delimiter)
+        header = _csv_header(cryptocurrencies or self.cryptocurrencies, self.n_currencies, delim)
+        if self.entries is None:
+            raise ValueError("a tree built from field elements holds no entries")
+        rows = []
+        for name, bal in self.entries:
+            if name is None:
+                continue
+            if not isinstance(name, str) or not name.isascii() or any(c in name for c in (delim, '"', "\r", "\n", "\0")):
+                raise ValueError(f"username {name!r} would not read back: the delimiter, a quote, a line end, NUL or a non-ASCII byte")
+            rows.append(delim.join([name] + [str(int(v) % R_MODULUS) for v in bal]))
+        text = (header + "".join(row + "\n" for row in rows)).encode()
+        with open(path, "wb") as f:
+            f.write(text)
+        return CsvExport(len(rows), len(text), "host")
 
     @classmethod
     def from_csv(cls, path: str, n_currencies: int, n_bytes: int = 8):
@@ -733,6 +789,10 @@ class DeviceMerkleSumTree(_Tree):
     balances in place without moving a leaf (sr_mst_apply_diff_dev: the balances are folded from the file's text in HBM and never
     visit the host), `apply_csv` does both.  The tree counts its updates, and a diff taken before another update is refused.
 
+    `to_csv` writes the snapshot the tree commits to NOW back out as a CSV the reader takes -- the names from the text in HBM, the
+    balances from `d_bals` as they are after any update or applied round (sx_mst_csv_measure_dev, sx_mst_csv_write_dev) -- when the
+    tree holds the names' order in HBM, else from `entries`; `csv_body_dev` leaves the rows on the device.
+
     `range_audit` says which users of the snapshot can receive a valid inclusion proof at all -- whose circuit would fail a range
     check, and at which one -- from the node balances in HBM (ss_mst_range_audit_dev); `explain_unprovable` names the balances."""
 
@@ -747,6 +807,7 @@ class DeviceMerkleSumTree(_Tree):
     _applied = ()             # the changed leaves of every device diff applied while the entries were unparsed
     _index_dev = None         # from_csv(name_index=True): the same record beside leaves in file order, plus "d_leaf_name_spans"
     name_index_reason = None  # from_csv(name_index=True) without an index: why
+    _csv_delim = None         # a device-read tree: the delimiter of its source file
 
     @property
     def entries(self):
@@ -914,6 +975,7 @@ class DeviceMerkleSumTree(_Tree):
             tree._sorted_dev = {"text": d_text, "size": size, "body_off": body_off, "delim": delim, "n": n, "d_order": d_order,
                                 "d_name_spans": d_name_spans}
         tree._csv_lazy = (path, {})
+        tree._csv_delim = delim
         tree.cryptocurrencies = crypto
         tree.csv_ingest = "device"
         return tree, None
@@ -1183,6 +1245,68 @@ class DeviceMerkleSumTree(_Tree):
         diff = self.diff_csv(path, cap)
         self.apply_diff(diff)
         return diff
+
+    def _csv_body_on_device(self, delimiter=None):
+        """-> (the body as a uint8 device tensor, None), or (None, why the device does not write this tree)"""
+        import torch
+        t = self._names_dev()
+        if t is None:
+            return None, "the tree holds no name index"
+        delim = _csv_delimiter(t["delim"] if delimiter is None else delimiter)
+        X = ffi.export_lib()
+        n, nc, stream = t["n"], self.n_currencies, ffi.current_stream_ptr()
+        leaf_spans = t.get("d_leaf_name_spans", t["d_name_spans"])     # a sorted tree's sorted spans are its leaves'
+        scratch_bytes, body_bytes = C.c_uint64(0), C.c_uint64(0)
+        ffi.check(X.sx_mst_csv_scratch(n, C.byref(scratch_bytes)))
+        d_row_off = torch.empty(n, dtype=torch.int32, device="cuda")
+        d_scratch = torch.empty(scratch_bytes.value // 4, dtype=torch.int32, device="cuda")
+        ffi.check(X.sx_mst_csv_measure_dev(ffi.dev_ptr(t["text"]), t["size"], t["body_off"], ffi.dev_ptr(leaf_spans), n, nc,
+                                           ffi.dev_ptr(self.d_bals), ffi.dev_ptr(d_row_off), ffi.dev_ptr(d_scratch), C.byref(body_bytes),
+                                           stream))
+        if body_bytes.value >= 1 << 32:
+            return None, "a body of 4 GiB or more"
+        d_out = torch.empty(body_bytes.value, dtype=torch.uint8, device="cuda")
+        ffi.check(X.sx_mst_csv_write_dev(ffi.dev_ptr(t["text"]), t["size"], t["body_off"], ffi.dev_ptr(leaf_spans), n, nc,
+                                         ffi.dev_ptr(self.d_bals), ord(delim), ffi.dev_ptr(d_row_off), body_bytes.value, ffi.dev_ptr(d_out),
+                                         stream))
+        return d_out, None
+
+    def csv_body_dev(self, delimiter=None):
+        """The body of `to_csv` -- every row behind the header line -- as a uint8 device tensor, made where the tree lies
+        (sx_mst_csv_measure_dev, sx_mst_csv_write_dev) and enqueued on the current stream: the names from the text the tree keeps
+        in HBM, the balances from `d_bals` as they are now in that stream's order.  The measure waits for the stream once, for the
+        body's length.  delimiter: the tree's own unless given.  ValueError for a tree without the names' order in HBM
+        (`has_name_index`) and for a body of 4 GiB or more."""
+        body, reason = self._csv_body_on_device(delimiter)
+        if body is None:
+            raise ValueError(reason)
+        return body
+
+    def to_csv(self, path: str, cryptocurrencies=None, delimiter=None) -> CsvExport:
+        """The snapshot CSV this tree commits to NOW, after any `update_leaves*`, `apply_diff` or `apply_csv` (_Tree.to_csv has
+        the text's rules).  A tree with the names' order in HBM (`has_name_index`: `from_csv_sorted`, `from_csv(name_index=True)`)
+        writes it where it lies: the header line on the host, `csv_body_dev`, one copy, one write.  That way parses no file and
+        reads nothing the host keeps of earlier updates: the balances are `d_bals`' and the names the text's.  A sorted tree is
+        written sorted, a tree in file order in file order, each with its own delimiter unless one is given; an un-updated tree in
+        file order gives a canonical source file (line ends "\\n", a final one, no leading zeros, values below r) back byte for
+        byte.  Any other tree goes the host's way, over `entries`, and the result says why (`ingest`, `fallback_reason`); there the
+        delimiter is that of the source file where the device read it, else ",", unless one is given.
+        A padding leaf given non-zero balances by `update_leaves_at` has no name and is not written: the file then reads back
+        to another root."""
+        t = self._names_dev()
+        if t is not None:                                     # refused before any device work
+            delimiter = _csv_delimiter(t["delim"] if delimiter is None else delimiter)
+            header = _csv_header(cryptocurrencies or self.cryptocurrencies, self.n_currencies, delimiter).encode()
+        body, reason = self._csv_body_on_device(delimiter)
+        if body is None:
+            done = super().to_csv(path, cryptocurrencies, self._csv_delim if delimiter is None else delimiter)
+            done.fallback_reason = reason
+            return done
+        data = body.cpu().numpy()
+        with open(path, "wb") as f:
+            f.write(header)
+            data.tofile(f)
+        return CsvExport(self._names_dev()["n"], len(header) + data.size, "device")
 
     def _balances_of_leaves(self, leaves):
         """the balances of some leaves as integers from their rows of `d_bals`: one gather and one copy"""
