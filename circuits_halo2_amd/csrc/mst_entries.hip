@@ -268,3 +268,4 @@ hipError_t mst_csv_split_launch(const uint8_t* d_body, uint64_t body_len, const 
 #include "mst_names.cuh"  // the names beside a tree in file order: the spans in file order, the report of repeated names
 #include "mst_diff.cuh"   // the next round's file against the tree: the join by name, the report, the changed balances packed
 #include "mst_export.cuh" // the tree written back out as its snapshot CSV: the rows' lengths and positions, the bytes
+#include "mst_admit.cuh"  // a round settled in full: new users into the padding, the index extended, the gone zeroed, one run

@@ -272,6 +272,29 @@ def export_lib():
     return L
 
 
+# C ABI of a round settled in full: the new users admitted into the tree's padding, the name index extended, the gone users zeroed,
+# one run of the update's kernels (include/summa_admit.h), exported by the same library; errors go through sg_last_error
+ADMIT_EXPORTS = ["sa_mst_admit_scratch", "sa_mst_admit_measure_dev", "sa_mst_settle_dev"]
+ADMIT_ARGTYPES = {
+    "sa_mst_admit_scratch": [C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p],
+    "sa_mst_admit_measure_dev": [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
+                                 C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "sa_mst_settle_dev": [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                          C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
+                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+}
+
+
+def admit_lib():
+    L = lib()
+    if not getattr(L, "_sa_ready", False):
+        for name in ADMIT_EXPORTS:
+            getattr(L, name).argtypes = ADMIT_ARGTYPES[name]
+        L._sa_ready = True
+    return L
+
+
 def check_prover(rc: int):
     if rc != SG_OK:
         raise SummaGpuError(rc, prover_lib().sp_last_error().decode())

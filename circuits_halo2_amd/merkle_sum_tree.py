@@ -219,8 +219,12 @@ class SnapshotDiff:
       ingest, fallback_reason   "device" (both texts were joined in HBM, sr_mst_csv_diff_dev) or "host" (from `entries`), and why
       row_leaf(), row_state(), leaf_state(), owner()   the arrays as numpy (on the device way they stay in HBM until asked for): per
                          row its leaf or 0xFFFFFFFF and its state (ROW_*), per leaf of all 2^depth its state (LEAF_*) and owner row
-    A diff is of the tree as it was: `apply_diff` refuses it after another update.  New users are not inserted and gone users are
-    not zeroed by an apply -- a leaf's username is fixed in a built tree --, so n_new or n_gone above 0 says that a rebuild is due."""
+      admitted           the range of leaves the NEW rows go to under `apply_diff(admit_new=True)`: the j-th new row becomes leaf
+                         n_tree + j.  A round fits while admitted.stop <= 2^depth (`tree.free_leaves` >= n_new)
+    A diff is of the tree as it was: `apply_diff` refuses it after another update.  A plain apply writes the changed balances alone:
+    new users are not inserted and gone users are not zeroed unless `apply_diff` is asked to (`admit_new`, `zero_gone`), which
+    settles the round in place.  A rebuild is still due when the new users no longer fit the padding (the depth has to grow), when
+    the tree is sorted or holds no name index, and to drop the zeroed rows of gone users for good."""
 
     LEAF_PADDING, LEAF_SAME, LEAF_CHANGED, LEAF_GONE, LEAF_UNREACHABLE = 0, 1, 2, 3, 4
     ROW_SAME, ROW_CHANGED, ROW_NEW, ROW_SHADOWED = 1, 2, 3, 4
@@ -233,11 +237,15 @@ class SnapshotDiff:
         self.ingest, self.fallback_reason = ingest, fallback_reason
         self.new_balances = new_balances       # the host way: the owner row's balances for every changed leaf, in the list's order
         self._dev = dev                        # the device way: what sr_mst_apply_diff_dev takes
-        self._tree, self._epoch = None, None
+        self._tree, self._epoch, self._n_tree = None, None, None
 
     @property
     def ok(self) -> bool:
         return self.n_new == self.n_changed == self.n_gone == 0
+
+    @property
+    def admitted(self) -> range:
+        return range(self._n_tree, self._n_tree + self.n_new)
 
     def summary(self):
         return {"new": self.n_new, "shadowed": self.n_shadowed_rows, "changed": self.n_changed, "same": self.n_same, "gone": self.n_gone,
@@ -425,8 +433,10 @@ class _Tree:
                 continue
             same = [v % R_MODULUS for v in entries[row][1]] == [v % R_MODULUS for v in self.entries[leaf][1]]
             row_state[row], leaf_state[leaf] = (D.ROW_SAME, D.LEAF_SAME) if same else (D.ROW_CHANGED, D.LEAF_CHANGED)
+        n_named = 0
         for leaf, (name, _) in enumerate(self.entries):
             if isinstance(name, str):
+                n_named += 1
                 if first[name] != leaf:
                     leaf_state[leaf] = D.LEAF_UNREACHABLE
                 elif owner[leaf] == D.ABSENT:
@@ -439,8 +449,16 @@ class _Tree:
         diff = SnapshotDiff(counts, changed, new_rows[:listed], gone[:listed],
                             {"row_leaf": row_leaf, "row_state": row_state, "leaf_state": leaf_state, "owner": owner}, "host",
                             new_balances=[list(entries[owner[leaf]][1]) for leaf in changed.tolist()])
-        diff._tree, diff._epoch = self, self._updates
+        diff._tree, diff._epoch, diff._n_tree = self, self._updates, n_named
         return diff
+
+    @property
+    def free_leaves(self) -> int:
+        """2^depth less the named leaves: how many new users `apply_diff(admit_new=True)` can still admit before the depth has to
+        grow"""
+        if self.entries is None:
+            raise ValueError("a tree built from field elements holds no entries")
+        return sum(1 for name, _ in self.entries if name is None)
 
     def diff_csv(self, path: str, cap=None) -> SnapshotDiff:
         """`diff_entries` of the next round's CSV, parsed on the host"""
@@ -788,6 +806,9 @@ class DeviceMerkleSumTree(_Tree):
     both texts lie when the tree holds the names' order (sr_mst_csv_diff_dev), else from `entries`; `apply_diff` writes the changed
     balances in place without moving a leaf (sr_mst_apply_diff_dev: the balances are folded from the file's text in HBM and never
     visit the host), `apply_csv` does both.  The tree counts its updates, and a diff taken before another update is refused.
+    With `admit_new=True` and `zero_gone=True` the apply settles the round in full (sa_mst_admit_measure_dev, sa_mst_settle_dev):
+    the new users become leaves in the padding behind the named ones, the name index and the text in HBM grow by them, the gone
+    users' balances become zero, and all of it is one run of the update's kernels.  `free_leaves` says how many still fit.
 
     `to_csv` writes the snapshot the tree commits to NOW back out as a CSV the reader takes -- the names from the text in HBM, the
     balances from `d_bals` as they are after any update or applied round (sx_mst_csv_measure_dev, sx_mst_csv_write_dev) -- when the
@@ -818,7 +839,11 @@ class DeviceMerkleSumTree(_Tree):
             parsed, _ = parse_csv_to_entries(path, self.n_currencies)
             if self._sorted_dev is not None:                  # the device's order: one copy and no host sort
                 parsed = [parsed[i] for i in self._sorted_dev["d_order"].cpu().tolist()]
+            n_file = len(parsed)
             parsed += [(None, [0] * self.n_currencies)] * ((1 << self.depth) - len(parsed))
+            if self._index_dev is not None and self._index_dev["n"] > n_file:     # admitted since: the names from the text in HBM
+                for j, name in enumerate(self._names_of_leaves(n_file, self._index_dev["n"])):
+                    parsed[n_file + j] = (name, parsed[n_file + j][1])
             if self._applied:                                 # leaves an applied diff changed: their balances are d_bals'
                 leaves = np.unique(np.concatenate(self._applied))
                 for i, bal in zip(leaves.tolist(), self._balances_of_leaves(leaves)):
@@ -1072,18 +1097,34 @@ class DeviceMerkleSumTree(_Tree):
         leaf_spans = d.get("d_leaf_name_spans", d["d_name_spans"])
         begin, end = (int(x) & 0xFFFFFFFF for x in leaf_spans[2 * index:2 * index + 2].cpu().tolist())
         lo, text = d["body_off"] + begin, b""
-        want = end - begin + 1 + 24 * nc
-        while b"\n" not in text[end - begin:] and lo + len(text) < d["size"]:       # the row ends at its line end or the file's
-            text = bytes(d["text"][lo:min(d["size"], lo + want)].cpu().numpy())
-            want *= 4
-        row = text[end - begin + 1:].split(b"\n")[0].rstrip(b"\r")
         if index in self._csv_lazy[1]:
             balances = self._csv_lazy[1][index]
         elif any(a[min(int(np.searchsorted(a, index)), a.size - 1)] == index for a in self._applied):
-            balances = self._balances_of_leaves([index])[0]   # an applied diff changed it: the leaf's own row of d_bals says what it holds
+            balances = self._balances_of_leaves([index])[0]   # an applied diff wrote it: the leaf's own row of d_bals says what it holds
         else:
-            balances = [int(x) for x in row.split(d["delim"].encode())]
-        return (text[:end - begin].decode(), balances)
+            balances = None
+        if balances is not None:                              # the name alone: an admitted leaf has no row behind it
+            return (bytes(d["text"][lo:lo + end - begin].cpu().numpy()).decode(), balances)
+        want = end - begin + 1 + 24 * nc
+        size = d.get("file_size", d["size"])                  # the source file's own end: admitted names lie behind it, unseparated
+        while b"\n" not in text[end - begin:] and lo + len(text) < size:           # the row ends at its line end or the file's
+            text = bytes(d["text"][lo:min(size, lo + want)].cpu().numpy())
+            want *= 4
+        row = text[end - begin + 1:].split(b"\n")[0].rstrip(b"\r")
+        return (text[:end - begin].decode(), [int(x) for x in row.split(d["delim"].encode())])
+
+    def _names_of_leaves(self, lo: int, hi: int):
+        """the names of the admitted leaves lo .. hi - 1 from the text in HBM, where they lie one after the other: two small copies"""
+        d = self._index_dev
+        spans = [int(x) & 0xFFFFFFFF for x in d["d_leaf_name_spans"][2 * lo:2 * hi].cpu().tolist()]
+        first = spans[0]
+        blob = bytes(d["text"][d["body_off"] + first:d["body_off"] + spans[-1]].cpu().numpy())
+        return [blob[b - first:e - first].decode() for b, e in zip(spans[0::2], spans[1::2])]
+
+    @property
+    def free_leaves(self) -> int:
+        d = self._names_dev()
+        return (1 << self.depth) - d["n"] if d is not None else super().free_leaves
 
     def get_entry(self, index: int):
         """tree.rs's get_entry; on a tree with the names' order in HBM whose entries are unparsed from the row's text there, no parse"""
@@ -1203,47 +1244,123 @@ class DeviceMerkleSumTree(_Tree):
         diff = SnapshotDiff(list(summary)[:6], take(d_changed, int(summary[2])), take(d_new, int(summary[6])), take(d_gone, int(summary[7])),
                             {"row_leaf": d_row_leaf, "row_state": d_row_state, "leaf_state": d_leaf_state, "owner": d_owner}, "device",
                             dev={"text": d_text, "size": size, "body_off": body_off, "n": n, "d_spans": d_spans, "d_owner": d_owner,
-                                 "d_changed": d_changed})
-        diff._tree, diff._epoch = self, self._updates
+                                 "d_changed": d_changed, "d_new": d_new, "d_gone": d_gone, "d_row_state": d_row_state,
+                                 "d_leaf_state": d_leaf_state})
+        diff._tree, diff._epoch, diff._n_tree = self, self._updates, t["n"]
         return diff, None
 
-    def apply_diff(self, diff: SnapshotDiff):
+    def apply_diff(self, diff: SnapshotDiff, admit_new: bool = False, zero_gone: bool = False):
         """Write the changed balances of `diff` into the tree in place and return the new root.  A device diff's balances are folded
         once more where the file's text lies and go through the update's kernels (sr_mst_apply_diff_dev): they never visit the
         host; only the list of changed leaves does, for the plan of the levels.  A host diff goes through `update_leaves_at`.
-        New users are not inserted and gone users are not zeroed.  ValueError for a diff taken of another tree, or of this tree
-        before another update: the tree is untouched."""
+        With both keywords at their defaults new users are not inserted and gone users are not zeroed.
+        zero_gone: every GONE leaf of the diff also gets zero balances.  Its username, its place and its entry in the name index
+        stay: a lookup still finds it, `to_csv` writes it as name,0,0 and a later diff of the same file still calls it GONE, with
+        nothing to change.  The liabilities leave the committed sums; the row stays until a rebuild drops it.  UNREACHABLE leaves
+        are not touched.  Every tree and both ingests.
+        admit_new: every NEW row of the diff also becomes a leaf, the j-th in the file's order leaf `diff.admitted[j]`, in the
+        padding behind the named leaves: username and balances as `from_csv` makes them, from the text in HBM; a name twice among
+        the new rows gets two leaves, the later one shadowed (`duplicate_names`).  The tree's text and name index in HBM grow by
+        the names and the tree answers by name as a fresh tree of the same leaves would.  Needs a device diff of a tree in file
+        order with a name index (`from_csv(name_index=True)`): a sorted tree's leaves are its order.
+        With either keyword a device diff is settled by sa_mst_admit_measure_dev / sa_mst_settle_dev: changed, gone and admitted
+        leaves in ONE run of the leaf and level kernels.
+        ValueError, with the tree untouched: a diff taken of another tree, or of this tree before another update; admit_new on a
+        sorted tree, a tree without a name index or a host diff; more new rows than `free_leaves` (the depth has to grow: the
+        rebuild that really is due); a new row with a name of more than 64 bytes; a text in HBM that would reach 4 GiB; a diff whose
+        `cap` left the list that is asked for incomplete."""
         import torch
         if diff._tree is not self:
             raise ValueError("a diff of another tree")
         if diff._epoch != self._updates:
             raise ValueError("a diff taken before another update of the tree")
-        if diff.n_changed == 0:
+        if admit_new:
+            if diff.ingest != "device":
+                raise ValueError("admit_new needs a device diff: the host's way admits nobody")
+            if self._index_dev is None:
+                raise ValueError("admit_new needs a tree in file order with a name index (from_csv(name_index=True)): "
+                                 "a sorted tree's leaves are its order")
+            if len(diff.new_rows) != diff.n_new:
+                raise ValueError("the diff's cap left the list of new rows incomplete")
+            if diff.admitted.stop > 1 << self.depth:
+                raise ValueError(f"{diff.n_new} new users and {self.free_leaves} free leaves: the depth has to grow, a rebuild is due")
+        if zero_gone and len(diff.gone) != diff.n_gone:
+            raise ValueError("the diff's cap left the list of gone leaves incomplete")
+        n_new, n_gone = diff.n_new if admit_new else 0, diff.n_gone if zero_gone else 0
+        if diff.n_changed + n_new + n_gone == 0:
             return self.root()
         if diff.ingest != "device":
-            return self.update_leaves_at(diff.changed.tolist(), diff.new_balances)
+            zeros = [[0] * self.n_currencies] * n_gone
+            return self.update_leaves_at(diff.changed.tolist() + diff.gone.tolist()[:n_gone], list(diff.new_balances) + zeros)
         d = diff._dev
-        ffi.check(ffi.rounds_lib().sr_mst_apply_diff_dev(ffi.dev_ptr(d["text"]), d["size"], d["body_off"], ffi.dev_ptr(d["d_spans"]), d["n"],
-                                                         ffi.dev_ptr(d["d_owner"]), ffi.dev_ptr(d["d_changed"]), diff.n_changed, self.depth,
-                                                         self.n_currencies, ffi.dev_ptr(self.d_users), ffi.dev_ptr(self.d_bals),
-                                                         ffi.dev_ptr(self.d_h), ffi.dev_ptr(self.d_b), ffi.current_stream_ptr()))
+        touched = diff.changed
+        if admit_new or zero_gone:
+            self._settle_dev(diff, n_new, n_gone)
+            touched = np.sort(np.concatenate([diff.changed, diff.gone[:n_gone], np.array(diff.admitted[:n_new], dtype=np.uint32)]))
+        else:
+            ffi.check(ffi.rounds_lib().sr_mst_apply_diff_dev(ffi.dev_ptr(d["text"]), d["size"], d["body_off"], ffi.dev_ptr(d["d_spans"]), d["n"],
+                                                             ffi.dev_ptr(d["d_owner"]), ffi.dev_ptr(d["d_changed"]), diff.n_changed, self.depth,
+                                                             self.n_currencies, ffi.dev_ptr(self.d_users), ffi.dev_ptr(self.d_bals),
+                                                             ffi.dev_ptr(self.d_h), ffi.dev_ptr(self.d_b), ffi.current_stream_ptr()))
         torch.cuda.current_stream().synchronize()             # for the constructor's reason, as _update_dev
         self._updates += 1
         self._root = None
         if self._csv_lazy is not None:                        # entries nobody has read yet: these leaves' balances are d_bals' now
-            self._applied = tuple(self._applied) + (diff.changed,)
+            self._applied = tuple(self._applied) + (touched,)
             if self._csv_lazy[1]:
-                for i in diff.changed.tolist():
+                for i in touched.tolist():
                     self._csv_lazy[1].pop(i, None)
         elif self._entries is not None:
-            for i, bal in zip(diff.changed.tolist(), self._balances_of_leaves(diff.changed)):
-                self._entries[i] = (self._entries[i][0], bal)
+            names = dict(zip(diff.admitted, self._names_of_leaves(diff.admitted.start, diff.admitted.stop))) if n_new else {}
+            for i, bal in zip(touched.tolist(), self._balances_of_leaves(touched)):
+                self._entries[i] = (names.get(i, self._entries[i][0]), bal)
+        if n_new:
+            self._name_index = None                           # update_leaves' own: names were added
         return self.root()
 
-    def apply_csv(self, path: str, cap=None) -> SnapshotDiff:
+    def _settle_dev(self, diff: SnapshotDiff, n_new: int, n_gone: int):
+        """sa_mst_admit_measure_dev (for new rows) and sa_mst_settle_dev on the current stream; every refusal comes before anything
+        of the tree is written, and the new text and index replace the old ones only behind a settle that was accepted"""
+        import torch
+        A, d, t = ffi.admit_lib(), diff._dev, self._names_dev()
+        nc, stream = self.n_currencies, ffi.current_stream_ptr()
+        opt = lambda x: ffi.dev_ptr(x) if x is not None else None
+        outs, d_scratch, name_bytes = {}, None, C.c_uint64(0)
+        if n_new:
+            scratch_bytes, problem = C.c_uint64(0), C.c_uint64(0)
+            ffi.check(A.sa_mst_admit_scratch(d["n"], nc, n_new, C.byref(scratch_bytes)))
+            d_scratch = torch.empty(scratch_bytes.value, dtype=torch.uint8, device="cuda")
+            ffi.check(A.sa_mst_admit_measure_dev(ffi.dev_ptr(d["text"]), d["size"], d["body_off"], ffi.dev_ptr(d["d_spans"]), d["n"], nc,
+                                                 ffi.dev_ptr(d["d_row_state"]), ffi.dev_ptr(d["d_new"]), n_new, t["n"], self.depth,
+                                                 ffi.dev_ptr(d_scratch), C.byref(name_bytes), C.byref(problem), stream))
+            if problem.value:
+                torch.cuda.current_stream().synchronize()
+                raise ValueError(f"row {problem.value >> 8}: {_CSV_ROW_PROBLEMS.get(problem.value & 0xff, 'a name of more than 64 bytes')}")
+            if t["size"] - t["body_off"] + name_bytes.value >= 1 << 32:
+                torch.cuda.current_stream().synchronize()
+                raise ValueError("the tree's text would reach 4 GiB with the new names appended")
+            pad, n_all = -t["body_off"] % 16, t["n"] + n_new      # the body on a 16-byte boundary, as the reader placed it
+            i32 = lambda count: torch.empty(count, dtype=torch.int32, device="cuda")
+            d_file = torch.empty(pad + t["size"] + name_bytes.value, dtype=torch.uint8, device="cuda")
+            # file_size: where the source file's own text ends; the rows are read up to there, the names behind it through spans
+            outs = {"text": d_file[pad:], "size": t["size"] + name_bytes.value, "file_size": t.get("file_size", t["size"]), "n": n_all,
+                    "d_order": i32(n_all), "d_name_spans": i32(2 * n_all), "d_leaf_name_spans": i32(2 * n_all)}
+        index = t if n_new else {}
+        ffi.check(A.sa_mst_settle_dev(ffi.dev_ptr(d["text"]), d["size"], d["body_off"], ffi.dev_ptr(d["d_spans"]), d["n"], nc,
+                                      ffi.dev_ptr(d["d_owner"]), ffi.dev_ptr(d["d_leaf_state"]), ffi.dev_ptr(d["d_changed"]), diff.n_changed,
+                                      opt(d["d_gone"]) if n_gone else None, n_gone, opt(d["d_new"]) if n_new else None, n_new,
+                                      opt(d_scratch), opt(index.get("text")), index.get("size", 0), index.get("body_off", 0),
+                                      opt(index.get("d_name_spans")), opt(index.get("d_order")), opt(index.get("d_leaf_name_spans")), t["n"],
+                                      self.depth, opt(outs.get("text")), name_bytes.value, opt(outs.get("d_name_spans")),
+                                      opt(outs.get("d_order")), opt(outs.get("d_leaf_name_spans")), ffi.dev_ptr(self.d_users),
+                                      ffi.dev_ptr(self.d_bals), ffi.dev_ptr(self.d_h), ffi.dev_ptr(self.d_b), stream))
+        if n_new:
+            self._index_dev = dict(t, **outs)
+
+    def apply_csv(self, path: str, cap=None, admit_new: bool = False, zero_gone: bool = False) -> SnapshotDiff:
         """`diff_csv` followed by `apply_diff`; returns the diff"""
         diff = self.diff_csv(path, cap)
-        self.apply_diff(diff)
+        self.apply_diff(diff, admit_new=admit_new, zero_gone=zero_gone)
         return diff
 
     def _csv_body_on_device(self, delimiter=None):
@@ -1347,7 +1464,7 @@ class DeviceMerkleSumTree(_Tree):
         """The usernames that occur more than once.  A tree with the names' order in HBM (`has_name_index`) answers from there in
         one device call (ss_mst_duplicate_names_dev) on the current stream, one small copy for the summary and one for each list,
         and parses nothing; any other tree answers from `entries` on the host.  cap: list at most that many shadowed leaves
-        (None: all).  Updates never change names, so the report holds for the life of the tree."""
+        (None: all).  Updates never change names, so the report holds until `apply_diff(admit_new=True)` adds some."""
         import torch
         d = self._names_dev()
         if d is None:
